@@ -2,29 +2,39 @@
 """bench.py -- SpGEMM GFLOP/s (2 * intermediate products / s) for A*A, the metric of BASELINE.json.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload scircuit|...] [--scaling weak|strong]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one COMPLETE MultiplyspECK call with A and B resident in HBM and the output matrix reused across
 steps (the reference's benchmark loop, source/Executor.cpp:43-72): analysis -> binning -> symbolic -> scan ->
 allocation check -> numeric (+ in-kernel sort), every stage inside the timed region, as the reference runs them in
 every iteration (source/GPU/Multiply.cu:488-575, 835-1043).  `value` / `ms_per_step` are THAT call (library option
-reuse = 0).  The structure-reuse mode of a repeated identical call (the replayed sequence) is
-reported beside it as `value_reuse` / `ms_reuse` at N = 1 and is never the metric.
+reuse = 0), timed over exactly K steps after W warm-up steps.
 
-stdout carries ONE JSON line (<= 4 KB, no prose).  Everything else -- every launch with bytes / duration / ceilings,
-rows per class, the verification details of every leg -- goes to --detail (default bench_detail.json next to this
-file; scripts/check_launch_ms.py and the profiles/ regeneration read that).
+A plain run does only that: it sets up, warms up, times the K steps, writes the output of the last step if
+--dump-outputs DIR is given, and prints ONE JSON line (no prose).  Everything else needs --full:
+
+* the structure-reuse mode of a repeated identical call (the replayed sequence), reported beside the
+  metric as `value_reuse` / `ms_reuse` at N = 1 and never the metric;
+* the profiled pre-pass behind `phases_ms` and `roofline`, and the --detail file (default bench_detail.json next to
+  this file: every launch with bytes / duration / ceilings, rows per class, the verification details of every leg;
+  scripts/check_launch_ms.py and the profiles/ regeneration read that);
+* the check of the last timed step's output (the reference compares after every iteration, source/Executor.cpp:51-55,
+  67-71): against the CPU oracle in full (indices bit-exact, values within 1e-12 * sum|a*b|), the nlpkkt leg through
+  size-independent properties on the device plus the oracle on sampled row blocks (oracle/verify.py).  `verified` is
+  false -- and the exit code 3 -- if any check of any leg fails;
+* at N = 1 `configs`: the other single-GPU configurations of BASELINE.json, one short object each; unless
+  --no-config5 `config5`: the nlpkkt160 stand-in, strong scaling, at this N; `lib_baseline` (rocSPARSE) and
+  `cpu_baseline` (the CPU oracle); at N > 1 `multiply_only`.
+The --no-* options switch single legs of --full off.
 
 N > 1 (torch.distributed.run, or started here when no launcher did): rows of A are sharded by the analysis pass'
 product counts, B is replicated, every step ends with ONE exchange: the gatherv of the C shards to rank 0
 (speck_gather_* of the C ABI over RCCL).  `value` includes the exchange, `multiply_only` is the same steps with C
 left row-sharded.  --scaling weak (default): N x the rows; --scaling strong: the same matrix at every N.
-Unless --no-config5 the line carries `config5`: the nlpkkt160 stand-in, strong scaling, at this N.
-At N = 1 the line carries `configs`: the other single-GPU configurations of BASELINE.json, one short object each.
 
-The output of the LAST timed step is downloaded and checked (the reference compares after every iteration,
-source/Executor.cpp:51-55, 67-71): against the CPU oracle in full (indices bit-exact, values within
-1e-12 * sum|a*b|), the nlpkkt leg through size-independent properties on the device plus the oracle on sampled row
-blocks (oracle/verify.py).  `verified` is false -- and the exit code 3 -- if any check of any leg fails.
+--dump-outputs DIR writes the output matrix C of the last timed step -- what the caller of MultiplyspECK receives;
+at N > 1 the matrix the exchange gathered on rank 0 -- as DIR/C_*.npy (dump_outputs).  The inputs are generated from
+--seed, so the same arguments give the same inputs in every run and two builds can be compared output for output.
 
 Inputs: $SPECK_MTX_DIR/<name>.mtx (scircuit, webbase-1M, mac_econ_fwd500, cant, nlpkkt160) is used when present
 ("data": "suitesparse"); SuiteSparse files do not exist offline, so the default is the stand-in of SURVEY.md 8d
@@ -238,6 +248,7 @@ class Job:
         self.plan = None
         self.n_step = 0
         self.last = None  # (config, output matrix) of the last step
+        self.gathered = None  # rank 0 with the exchange: what the exchange of the last step delivered
         self.bounds = (0, A.rows) if env.world == 1 else (bounds[env.rank], bounds[env.rank + 1])
 
     def set_reuse(self, on):
@@ -270,7 +281,9 @@ class Job:
 
     def drain(self):
         if self.plan is not None:
-            self.plan.wait_all()
+            got = self.plan.wait_all()[(self.n_step - 1) % len(self.slots)]
+            if got is not None:
+                self.gathered = got
 
     def barrier(self):
         self.drain()
@@ -471,9 +484,60 @@ def verify_last_output(env, job, A, mode, cache):
     return info
 
 
-def measure(env, A, steps, warmup, gather, profile, verify=None, reuse=False):
-    """One leg.  Returns a result dict on every rank: the COMPLETE call timed (`ms_per_step`), and with `reuse` the
-    structure-reuse mode of the same repeated call beside it (`ms_reuse`)."""
+DUMP_BYTES = 64_000_000  # --dump-outputs: all files together
+
+
+def _positions(n, cap, seed):
+    """None (keep all n) or a fixed, seeded, sorted sample of at most cap of the positions 0 .. n-1."""
+    if n <= cap:
+        return None
+    return np.unique(np.random.default_rng(seed).integers(0, n, size=cap))
+
+
+def dump_outputs(directory, rows, cols, row_offsets, col_ids, values):
+    """--dump-outputs: C as DIR/C_shape.npy ([rows, cols, nnz]), C_row_offsets.npy, C_col_ids.npy (float64: exact
+    below 2^53) and C_values.npy (the value type of the run).  What exceeds DUMP_BYTES is cut to a fixed seeded sample
+    of positions, written beside it as C_row_offsets_index.npy / C_entry_index.npy; the same C gives the same sample."""
+    os.makedirs(directory, exist_ok=True)
+    values = np.asarray(values)
+    nnz = len(values)
+    budget = DUMP_BYTES - 6 * 128  # (npy headers)
+    out = {"C_shape": np.array([rows, cols, nnz], dtype=np.float64)}
+    ro = np.asarray(row_offsets)
+    keep = _positions(len(ro), budget // 4 // 16, 1)  # the row offsets take at most a quarter (value + index)
+    out["C_row_offsets"] = (ro if keep is None else ro[keep]).astype(np.float64)
+    if keep is not None:
+        out["C_row_offsets_index"] = keep.astype(np.float64)
+    left = budget - sum(a.nbytes for a in out.values())
+    per = 8 + values.dtype.itemsize
+    keep = None if nnz * per <= left else _positions(nnz, left // (per + 8), 2)
+    out["C_col_ids"] = (col_ids if keep is None else col_ids[keep]).astype(np.float64)
+    out["C_values"] = values if keep is None else values[keep]
+    if keep is not None:
+        out["C_entry_index"] = keep.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
+def dump_last_output(env, job, directory):
+    """The output of the last step: this process' C at N = 1, the gathered C on rank 0 at N > 1."""
+    if env.world == 1:
+        h = job.last[1].to_host()
+        dump_outputs(directory, h.rows, h.cols, h.row_offsets, h.col_ids, h.data)
+    elif env.rank == 0:
+        got = job.gathered
+        if isinstance(got, sa.dCSR):
+            h = got.to_host()
+            dump_outputs(directory, h.rows, h.cols, h.row_offsets, h.col_ids, h.data)
+        else:
+            ro, col, val = (t.cpu().numpy() for t in got)
+            dump_outputs(directory, len(ro) - 1, job.dA.cols, ro, col.view(np.uint32), val)
+
+
+def measure(env, A, steps, warmup, gather, profile, verify=None, reuse=False, multiply_only=True, dump=None):
+    """One leg.  Returns a result dict on every rank: the COMPLETE call timed (`ms_per_step`), with `reuse` the
+    structure-reuse mode of the same repeated call beside it (`ms_reuse`), at N > 1 with `multiply_only` the same steps
+    without the exchange.  `dump`: directory for the output of the last timed step (dump_last_output)."""
     job = Job(env, A, gather)
     job.set_reuse(False)
     out = {}
@@ -487,6 +551,8 @@ def measure(env, A, steps, warmup, gather, profile, verify=None, reuse=False):
     for _ in range(max(warmup, len(job.slots) + 1)):
         job.step()
     elapsed = job.timed(steps)
+    if dump:
+        dump_last_output(env, job, dump)
     out["speculated"] = job.cfg.last_stats()["eager_speculated"]
     out["through"] = job.cfg.last_stats().get("eager_through", 0)  # 1: the timed complete calls were enqueued as one batch
     cache = {}
@@ -510,7 +576,7 @@ def measure(env, A, steps, warmup, gather, profile, verify=None, reuse=False):
     # N > 1, reported next to `value` (never instead of it): the same K steps without the exchange,
     # i.e. what the row-sharded multiply alone sustains while C stays distributed like A
     out["multiply_only"] = None
-    if job.gather:
+    if job.gather and multiply_only:
         e2 = job.timed(steps, exchange=False)
         out["multiply_only"] = {"value": round(2.0 * out["P"] / (e2 / steps) / 1e9, 3), "ms_per_step": round(e2 * 1e3 / steps, 4)}
     # the structure-reuse mode of the same repeated call: reported beside the metric, never as it
@@ -586,14 +652,23 @@ def main():
     ap.add_argument("--configs-steps", type=int, default=20)
     ap.add_argument("--config5-scale", type=float, default=1.0)
     ap.add_argument("--config5-steps", type=int, default=5)
-    ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"), help="file for everything the line omits")
+    ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"),
+                    help="--full: file for everything the line omits")
     ap.add_argument("--opt", action="append", default=[], help="library option name=value (tuning)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output matrix of the last timed step as DIR/C_*.npy (at most 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side legs: reuse mode, profile / roofline, verification, other configurations, "
+                         "library and CPU baselines, detail file")
     args = ap.parse_args()
+    if args.gpus > 1 and args.dump_outputs and args.no_gather:
+        ap.error("--dump-outputs at N > 1 writes the gathered output: it needs the exchange (drop --no-gather)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
     env = Env(args)
     n_gpus, rank = env.world, env.rank
-    reuse = n_gpus == 1 and not args.no_reuse
+    full = args.full
+    reuse = full and n_gpus == 1 and not args.no_reuse
 
     # ---- workload (same on every rank: deterministic generator / same file, B replicated)
     scale = args.scale * (n_gpus if args.scaling == "weak" else 1)
@@ -605,30 +680,24 @@ def main():
     assert A.rows == A.cols, "A*A needs a square matrix (use the transpose for rectangular inputs)"
     # oracle in full wherever it finishes in seconds; the big stencil through properties + sampled blocks
     def verify_mode(w, A_):
-        if args.no_verify:
+        if args.no_verify or not full:
             return None
         return "properties" if (w == "nlpkkt" and A_.rows > 2_000_000) or A_.nnz > 40_000_000 else "oracle"
 
-    res = measure(env, A, args.steps, args.warmup, gather=not args.no_gather, profile=True,
-                  verify=verify_mode(args.workload, A), reuse=reuse)
+    res = measure(env, A, args.steps, args.warmup, gather=not args.no_gather, profile=full,
+                  verify=verify_mode(args.workload, A), reuse=reuse, multiply_only=full, dump=args.dump_outputs)
     verdicts = []
     out, detail = None, {}
     if rank == 0:
-        short, full, roof = config_objects(args.workload, wl_name, data_label, A, res, args.steps)
-        detail["headline"] = full
         out = {
             "metric": "SpGEMM GFLOP/s (2*flops_intermediate/s), A*A",
-            "value": short["value"], "unit": "GFLOP/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": short["ms_per_step"], "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-            "dtype": short["dtype"],
+            "value": round(res["gflops"], 2), "unit": "GFLOP/s", "n_gpus": n_gpus, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(res["ms_per_step"], 4), "higher_is_better": True,
+            "scaling": args.scaling, "vs_baseline": None, "dtype": "f32" if A.data.dtype == np.float32 else "f64",
             "data": data_label if not env.shared_gpu else data_label + " (ranks share one GPU, gloo: plumbing check only)",
             "config": {"workload": wl_name, "rows": A.rows, "nnzA": A.nnz, "products": res["P"], "nnzC": res["nnzC"],
                        "parallelism": f"rows{n_gpus}" if n_gpus > 1 else "single",
                        "timed_call": "complete (analysis+binning+symbolic+scan+numeric+sort)"},
-            "value_reuse": short["value_reuse"], "ms_reuse": short["ms_reuse"],
-            "verified": None,
-            "phases_ms": full["phases_ms"],
-            "roofline": roof,
         }
         if n_gpus > 1:
             out["config"].update(gather=not args.no_gather, exchange_floor_ms=res["exchange_floor_ms"],
@@ -636,6 +705,12 @@ def main():
                                            else "torch") if not args.no_gather else None)
             if env.exchange_note:
                 detail["exchange_note"] = out["config"]["exchange_note"] = env.exchange_note[:160]
+    if rank == 0 and full:
+        short, full_obj, roof = config_objects(args.workload, wl_name, data_label, A, res, args.steps)
+        detail["headline"] = full_obj
+        out.update(value_reuse=short["value_reuse"], ms_reuse=short["ms_reuse"], verified=None,
+                   phases_ms=full_obj["phases_ms"], roofline=roof)
+        if n_gpus > 1:
             out["multiply_only"] = res["multiply_only"]
         verdicts.append(short["verified"])
         if n_gpus == 1 and not args.no_lib_baseline:
@@ -647,7 +722,7 @@ def main():
     del res
 
     # ---- N = 1: every other single-GPU configuration of BASELINE.json (configs[1..3]), one short object each
-    if n_gpus == 1 and not args.no_configs:
+    if full and n_gpus == 1 and not args.no_configs:
         entries, full_entries = [], []
         for w in ("scircuit", "webbase", "mac_econ", "cant"):
             if w == args.workload and args.scale == 1.0 and not args.mtx and args.dtype == "f64":
@@ -679,7 +754,7 @@ def main():
         detail["configs"] = full_entries
 
     # ---- BASELINE.json configs[4]: the nlpkkt160 stand-in, STRONG scaling, at this N
-    if not args.no_config5 and not (args.workload == "nlpkkt" and args.scaling == "strong"):
+    if full and not args.no_config5 and not (args.workload == "nlpkkt" and args.scaling == "strong"):
         A5, label5, name5 = load_workload("nlpkkt", args.config5_scale, args.seed)
         r5 = measure(env, A5, args.config5_steps, 2, gather=not args.no_gather, profile=n_gpus == 1,
                      verify=verify_mode("nlpkkt", A5), reuse=reuse)
@@ -707,21 +782,21 @@ def main():
             verdicts.append(out["config5"]["verified"])
         del A5, r5
 
-    if rank == 0:
+    if rank == 0 and full:
         if n_gpus == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(A, out["config"]["products"])
         checked = [v for v in verdicts if v is not None]
         out["verified"] = all(checked) if checked else None
-        line = json.dumps(out, separators=(",", ":"))
         detail["line"] = out
-        detail["line_bytes"] = len(line)
+        detail["line_bytes"] = len(json.dumps(out, separators=(",", ":")))
         try:
             with open(args.detail, "w") as f:
                 json.dump(detail, f, indent=1)
         except OSError as e:
             print(f"bench.py: could not write {args.detail}: {e}", file=sys.stderr)
-        print(line, flush=True)
-    failed = rank == 0 and out["verified"] is False
+    if rank == 0:
+        print(json.dumps(out, separators=(",", ":")), flush=True)
+    failed = rank == 0 and out.get("verified") is False
     if env.comm is not None:
         env.comm.close()
     if n_gpus > 1:

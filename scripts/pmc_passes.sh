@@ -1,10 +1,11 @@
 #!/bin/bash
-# usage (GPU box): bash scripts/pmc_passes.sh <tag> <workload> [bench opts...]   -> gpurun_out/pmc/<tag>_passN.csv
-# separate rocprofv3 --pmc passes (kernel-trace only, as gpurun requires) of a short bench run
+# usage (GPU box): bash scripts/pmc_passes.sh <tag> <workload> [bench opts...]   -> $OUT_ROOT/pmc/<tag>_passN.csv
+# separate rocprofv3 --pmc passes (kernel-trace only, counters in runs of their own) of a short bench run
 TAG=$1; W=$2; shift 2
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-/root/repo}"
+export OUT_ROOT=${OUT_ROOT:-build/out}  # everything the script writes goes under here
 export PYTHONPATH=$PWD
-mkdir -p gpurun_out/pmc
+mkdir -p $OUT_ROOT/pmc
 PASSES=(
  "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM"
  "SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INST_CYCLES_VMEM_RD SQ_INST_CYCLES_VMEM_WR SQ_WAIT_INST_LDS SQ_INSTS_SALU"
@@ -16,9 +17,9 @@ PASSES=(
 i=0
 for p in "${PASSES[@]}"; do
   i=$((i+1))
-  rm -rf gpurun_out/_pmc_tmp
-  timeout 600 rocprofv3 --kernel-trace --pmc $p -d gpurun_out/_pmc_tmp -o r -- python bench.py --workload $W --steps 3 --warmup 2 --no-cpu-baseline --no-config5 --no-configs --no-verify "$@" > gpurun_out/pmc/${TAG}_pass$i.log 2>&1
-  db=$(find gpurun_out/_pmc_tmp -name "*.db" | head -n 1)
-  if [ -n "$db" ]; then python scripts/rocpd_pmc.py $db gpurun_out/pmc/${TAG}_pass$i.csv > /dev/null; else echo "pass $i: no db"; tail -n 3 gpurun_out/pmc/${TAG}_pass$i.log; fi
+  rm -rf $OUT_ROOT/_pmc_tmp
+  timeout 600 rocprofv3 --kernel-trace --pmc $p -d $OUT_ROOT/_pmc_tmp -o r -- python bench.py --full --workload $W --steps 3 --warmup 2 --no-cpu-baseline --no-config5 --no-configs --no-verify "$@" > $OUT_ROOT/pmc/${TAG}_pass$i.log 2>&1
+  db=$(find $OUT_ROOT/_pmc_tmp -name "*.db" | head -n 1)
+  if [ -n "$db" ]; then python scripts/rocpd_pmc.py $db $OUT_ROOT/pmc/${TAG}_pass$i.csv > /dev/null; else echo "pass $i: no db"; tail -n 3 $OUT_ROOT/pmc/${TAG}_pass$i.log; fi
 done
-rm -rf gpurun_out/_pmc_tmp
+rm -rf $OUT_ROOT/_pmc_tmp

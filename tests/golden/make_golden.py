@@ -126,8 +126,24 @@ def formats():
     json.dump(meta, open(os.path.join(HERE, "formats.json"), "w"), indent=1)
 
 
+def ours_read_by_reference():
+    """formats/mac_econ_ours.hicsr (written by speck_amd.store_hicsr) and formats/mac_econ_ours.dump, what the
+    REFERENCE's loadCSR reads back from it (ref_formats dump): tests/test_host.py checks against them where
+    oracle/_ref cannot be built."""
+    import speck_amd
+    ref = os.path.join(ROOT, "oracle", "_ref", "ref_formats")
+    if not os.path.exists(ref):
+        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "ref"])
+    A = speck_amd.gen_matrix("mac_econ", 0.002, 3, signed=True)
+    hic = os.path.join(HERE, "formats", "mac_econ_ours.hicsr")
+    speck_amd.store_hicsr(A, hic)
+    with open(hic[:-len(".hicsr")] + ".dump", "wb") as f:
+        f.write(subprocess.check_output([ref, "dump", hic]))
+
+
 if __name__ == "__main__":
     synth10k()
     tiny_cases()
     formats()
+    ours_read_by_reference()
     print("golden fixtures written to", HERE)

@@ -98,7 +98,7 @@ def test_bench_two_ranks_share_the_gpu(tmp_path):
     detail = tmp_path / "detail.json"
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port),
-                        os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
+                        os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "2",
                         "--scale", "0.25", "--config5-scale", "0.004", "--config5-steps", "3", "--detail", str(detail)],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     out = p.stdout.decode()
@@ -125,8 +125,8 @@ def test_bench_launches_its_own_ranks_when_called_without_a_launcher(tmp_path):
     import sys
     import torch
     base = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--scale", "0.1",
-           "--no-config5", "--no-cpu-baseline", "--detail", str(tmp_path / "detail.json")]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "2",
+           "--scale", "0.1", "--no-config5", "--no-cpu-baseline", "--detail", str(tmp_path / "detail.json")]
     p = subprocess.run(cmd, cwd=ROOT, env=dict(base, SPECK_BENCH_SHARED_GPU="1"), stdout=subprocess.PIPE,
                        stderr=subprocess.STDOUT, timeout=600)
     out = p.stdout.decode()
@@ -147,8 +147,9 @@ def test_bench_default_line_is_compact_and_times_the_complete_call(tmp_path):
     import json
     import sys
     detail = tmp_path / "detail.json"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--configs-steps", "3",
-                        "--config5-scale", "0.01", "--config5-steps", "2", "--no-cpu-baseline", "--detail", str(detail)],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "5", "--warmup", "2",
+                        "--configs-steps", "3", "--config5-scale", "0.01", "--config5-steps", "2", "--no-cpu-baseline",
+                        "--detail", str(detail)],
                        cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
     out = p.stdout.decode()
     assert p.returncode == 0, out[-2000:]
@@ -181,6 +182,73 @@ def test_bench_default_line_is_compact_and_times_the_complete_call(tmp_path):
     assert full["line_bytes"] <= 4096 and len(full["headline"]["roofline"]["launches"]) >= 1
 
 
+def _dumped(d):
+    import numpy as np
+    return {f[:-len(".npy")]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+
+
+def _assert_dump_is_the_product(got, A):
+    """A --dump-outputs directory (small enough to be written in full) against the oracle's A * A."""
+    import numpy as np
+    from oracle import pyoracle as po
+    H = po.HostCSR(A.rows, A.cols, A.row_offsets, A.col_ids, A.data)
+    R, ab = po.spgemm(H, H)
+    assert set(got) == {"C_shape", "C_row_offsets", "C_col_ids", "C_values"}
+    assert got["C_values"].dtype == np.float64 and got["C_col_ids"].dtype == np.float64
+    assert got["C_shape"].tolist() == [A.rows, A.cols, R.nnz]
+    assert (got["C_row_offsets"] == R.row_offsets).all() and (got["C_col_ids"] == R.col_ids).all()
+    assert (np.abs(got["C_values"] - R.data) <= 1e-12 * ab + 1e-300).all()
+
+
+def test_bench_plain_run_prints_the_headline_only_and_dumps_the_last_output(tmp_path):
+    """A run without --full: the one line carries the headline fields and none of the side legs, no detail file is
+    written, and --dump-outputs writes the output of the last timed step -- the oracle's product -- the same in two
+    runs with the same arguments (indices exact, values within the product tolerance)."""
+    import json
+    import sys
+    import numpy as np
+    import speck_amd as sa
+    detail, dumps = tmp_path / "detail.json", []
+    for k in range(2):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "7", "--warmup", "2", "--scale",
+                            "0.05", "--seed", "3", "--dump-outputs", str(tmp_path / f"out{k}"), "--detail", str(detail)],
+                           cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
+        out = p.stdout.decode()
+        assert p.returncode == 0, out[-2000:]
+        lines = [ln for ln in out.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 7 and d["warmup"] == 2 and d["n_gpus"] == 1 and d["dtype"] == "f64"
+        assert d["ms_per_step"] > 0 and d["value"] > 0 and d["higher_is_better"] is True and d["unit"] == "GFLOP/s"
+        assert d["config"]["timed_call"].startswith("complete")
+        assert not {"value_reuse", "verified", "phases_ms", "roofline", "lib_baseline", "configs", "config5",
+                    "cpu_baseline"} & set(d), sorted(d)
+        assert not detail.exists()
+        dumps.append(_dumped(tmp_path / f"out{k}"))
+    _assert_dump_is_the_product(dumps[0], sa.gen_matrix("scircuit", 0.05, 3, signed=True))
+    for name in ("C_shape", "C_row_offsets", "C_col_ids"):
+        assert (dumps[1][name] == dumps[0][name]).all(), name
+    assert np.allclose(dumps[1]["C_values"], dumps[0]["C_values"], rtol=1e-12, atol=0)
+
+
+@pytest.mark.parametrize("exchange", ["native", "torch"])
+def test_bench_dumps_the_gathered_output_when_two_ranks_share_the_gpu(tmp_path, exchange):
+    """N = 2 (ranks on GPU 0, plumbing check): --dump-outputs writes what the exchange gathered on rank 0 -- the whole
+    product of the strong-scaling input, not a shard."""
+    import sys
+    import speck_amd as sa
+    base = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
+                        "--scale", "0.05", "--seed", "3", "--scaling", "strong", "--exchange", exchange,
+                        "--dump-outputs", str(tmp_path / "out")],
+                       cwd=ROOT, env=dict(base, SPECK_BENCH_SHARED_GPU="1"), stdout=subprocess.PIPE,
+                       stderr=subprocess.STDOUT, timeout=600)
+    out = p.stdout.decode()
+    assert p.returncode == 0, out[-2000:]
+    assert '"n_gpus":2' in out
+    _assert_dump_is_the_product(_dumped(tmp_path / "out"), sa.gen_matrix("scircuit", 0.05, 3, signed=True))
+
+
 def test_bench_falls_back_to_the_torch_exchange_when_the_native_one_fails_its_self_test():
     """bench.py brings the library's exchange up with a tiny self-checked gatherv; if that fails (here: forced on every
     rank) all ranks switch to the torch.distributed exchange together, and the line says so."""
@@ -190,7 +258,7 @@ def test_bench_falls_back_to_the_torch_exchange_when_the_native_one_fails_its_se
     port = 29000 + os.getpid() % 300
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port),
-                        os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
+                        os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "2",
                         "--scale", "0.1", "--no-config5", "--no-cpu-baseline"],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     out = p.stdout.decode()
@@ -208,9 +276,9 @@ def test_bench_strong_scaling_mode_two_ranks_share_the_gpu():
     port = 29300 + os.getpid() % 300
     sizes = {}
     for n in (1, 2):
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py")] if n == 1 else \
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full"] if n == 1 else \
             [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-             "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py")]
+             "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full"]
         p = subprocess.run(cmd + ["--gpus", str(n), "--steps", "3", "--warmup", "2", "--workload", "nlpkkt", "--scale",
                                   "0.004", "--scaling", "strong", "--no-cpu-baseline", "--no-configs"],
                            cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
@@ -282,8 +350,8 @@ def test_bench_reads_a_symmetric_suitesparse_file(tmp_path):
     n_lower = int((A.col_ids <= rows_of).sum())
     n_diag = int((A.col_ids == rows_of).sum())
     env = dict(os.environ, SPECK_MTX_DIR=str(tmp_path))
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "nlpkkt", "--scaling", "strong",
-                        "--steps", "3", "--warmup", "2", "--no-configs", "--no-cpu-baseline", "--detail",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", "nlpkkt", "--scaling",
+                        "strong", "--steps", "3", "--warmup", "2", "--no-configs", "--no-cpu-baseline", "--detail",
                         str(tmp_path / "detail.json")],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=600)
     out = p.stdout.decode()
