@@ -194,6 +194,10 @@ int speck_dcsr_update(speck_dcsr *dst, const uint32_t *h_row_offsets, const uint
                       const void *h_data, size_t value_size);
 /* spECK::Compare(ref, cmp, compare_data) -- include/Compare.h:5-6, source/GPU/Compare.cu:11-82;
  * stricter: offsets + col ids bit-exact; values |x-y| <= rel_tol*max(|x|,|y|) when compare_data.
+ * Special values (here and in speck_compare_bounded_f64): x and y match iff both are NaN, or x == y,
+ * or both are finite and within the bound -- equal infinities match, an infinity never matches a
+ * finite value or the opposite infinity, NaN matches NaN only (the reference passes NaN against any
+ * value, source/GPU/Compare.cu:50).
  * *h_mismatches = number of differing rows (0 = equal). */
 int speck_compare_f64(speck_config *cfg, const speck_dcsr *ref, const speck_dcsr *cmp,
                       int compare_data, double rel_tol, uint64_t *h_mismatches);

@@ -35,6 +35,15 @@ namespace {
 // one wave per row.  Structure: offsets and column ids bit-exact.  Values (compare_data): relative to
 // max(|x|, |y|), or -- when `scale` is given -- |x - y| <= rel_tol * scale[j] with scale = sum |a*b| of
 // the entry (the bound any summation order satisfies; `scale` has the pattern of `ref`).
+// Special values: x and y match iff both are NaN, or x == y (equal infinities, +0 and -0), or both are
+// finite and within the bound -- an infinity never matches a finite value, nor the other infinity.
+__device__ __forceinline__ bool values_match(double x, double y, double bound)
+{
+    if (x == y) return true;
+    if (isnan(x) || isnan(y)) return isnan(x) && isnan(y);
+    return isfinite(x) && isfinite(y) && fabs(x - y) <= bound;
+}
+
 template <typename T>
 __global__ void compare_kernel(const u32* __restrict__ ro_a, const u32* __restrict__ col_a,
                                const T* __restrict__ val_a, const u32* __restrict__ ro_b,
@@ -60,7 +69,7 @@ __global__ void compare_kernel(const u32* __restrict__ ro_a, const u32* __restri
                 if (compare_data) {
                     const double x = (double)val_a[a0 + j], y = (double)val_b[b0 + j];
                     const double scale = val_s ? fabs((double)val_s[s0 + j]) : fmax(fabs(x), fabs(y));
-                    if (!(fabs(x - y) <= rel_tol * scale + 1e-300)) badv = true;
+                    if (!values_match(x, y, rel_tol * scale + 1e-300)) badv = true;
                 }
             }
         }
