@@ -216,6 +216,45 @@ int speck_transpose_f64(speck_config *cfg, const speck_dcsr *A, speck_dcsr *At);
 /* ... and its float instantiation (source/GPU/Transpose.cu:116) */
 int speck_transpose_f32(speck_config *cfg, const speck_dcsr *A, speck_dcsr *At);
 
+/* ---- rows of a device CSR sorted in place (new: the reference sorts on the host while it loads, source/CSR.cpp:173-212;
+ *      a matrix that is already on the device -- the output of a library SpGEMM, a CSR assembled from element
+ *      contributions, columns relabelled in place -- has no loader in the way).  Makes `M` acceptable as an input of
+ *      speck_multiply_*: every row ascending by column id, optionally with equal columns merged into one entry.
+ *  IN PLACE: the three device pointers of M are the same after the call, nothing of M is allocated or freed.  Temporaries
+ *      (class lists, the long-row class, the compaction) are grow-only buffers of the config, released with it; cfg == NULL
+ *      is allowed as for speck_transpose_*, with temporaries of the call's own on the NULL stream.
+ *  SPECK_SORT_KEEP_DUPLICATES: every row becomes the STABLE sort of itself by column id -- entries of equal column keep
+ *      their input order.  row_offsets and nnz are not written.  Works on a row-range view with absolute offsets: only the
+ *      entries of the view's rows are touched.
+ *  SPECK_SORT_SUM_DUPLICATES: as above, then every run of equal columns becomes ONE entry whose value is the sum of the
+ *      run, accumulated in double for both precisions and rounded once; the order of the sum is unspecified.  An entry is
+ *      kept even if its sum is zero.  Rows are compacted to the front of col_ids / data, row_offsets is rewritten, M->nnz and
+ *      info->nnz_out are the new count; the tail of the buffers is unspecified.  A view with row_offsets[0] != 0 that has
+ *      duplicates is refused with SPECK_ERR_INVALID and left as it was (without duplicates the flag changes nothing and a
+ *      view is fine).
+ *  A matrix that is already canonical costs one streaming read of row_offsets and col_ids and writes nothing.  The same
+ *      pass is the input check: row_offsets descending or leaving [row_offsets[0], row_offsets[0] + nnz], or a column id
+ *      >= cols, returns SPECK_ERR_INVALID with NO BYTE of M written; no kernel leaves the buffers on such input (the pass
+ *      clamps, the sorting kernels start after its verdict).  Limits as for the multiply: rows, cols <= 2^27
+ *      (SPECK_ERR_DIM_LIMIT), nnz < 2^32.
+ *  Runs on the config's stream (speck_config_set_stream is honoured) and returns with M complete.  With the debug option
+ *      guard_bytes the canary zones of M's buffers and of the temporaries are checked after the call.
+ *  Rows are handled by length: <= SPECK_SORT_REG_MAX entries in registers (when the row's column range is below 2^24 - 1),
+ *      <= SPECK_SORT_LDS_MAX in LDS, longer ones by a radix sort through global memory; options sort_reg_max / sort_lds_max
+ *      lower the two limits (values are clamped to the constants). ---- */
+enum { SPECK_SORT_KEEP_DUPLICATES = 0, SPECK_SORT_SUM_DUPLICATES = 1 };
+#define SPECK_SORT_REG_MAX 256
+#define SPECK_SORT_LDS_MAX 4096
+typedef struct speck_sort_info {
+    uint64_t rows_in_order;      /* rows that were strictly ascending already: not touched */
+    uint64_t rows_sorted[3];     /* rows handled by the register / LDS / global-memory class */
+    uint64_t duplicates;         /* entries whose column equals that of an earlier entry of their row (found, and
+                                    with SUM_DUPLICATES removed) */
+    uint64_t nnz_out;            /* nnz after the call */
+} speck_sort_info;
+int speck_sort_rows_f64(speck_config *cfg, speck_dcsr *M, int flags, speck_sort_info *info /* may be NULL */);
+int speck_sort_rows_f32(speck_config *cfg, speck_dcsr *M, int flags, speck_sort_info *info);
+
 /* ---- row-sharded multi-GPU (new: the reference is single-GPU, source/Executor.cpp:25).  One process per GPU;
  *      rank p multiplies the row range [b_p, b_{p+1}) of A (a view with absolute offsets, boundaries from
  *      speck_partition_rows) with a replicated B, then ONE exchange concatenates the shards on a root rank:

@@ -7,5 +7,5 @@ reference's host interface used by the tests and the benchmark harness.
 from .api import (  # noqa: F401
     SpeckError, Timings, dCSR, spECKConfig, HostCSR, MultiplyspECK, BoundMultiply, analysis, symbolic,
     partition_rows, compare, compare_bounded, transpose, gen_matrix, load_matrix, load_mtx, store_mtx, load_hicsr,
-    store_hicsr, lib_path,
+    store_hicsr, lib_path, sort_rows, SortInfo, SORT_REG_MAX, SORT_LDS_MAX,
 )

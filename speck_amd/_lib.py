@@ -42,6 +42,12 @@ class CStats(C.Structure):
                 ("walk_misses", C.c_int32), ("eager_through", C.c_int32)]
 
 
+class CSortInfo(C.Structure):
+    # include/speck_c_api.h: speck_sort_info
+    _fields_ = [("rows_in_order", C.c_uint64), ("rows_sorted", C.c_uint64 * 3), ("duplicates", C.c_uint64),
+                ("nnz_out", C.c_uint64)]
+
+
 # every symbol include/speck_c_api.h declares, with its ctypes signature
 _P = C.POINTER
 _SIGS = {
@@ -71,6 +77,8 @@ _SIGS = {
     "speck_compare_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), C.c_int, C.c_double, _P(C.c_uint64)]),
     "speck_transpose_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr)]),
     "speck_transpose_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr)]),
+    "speck_sort_rows_f64": (C.c_int, [C.c_void_p, _P(DCsr), C.c_int, _P(CSortInfo)]),
+    "speck_sort_rows_f32": (C.c_int, [C.c_void_p, _P(DCsr), C.c_int, _P(CSortInfo)]),
     "speck_compare_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), C.c_int, C.c_double, _P(C.c_uint64)]),
     "speck_compare_bounded_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), _P(DCsr), C.c_double, _P(C.c_uint64),
                                             _P(C.c_uint64)]),

@@ -414,3 +414,35 @@ def transpose(A, config):
     fn = _lib.load().speck_transpose_f32 if A.dtype == np.float32 else _lib.load().speck_transpose_f64
     _check(fn(config._h, C.byref(A._c), C.byref(At._c)), "Transpose")
     return At
+
+
+# include/speck_c_api.h: SPECK_SORT_REG_MAX / SPECK_SORT_LDS_MAX (rows up to this many entries are sorted in registers / in LDS)
+SORT_REG_MAX = 256
+SORT_LDS_MAX = 4096
+
+
+class SortInfo:
+    """speck_sort_info: what a sort_rows call found and did."""
+
+    def __init__(self, c):
+        self.rows_in_order = int(c.rows_in_order)
+        self.rows_sorted = tuple(int(x) for x in c.rows_sorted)  # register / LDS / global-memory class
+        self.duplicates = int(c.duplicates)
+        self.nnz_out = int(c.nnz_out)
+
+    def __repr__(self):
+        return (f"SortInfo(rows_in_order={self.rows_in_order}, rows_sorted={self.rows_sorted}, "
+                f"duplicates={self.duplicates}, nnz_out={self.nnz_out})")
+
+
+def sort_rows(M, config, sum_duplicates=False):
+    """Sort every row of the device matrix M in place by column id (stable); sum_duplicates merges equal columns
+    (speck_sort_rows_f64 / _f32).  config may be None.  Returns a SortInfo; M.nnz is the new count."""
+    L = _lib.load()
+    fn = L.speck_sort_rows_f32 if M.dtype == np.float32 else L.speck_sort_rows_f64
+    info = _lib.CSortInfo()
+    _check(fn(config._h if config is not None else None, C.byref(M._c), 1 if sum_duplicates else 0, C.byref(info)),
+           "sort_rows")
+    if sum_duplicates and info.duplicates and M._host_row_offsets is not None:
+        M._host_row_offsets = None  # (row_offsets were rewritten on the device)
+    return SortInfo(info)

@@ -30,6 +30,7 @@
 #include "guards.hpp"
 #include "launch.hpp"
 #include "row_groups.hpp"
+#include "sort_rows.hpp"
 
 using namespace speck;
 
@@ -238,6 +239,7 @@ struct speck_config {
     // debug option guard_bytes (guards.hpp): the zones between the regions carved from the arena / the spill pool, and what
     // layout the arena's were last filled for
     std::vector<GuardZone> arena_zones, gpool_zones, nfpool_zones;
+    SortScratch sort;  // temporaries and class limits of speck_sort_rows_* (sort_rows.hip)
     const void* zones_arena = nullptr;
     u64 zones_m = 0, zones_nnz = 0, zones_gap = 0;
     bool gpool_zones_filled = false;
@@ -1918,6 +1920,11 @@ int multiply_impl(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, spe
 
 }  // namespace
 
+namespace speck {
+SortScratch* sort_scratch(speck_config* c) { return &c->sort; }
+hipStream_t sort_stream(speck_config* c) { return main_stream(c); }
+}  // namespace speck
+
 extern "C" {
 
 int speck_config_create(int device, speck_config** out)
@@ -2028,6 +2035,7 @@ int speck_config_destroy(speck_config* c)
     if (c->snap) (void)guarded_free(c->snap);
     if (c->gpool) (void)guarded_free(c->gpool);
     if (c->nfpool) (void)guarded_free(c->nfpool);
+    c->sort.release();
     if (c->pred.off) (void)guarded_free(c->pred.off);
     if (c->gpred.off) (void)guarded_free(c->gpred.off);
     if (c->d_stats) (void)hipFree(c->d_stats);
@@ -2108,7 +2116,10 @@ int speck_config_set_option(speck_config* c, const char* name, int64_t value)
         if (c->gpool) (void)guarded_free(c->gpool);
         c->gpool = nullptr, c->gpool_bytes = 0, c->gpool_zones.clear(), c->spill = SpillBuffers{};
         c->spec_valid = false;
+        c->sort.release();
     }
+    else if (n == "sort_reg_max") c->sort.reg_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_REG_MAX);
+    else if (n == "sort_lds_max") c->sort.lds_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_LDS_MAX);
     else if (n == "walk_debug") set_walk_debug((u32)value & 0xFFFFu, (u32)(value >> 16));  // (tile rows | flags << 16)
     else if (n == "verify_inputs") c->verify_inputs = value != 0, c->snap_for_arena = false, forget(false);
     else if (n == "num_verify") c->num_verify = (int)value, forget(false);
