@@ -255,6 +255,52 @@ typedef struct speck_sort_info {
 int speck_sort_rows_f64(speck_config *cfg, speck_dcsr *M, int flags, speck_sort_info *info /* may be NULL */);
 int speck_sort_rows_f32(speck_config *cfg, speck_dcsr *M, int flags, speck_sort_info *info);
 
+/* ---- masked SpGEMM (new: the reference has no counterpart): C = M o (A B), the product kept only where the mask M has an
+ *      entry -- triangle counting L o (L L), a Galerkin product kept on the pattern of A, the gradient of a sparse product
+ *      with respect to a sparse operand.  The table a row accumulates in is its mask row: nothing beyond nnz(M) entries is
+ *      counted, allocated, sorted or stored.
+ *  M is rows(A) x cols(B); only its pattern is read, M->data may be NULL.  A row of M that is not strictly ascending or holds
+ *      an id >= cols(B): SPECK_ERR_UNSORTED (as for B in the multiply; the remedy is speck_sort_rows_*).  A and B under the
+ *      multiply's preconditions with the multiply's statuses (a row of B not strictly ascending or an id >= cols(B):
+ *      SPECK_ERR_UNSORTED; an id of A >= rows(B): SPECK_ERR_INVALID), checked with every call.  Offsets of A / M descending or
+ *      leaving [row_offsets[0], row_offsets[0] + nnz], inconsistent shapes, NULL buffers with nnz > 0, unknown flags, C sharing
+ *      a buffer with A, B or M: SPECK_ERR_INVALID.  rows, cols <= 2^27 and fewer than 2^32 products in any one row
+ *      (SPECK_ERR_DIM_LIMIT), nnz < 2^32.  A and M may both be row-range views with absolute offsets (sharding: rank p
+ *      passes its rows of both).
+ *  SPECK_MASK_STRUCTURE: C(i,j) exists iff (i,j) is in M AND some k has (i,k) in A and (k,j) in B -- structural, as in the
+ *      multiply: an entry whose products cancel to 0.0 stays.  Offsets and column ids are bit for bit what speck_multiply_*
+ *      followed by "keep (i,j) in M" gives; the values are the sums of a*b in unspecified order, each product rounded to the
+ *      value type, the sum kept in double and rounded once (the multiply's bound).  Rows ascending: the mask row's order is
+ *      the output order.
+ *  SPECK_MASK_FULL_PATTERN: C has exactly M's pattern (offsets rebased to 0), +0.0 where no product falls -- the sampled
+ *      product; no count, scan or compaction.
+ *  Ownership of C as speck_multiply_* documents it: row_offsets reused when C->rows == A->rows, data / col_ids re-allocated
+ *      only when C->nnz differs from the result's.  On any error the struct, its allocations AND the contents of C are
+ *      untouched: there is no speculative path here.  No kernel uses a column id of A to index B->row_offsets, or an offset
+ *      to index col_ids, before it has been checked, and nothing of C is written before the verdict on all three inputs
+ *      is in.
+ *  Runs on the config's stream (speck_config_set_stream is honoured) and returns with C complete.  Temporaries are grow-only
+ *      buffers of the config's own (not the multiply's arena: a masked call between two identical multiplies does not disturb
+ *      the second one's reuse sequence), released with it; cfg == NULL is allowed as for speck_sort_rows_*.  With the debug
+ *      option guard_bytes the canary zones of the temporaries and of C are checked after the call.
+ *  Rows are handled by the length of their mask row: <= SPECK_MASK_GROUP_MAX entries by 8 / 16 / 32 / 64 lanes, several rows
+ *      per workgroup; <= SPECK_MASK_LDS_MAX by a workgroup with a table in LDS; longer ones through global memory.  Options
+ *      mask_group_max / mask_lds_max lower the two limits (values are clamped to the constants). ---- */
+enum { SPECK_MASK_STRUCTURE = 0, SPECK_MASK_FULL_PATTERN = 1 };
+#define SPECK_MASK_GROUP_MAX 256
+#define SPECK_MASK_LDS_MAX 4096
+typedef struct speck_masked_info {
+    uint64_t rows_idle;          /* rows with an empty mask row or an empty row of A: no product is formed for them */
+    uint64_t rows_class[3];      /* rows with work, by mask-row length: group / LDS / global-memory class */
+    uint64_t products;           /* products a(i,k)*b(k,j) of the rows with work */
+    uint64_t hits;               /* ... of which (i,j) is in the mask */
+    uint64_t nnz_out;            /* nnz(C) */
+} speck_masked_info;
+int speck_multiply_masked_f64(speck_config *cfg, const speck_dcsr *A, const speck_dcsr *B, const speck_dcsr *M,
+                              speck_dcsr *C, int flags, speck_masked_info *info /* may be NULL */);
+int speck_multiply_masked_f32(speck_config *cfg, const speck_dcsr *A, const speck_dcsr *B, const speck_dcsr *M,
+                              speck_dcsr *C, int flags, speck_masked_info *info);
+
 /* ---- row-sharded multi-GPU (new: the reference is single-GPU, source/Executor.cpp:25).  One process per GPU;
  *      rank p multiplies the row range [b_p, b_{p+1}) of A (a view with absolute offsets, boundaries from
  *      speck_partition_rows) with a replicated B, then ONE exchange concatenates the shards on a root rank:

@@ -8,4 +8,5 @@ from .api import (  # noqa: F401
     SpeckError, Timings, dCSR, spECKConfig, HostCSR, MultiplyspECK, BoundMultiply, analysis, symbolic,
     partition_rows, compare, compare_bounded, transpose, gen_matrix, load_matrix, load_mtx, store_mtx, load_hicsr,
     store_hicsr, lib_path, sort_rows, SortInfo, SORT_REG_MAX, SORT_LDS_MAX,
+    multiply_masked, MaskedInfo, MASK_GROUP_MAX, MASK_LDS_MAX,
 )

@@ -48,6 +48,12 @@ class CSortInfo(C.Structure):
                 ("nnz_out", C.c_uint64)]
 
 
+class CMaskedInfo(C.Structure):
+    # include/speck_c_api.h: speck_masked_info
+    _fields_ = [("rows_idle", C.c_uint64), ("rows_class", C.c_uint64 * 3), ("products", C.c_uint64), ("hits", C.c_uint64),
+                ("nnz_out", C.c_uint64)]
+
+
 # every symbol include/speck_c_api.h declares, with its ctypes signature
 _P = C.POINTER
 _SIGS = {
@@ -79,6 +85,8 @@ _SIGS = {
     "speck_transpose_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr)]),
     "speck_sort_rows_f64": (C.c_int, [C.c_void_p, _P(DCsr), C.c_int, _P(CSortInfo)]),
     "speck_sort_rows_f32": (C.c_int, [C.c_void_p, _P(DCsr), C.c_int, _P(CSortInfo)]),
+    "speck_multiply_masked_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), _P(DCsr), _P(DCsr), C.c_int, _P(CMaskedInfo)]),
+    "speck_multiply_masked_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), _P(DCsr), _P(DCsr), C.c_int, _P(CMaskedInfo)]),
     "speck_compare_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), C.c_int, C.c_double, _P(C.c_uint64)]),
     "speck_compare_bounded_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), _P(DCsr), C.c_double, _P(C.c_uint64),
                                             _P(C.c_uint64)]),

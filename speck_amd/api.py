@@ -446,3 +446,44 @@ def sort_rows(M, config, sum_duplicates=False):
     if sum_duplicates and info.duplicates and M._host_row_offsets is not None:
         M._host_row_offsets = None  # (row_offsets were rewritten on the device)
     return SortInfo(info)
+
+
+# include/speck_c_api.h: SPECK_MASK_GROUP_MAX / SPECK_MASK_LDS_MAX (mask rows up to this many entries: several rows per
+# workgroup / one workgroup per row with its table in LDS; longer ones go through global memory)
+MASK_GROUP_MAX = 256
+MASK_LDS_MAX = 4096
+
+
+class MaskedInfo:
+    """speck_masked_info: what a multiply_masked call found and did."""
+
+    def __init__(self, c):
+        self.rows_idle = int(c.rows_idle)
+        self.rows_class = tuple(int(x) for x in c.rows_class)  # group / LDS / global-memory class
+        self.products = int(c.products)
+        self.hits = int(c.hits)
+        self.nnz_out = int(c.nnz_out)
+
+    def __repr__(self):
+        return (f"MaskedInfo(rows_idle={self.rows_idle}, rows_class={self.rows_class}, products={self.products}, "
+                f"hits={self.hits}, nnz_out={self.nnz_out})")
+
+
+def multiply_masked(A, B, M, config, matOut=None, full_pattern=False):
+    """C = M o (A B): the product kept only where the mask M has an entry (speck_multiply_masked_f64 / _f32).  Only the
+    pattern of M is read.  full_pattern: C takes exactly M's pattern, +0.0 where no product falls; otherwise an entry
+    exists where M has one AND a product falls.  config may be None.  Returns (matOut, MaskedInfo)."""
+    L = _lib.load()
+    if A.dtype != B.dtype:
+        raise TypeError("A and B must share a value type")
+    fn = L.speck_multiply_masked_f32 if A.dtype == np.float32 else L.speck_multiply_masked_f64
+    if matOut is None:
+        matOut = dCSR(A.dtype)
+    if matOut.dtype != A.dtype:
+        matOut.reset()
+        matOut.dtype = A.dtype
+    info = _lib.CMaskedInfo()
+    _check(fn(config._h if config is not None else None, C.byref(A._c), C.byref(B._c), C.byref(M._c), C.byref(matOut._c),
+              1 if full_pattern else 0, C.byref(info)), "multiply_masked")
+    matOut._host_row_offsets = None  # (row_offsets were rewritten on the device)
+    return matOut, MaskedInfo(info)

@@ -1,0 +1,1017 @@
+// masked.hip -- speck_multiply_masked_*: C = M o (A B), the product kept only where the mask M has an entry.  The
+// reference has no counterpart.  The table a row accumulates in IS its mask row: its size is known before a product is
+// formed, it is sorted already, and a product's column is looked up with reads -- nothing is inserted, nothing is sorted.
+//
+//   masked_classify_kernel   one streaming pass over the rows: the input check of A and M (offsets monotone and inside
+//                            their matrices, ids of A < rows(B), mask rows strictly ascending and < cols(B) -- no offset
+//                            or id is used as an address before it was checked), the products of the rows with work, and
+//                            those rows appended to one of seven lists by mask-row length (cursors aggregated per
+//                            workgroup).  B is checked by the multiply's own validate_b_kernel (stages.hip), behind it
+//                            on the same stream.
+//   masked_group_kernel<L>   mask rows of <= 4 L entries, L = 8 / 16 / 32 / 64 lanes per row: the mask row's columns and one
+//                            double per entry in the group's slice of LDS, binary search, ds_add_f64.
+//   masked_lds_kernel        a workgroup per row of <= 1024 (256 threads) or <= SPECK_MASK_LDS_MAX (1024 threads) entries:
+//                            an open-addressed table of 16-bit positions over the row's columns, built once, probed read-only.
+//   masked_global_kernel     a workgroup per longer row: binary search in the mask row where it lies, global atomic adds.
+//   (all three walk a row's products flattened, a batch of entries of A at a time: "the product walk" below)
+//   finish                   STRUCTURE: hits per row -> scan -> the new row offsets; a scan over the hit bytes -> one
+//                            streaming compaction.  FULL_PATTERN: the accumulators
+//                            are C's values (fp64: accumulated in place), offsets rebased, column ids copied.
+// A hit is marked in bit 31 of the column's LDS copy (columns are < 2^27).  As in the multiply a product is rounded to T,
+// the sum is kept in double and rounded once.  Every kernel but the classifying pass starts after the host has read the
+// verdict on all three inputs; nothing of C is written before that.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <type_traits>
+#include <vector>
+
+#include "../../include/speck_c_api.h"
+#include "device_common.hpp"
+#include "guards.hpp"
+#include "launch.hpp"
+#include "masked.hpp"
+#include "sort_rows.hpp"
+
+using namespace speck;
+
+#define HIP_TRY(expr)                                                                     \
+    do {                                                                                  \
+        hipError_t _e = (expr);                                                           \
+        if (_e != hipSuccess) {                                                           \
+            std::fprintf(stderr, "speck_amd: HIP error %s at %s:%d\n", hipGetErrorString(_e), \
+                         __FILE__, __LINE__);                                             \
+            return (_e == hipErrorOutOfMemory) ? SPECK_ERR_OOM : SPECK_ERR_HIP;           \
+        }                                                                                 \
+    } while (0)
+
+namespace speck {
+void MaskedScratch::release()
+{
+    if (fixed) (void)guarded_free(fixed);
+    if (var) (void)guarded_free(var);
+    fixed = var = nullptr;
+    fixed_bytes = var_bytes = 0;
+    for (int i = 0; i < 3; ++i) {
+        if (side[i]) (void)hipStreamDestroy(side[i]);
+        if (join[i]) (void)hipEventDestroy(join[i]);
+        side[i] = nullptr, join[i] = nullptr;
+    }
+    if (fork) (void)hipEventDestroy(fork);
+    fork = nullptr;
+}
+}  // namespace speck
+
+namespace {
+
+constexpr u32 kGroupMax = SPECK_MASK_GROUP_MAX, kLdsMax = SPECK_MASK_LDS_MAX;
+constexpr u32 kLdsSmall = 1024;      // LDS class: rows up to this many entries take the 256-thread launch
+constexpr u32 kHitBit = 0x80000000u, kColMask = 0x7FFFFFFFu;
+constexpr u32 kNoColumn = 0xFFFFFFFFu;  // above every column of a mask row: "no product"
+enum { LIST_G8 = 0, LIST_G16, LIST_G32, LIST_G64, LIST_LDS_S, LIST_LDS_L, LIST_GLOBAL, MASK_LISTS };
+static_assert(kGroupMax == 256 && kLdsMax <= 4096, "group widths / 16-bit table positions");
+
+struct MaskedStatus {
+    u32 invalid;            // offsets of A / M, an id of A
+    u32 unsorted;           // a mask row
+    u32 verdict_b;          // bit 2: validate_b_kernel found B wanting
+    u32 idle;               // rows without work
+    u32 cnt[MASK_LISTS];    // list lengths
+    u32 base_m;             // M.row_offsets[0]
+    u32 too_many;           // a row with work holds 2^32 products or more (the walk numbers a row's products in 32 bits)
+    unsigned long long products, hits, nnz_out;
+};
+
+// list k lives in region k / 2 (`rows` words each), the even one grows up from the region's first word, the odd one down
+// from its last (the lists hold different rows: they cannot meet)
+__host__ __device__ __forceinline__ u32* list_at(u32* lists, u32 rows, u32 k, u32 i)
+{
+    u32* region = lists + size_t(k >> 1) * rows;
+    return (k & 1u) ? region + (rows - 1u - i) : region + i;
+}
+
+template <typename T>
+struct MaskedArgs {
+    const u32 *a_ro, *a_col;
+    const T* a_val;
+    const u32 *b_ro, *b_col;
+    const T* b_val;
+    const u32 *m_ro, *m_col;
+    u32 rows, base_m;
+    u32* lists;
+    MaskedStatus* st;
+    double* acc;    // one per mask entry (entry e of M's buffers at e - base_m), zero before the walk
+    u8* hit;        // ... and one byte: a product fell there (nullptr: FULL_PATTERN, nobody asks)
+    u32* row_cnt;   // entries hit per row, zero before the walk (nullptr: FULL_PATTERN)
+};
+
+// ------------------------------------------------------------------------------------------------ check + classify
+
+// the row of entry i of a tile: the first one whose end lies beyond i
+__device__ __forceinline__ u32 row_of(const u32* s_ro, u32 nr, u64 i)
+{
+    u32 a = 0, b = nr;
+    while (a < b) {
+        const u32 mid = (a + b) >> 1;
+        if (s_ro[mid + 1] <= i) a = mid + 1; else b = mid;
+    }
+    return a;
+}
+
+// TILE rows and TILE threads per workgroup: 1024 where rows are short, 256 where a row holds 16 entries or more on
+// average (a tile should hold enough entries to pay for its barriers, and there should be enough tiles for the machine:
+// the 62 k rows of the cant stand-in are 61 tiles of 1024).  The cursors of the lists, the idle rows and the products are counted in LDS
+// first and reach the status block with ONE atomic per workgroup and counter: atomics of every wave on the same few words
+// of global memory cost ~8 ns each, one after the other (measured: 0.42 ms for the 1 M rows of the webbase stand-in).
+template <u32 kTileRows>
+__global__ __launch_bounds__(kTileRows) void masked_classify_kernel(const u32* __restrict__ a_ro, const u32* __restrict__ a_col,
+                                                                    u64 a_nnz, const u32* __restrict__ b_ro, u32 b_rows, u32 b_cols,
+                                                                    u64 b_nnz, const u32* __restrict__ m_ro,
+                                                                    const u32* __restrict__ m_col, u64 m_nnz, u32 rows, u32 group_max,
+                                                                    u32 lds_max, u32* __restrict__ lists, MaskedStatus* __restrict__ st)
+{
+    SPECK_POISON();
+    __shared__ u32 s_aro[kTileRows + 1];
+    __shared__ u32 s_mro[kTileRows + 1];
+    __shared__ u32 s_bad;
+    __shared__ u32 s_cnt[MASK_LISTS + 1];   // rows of the tile per list; [MASK_LISTS]: idle rows
+    __shared__ u32 s_first[MASK_LISTS];     // where the tile's rows start in each list
+    __shared__ unsigned long long s_products;
+    __shared__ u32 s_ops[kTileRows];        // products per row (saturating well below 2^32: it only picks a group width)
+    const u32 t = threadIdx.x;
+    const u32 r0 = blockIdx.x * kTileRows;
+    const u32 nr = min(kTileRows, rows - r0);
+    const u32 base_a = a_ro[0], base_m = m_ro[0];
+    if (t == 0) s_bad = 0, s_products = 0;
+    if (t <= MASK_LISTS) s_cnt[t] = 0;
+    s_ops[t] = 0;
+    if (t == 0 && blockIdx.x == 0) st->base_m = base_m;
+    __syncthreads();
+    for (u32 i = t; i <= nr; i += kTileRows) {
+        const u32 oa = a_ro[r0 + i], om = m_ro[r0 + i];
+        s_aro[i] = oa;
+        s_mro[i] = om;
+        if (oa < base_a || u64(oa - base_a) > a_nnz || om < base_m || u64(om - base_m) > m_nnz) s_bad = 1;
+    }
+    __syncthreads();
+    if (t < nr && (s_aro[t] > s_aro[t + 1] || s_mro[t] > s_mro[t + 1])) s_bad = 1;
+    __syncthreads();
+    if (s_bad) {  // (nothing of col_ids is addressed through such offsets)
+        if (t == 0) st->invalid = 1;
+        return;
+    }
+    // the tile's mask entries: below cols(B), above their predecessor unless they start a row
+    bool unsorted = false;
+    {
+        const u64 lo = s_mro[0], hi = s_mro[nr];
+#pragma unroll 4
+        for (u64 i = lo + t; i < hi; i += kTileRows) {
+            const u32 c = m_col[i];
+            unsorted |= c >= b_cols;
+            if (i > lo && m_col[i - 1] >= c) unsorted |= i > s_mro[row_of(s_mro, nr, i)];
+        }
+    }
+    // the tile's entries of A: below rows(B); the products they stand for, where their row has a mask row
+    bool bad_a = false;
+    u64 products = 0;
+    {
+        const u64 lo = s_aro[0], hi = s_aro[nr];
+#pragma unroll 4
+        for (u64 i = lo + t; i < hi; i += kTileRows) {
+            const u32 k = a_col[i];
+            if (k >= b_rows) {
+                bad_a = true;
+                continue;
+            }
+            const u32 b0 = b_ro[k], b1 = b_ro[k + 1];
+            const u64 len = b1 > b0 ? min(u64(b1 - b0), b_nnz) : 0ull;  // (B's own check speaks later: clamped)
+            const u32 r = row_of(s_aro, nr, i);
+            if (s_mro[r + 1] > s_mro[r]) {
+                products += len;
+                if (s_ops[r] < (1u << 20)) atomicAdd(&s_ops[r], (u32)min(len, u64(1u << 20)));
+            }
+        }
+    }
+    __syncthreads();
+    if (unsorted) st->unsorted = 1;
+    if (bad_a) st->invalid = 1;
+    const u32 lane = lane_id();
+    products = wave_reduce_add(products);
+    if (lane == 0 && products) atomicAdd(&s_products, (unsigned long long)products);
+    int cls = -2;  // no row
+    if (t < nr) {
+        const u32 len = s_mro[t + 1] - s_mro[t];
+        if (len == 0 || s_aro[t + 1] == s_aro[t]) cls = MASK_LISTS;
+        else if (len <= group_max && len <= kGroupMax) {
+            // four mask entries per lane at most -- and not more than ~32 products per lane where a wider group can help
+            const u32 want = max((len + 3u) / 4u, s_ops[t] / 32u);
+            cls = want <= 8 ? LIST_G8 : want <= 16 ? LIST_G16 : want <= 32 ? LIST_G32 : LIST_G64;
+        }
+        else if (len <= lds_max && len <= kLdsMax) cls = len <= kLdsSmall ? LIST_LDS_S : LIST_LDS_L;
+        else cls = LIST_GLOBAL;
+    }
+    u32 rank = 0;  // of my row among the tile's rows of its list
+#pragma unroll
+    for (int k = 0; k <= MASK_LISTS; ++k) {
+        const u64 m = __ballot(cls == k);
+        if (m == 0) continue;
+        const u32 leader = (u32)__ffsll((long long)m) - 1u;
+        u32 first = 0;
+        if (lane == leader) first = atomicAdd(&s_cnt[k], (u32)__popcll(m));
+        first = (u32)__shfl((int)first, (int)leader);
+        if (cls == k) rank = first + (u32)__popcll(m & lanemask_lt());
+    }
+    __syncthreads();
+    if ((s_products >> 32) != 0 && cls >= 0 && cls < MASK_LISTS) {  // (never on a real input: a thread sums its own row)
+        u64 ops = 0;
+        for (u32 i = s_aro[t]; i < s_aro[t + 1]; ++i) {
+            const u32 k = a_col[i];
+            if (k >= b_rows) continue;
+            const u32 b0 = b_ro[k], b1 = b_ro[k + 1];
+            ops += b1 > b0 ? min(u64(b1 - b0), b_nnz) : 0ull;
+        }
+        if ((ops >> 32) != 0) st->too_many = 1;
+    }
+    if (t < MASK_LISTS && s_cnt[t]) s_first[t] = atomicAdd(&st->cnt[t], s_cnt[t]);
+    if (t == MASK_LISTS && s_cnt[t]) atomicAdd(&st->idle, s_cnt[t]);
+    if (t == MASK_LISTS + 1 && s_products) atomicAdd(&st->products, s_products);
+    __syncthreads();
+    if (cls >= 0 && cls < MASK_LISTS) *list_at(lists, rows, (u32)cls, s_first[cls] + rank) = r0 + t;
+}
+
+// ------------------------------------------------------------------------------------------------ the product walk
+// All three classes walk a row's products FLATTENED, a batch of entries of A at a time: every lane of the group takes one
+// entry of the batch (its column, the bounds of "its" row of B), an inclusive scan of the B-row lengths numbers the
+// batch's products, and the lanes stride over those numbers -- a product's entry of A is found by binary search over
+// the scan (LDS).  The chain of dependent loads (A.col -> B.row_offsets -> B.col) is paid once per batch, not once per
+// entry of A, and no lane idles on a short row of B.  (First form: teams of eight lanes per entry of A, one entry after
+// the other -- a row of 256 entries of A cost 32 such chains, 120 us for a handful of rows of the scircuit stand-in.)
+// `end[i]`: products of the batch up to and including entry i;  `off[i]`: first entry of its B row - products before it.
+__device__ __forceinline__ u32 batch_entry(const u32* end, u32 n, u32 p)
+{
+    u32 lo = 0, hi = n;  // the first entry whose end lies beyond p
+    while (lo < hi) {
+        const u32 mid = (lo + hi) >> 1;
+        if (end[mid] <= p) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+// one counter per workgroup reaches the status block (atomics of every wave on one word serialise: see the classifying pass)
+__device__ __forceinline__ void add_hits(u64 hits, unsigned long long* s_hits, MaskedStatus* st)
+{
+    hits = wave_reduce_add(hits);
+    if (lane_id() == 0 && hits) atomicAdd(s_hits, (unsigned long long)hits);
+    __syncthreads();
+    if (threadIdx.x == 0 && *s_hits) atomicAdd(&st->hits, *s_hits);
+}
+
+// ------------------------------------------------------------------------------------------------ group class
+// 256 threads = 256 / L groups; per group 4 L columns and 4 L doubles of LDS for the mask row, 2 L words and L values for
+// the batch (16 KiB per workgroup whatever L): eight workgroups per CU, bounded by waves.
+template <typename T, u32 L>
+__global__ __launch_bounds__(256) void masked_group_kernel(const MaskedArgs<T> g)
+{
+    SPECK_POISON();
+    constexpr u32 NG = 256 / L, NP = 4 * L;
+    constexpr u32 K = L == 8 ? LIST_G8 : L == 16 ? LIST_G16 : L == 32 ? LIST_G32 : LIST_G64;
+    __shared__ double s_acc[NG * NP];
+    __shared__ u32 s_col[NG * NP];
+    __shared__ u32 s_end[256], s_off[256];
+    __shared__ T s_av[256];
+    __shared__ unsigned long long s_hits;
+    const u32 wl = lane_id(), gl = wl & (L - 1u), base_lane = wl & ~(L - 1u);
+    const u32 gid = threadIdx.x / L;
+    double* acc = s_acc + gid * NP;
+    u32* col = s_col + gid * NP;
+    u32* end = s_end + gid * L;
+    u32* off = s_off + gid * L;
+    T* av = s_av + gid * L;
+    if (threadIdx.x == 0) s_hits = 0;
+    __syncthreads();
+    const u32 n_list = g.st->cnt[K];
+    u64 hits = 0;
+    for (u32 e = blockIdx.x * NG + gid; e < n_list; e += gridDim.x * NG) {
+        const u32 row = *list_at(g.lists, g.rows, K, e);
+        const u32 m0 = g.m_ro[row], n = min(g.m_ro[row + 1] - m0, NP);
+        const u32 a0 = g.a_ro[row], a1 = g.a_ro[row + 1];
+#pragma unroll
+        for (u32 u = 0; u < 4; ++u) {
+            const u32 p = u * L + gl;
+            if (p < n) {
+                col[p] = g.m_col[m0 + p];
+                acc[p] = 0.0;
+            }
+        }
+        wave_lds_fence();
+        const u32 cmin = col[0], cmax = col[n - 1];  // (n >= 1: a row with work; no hit is marked yet)
+        for (u32 ab = a0; ab < a1; ab += L) {
+            const u32 nb = min(L, a1 - ab);
+            u32 len = 0, b0 = 0;
+            if (gl < nb) {
+                const u32 k = g.a_col[ab + gl];
+                av[gl] = g.a_val[ab + gl];
+                b0 = g.b_ro[k];
+                len = g.b_ro[k + 1] - b0;
+            }
+            u32 incl = len;
+#pragma unroll
+            for (u32 d = 1; d < L; d <<= 1) {
+                const u32 up = (u32)__shfl_up((int)incl, d, (int)L);
+                if (gl >= d) incl += up;
+            }
+            const u32 total = (u32)__shfl((int)incl, (int)(L - 1u), (int)L);
+            end[gl] = incl;
+            off[gl] = b0 - (incl - len);
+            wave_lds_fence();
+            // a product whose column `c` of B is in a register: looked up in the mask row, added on a hit
+            // (the four searches of a lane in lockstep, branch-free, lost: the products outside the mask row's span pay
+            //  for a search then -- cant stand-in 1.24 -> 1.47 ms, webbase triangles 0.74 -> 0.91 ms)
+            auto apply = [&](u32 i, u32 j, u32 c) {
+                if (c < cmin || c > cmax) return;
+                u32 lo = 0, hi = n;
+                while (lo < hi) {
+                    const u32 mid = (lo + hi) >> 1;
+                    if ((col[mid] & kColMask) < c) lo = mid + 1; else hi = mid;
+                }
+                if (lo >= n) return;
+                const u32 v = col[lo];
+                if ((v & kColMask) != c) return;
+                const T prod = av[i] * g.b_val[j];
+                atomicAdd(&acc[lo], (double)prod);
+                if (!(v & kHitBit)) atomicOr(&col[lo], kHitBit);
+                ++hits;
+            };
+            // (four loads of B's columns in flight per lane in either walk: a walk is a chain of such loads otherwise)
+            if (total >= 16u * nb) {
+                // long rows of B (16 entries on average): teams of eight lanes take the batch's entries in turn and walk
+                // "their" row eight entries at a time -- no search for the entry of A
+                constexpr u32 NT = L / 8u;
+                for (u32 i = gl / 8u; i < nb; i += NT) {
+                    const u32 before = i ? end[i - 1] : 0u;
+                    const u32 j1 = off[i] + end[i];
+                    for (u32 j = off[i] + before + (gl & 7u); j < j1; j += 4u * 8u) {
+                        u32 c[4];
+#pragma unroll
+                        for (u32 u = 0; u < 4; ++u) c[u] = j + u * 8u < j1 ? g.b_col[j + u * 8u] : kNoColumn;
+#pragma unroll
+                        for (u32 u = 0; u < 4; ++u) apply(i, j + u * 8u, c[u]);
+                    }
+                }
+            } else {
+                for (u32 p = gl; p < total; p += 4u * L) {
+                    u32 i[4], j[4], c[4];
+#pragma unroll
+                    for (u32 u = 0; u < 4; ++u) {
+                        const u32 q = p + u * L;
+                        i[u] = q < total ? batch_entry(end, nb, q) : 0u;
+                        j[u] = off[i[u]] + q;
+                        c[u] = q < total ? g.b_col[j[u]] : kNoColumn;
+                    }
+#pragma unroll
+                    for (u32 u = 0; u < 4; ++u) apply(i[u], j[u], c[u]);
+                }
+            }
+            wave_lds_fence();  // the next batch overwrites end / off
+        }
+        u32 cnt = 0;
+#pragma unroll
+        for (u32 u = 0; u < 4; ++u) {
+            const u32 p = u * L + gl;
+            const bool h = p < n && (col[p] & kHitBit);
+            if (h) {
+                const size_t at = size_t(m0 - g.base_m) + p;
+                g.acc[at] = acc[p];
+                if (g.hit) g.hit[at] = 1;
+            }
+            const u64 m = __ballot(h);
+            cnt += (u32)__popcll(L == 64 ? m : (m >> base_lane) & ((1ull << (L & 63u)) - 1ull));
+        }
+        if (gl == 0 && g.row_cnt) g.row_cnt[row] = cnt;
+        wave_lds_fence();  // the next row overwrites the slice
+    }
+    add_hits(hits, &s_hits, g.st);
+}
+
+// ------------------------------------------------------------------------------------------------ LDS class
+// One workgroup per row.  Dynamic LDS for `cap` entries: cap doubles | cap columns | 2 cap table slots of 16 bits, each the
+// position of a column in the row or 0xFFFF | 2 THREADS words for the batch.  cap = 1024, 256 threads: 18 KiB, eight
+// workgroups per CU by waves; cap = 4096, 1024 threads: 72 KiB, two workgroups per CU.  A row's table is the smallest
+// power of two >= twice its length (load <= 1/2): clearing and building cost what the row is long, not what the class
+// admits.  The columns of a row are distinct, so building the table races only for empty slots: one compare-and-swap on
+// the word that holds the slot, repeated when the OTHER half of the word changed meanwhile.  Probes read.
+__device__ __forceinline__ u32 table_slot(u32 c, u32 bits) { return (c * 0x9E3779B1u) >> (32u - bits); }
+
+template <typename T, u32 THREADS>
+__global__ __launch_bounds__(THREADS) void masked_lds_kernel(const MaskedArgs<T> g, u32 list, u32 cap)
+{
+    SPECK_POISON();
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    __shared__ u32 s_scan[THREADS / 64 + 1];
+    __shared__ unsigned long long s_hits;
+    double* acc = reinterpret_cast<double*>(smem);
+    u32* col = reinterpret_cast<u32*>(smem + size_t(cap) * 8);
+    u32* tab = col + cap;
+    u32* end = tab + cap;
+    u32* off = end + THREADS;
+    const u32 t = threadIdx.x;
+    if (t == 0) s_hits = 0;
+    const u32 n_list = g.st->cnt[list];
+    u64 hits = 0;
+    for (u32 e = blockIdx.x; e < n_list; e += gridDim.x) {
+        const u32 row = *list_at(g.lists, g.rows, list, e);
+        const u32 m0 = g.m_ro[row], n = min(g.m_ro[row + 1] - m0, cap);
+        const u32 a0 = g.a_ro[row], a1 = g.a_ro[row + 1];
+        u32 bits = 4;
+        while ((1u << bits) < 2u * n) ++bits;
+        const u32 slots = 1u << bits;
+        for (u32 p = t; p < n; p += THREADS) {
+            col[p] = g.m_col[m0 + p];
+            acc[p] = 0.0;
+        }
+        for (u32 w = t; w < slots / 2; w += THREADS) tab[w] = 0xFFFFFFFFu;
+        __syncthreads();
+        for (u32 p = t; p < n; p += THREADS) {
+            u32 s = table_slot(col[p], bits);
+            while (true) {
+                u32* w = &tab[s >> 1];
+                const u32 sh = (s & 1u) * 16u;
+                const u32 old = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (((old >> sh) & 0xFFFFu) != 0xFFFFu) {
+                    s = (s + 1u) & (slots - 1u);
+                    continue;
+                }
+                if (atomicCAS(w, old, (old & ~(0xFFFFu << sh)) | (p << sh)) == old) break;
+            }
+        }
+        const u32 cmin = col[0], cmax = col[n - 1];  // (no hit is marked before the barriers of the first batch)
+        for (u32 ab = a0; ab < a1; ab += THREADS) {
+            const u32 nb = min(THREADS, a1 - ab);
+            u32 len = 0, b0 = 0;
+            if (t < nb) {
+                const u32 k = g.a_col[ab + t];
+                b0 = g.b_ro[k];
+                len = g.b_ro[k + 1] - b0;
+            }
+            u32 total;
+            const u32 excl = block_exclusive_scan<THREADS>(len, s_scan, &total);  // (its barriers: the table is built)
+            end[t] = excl + len;
+            off[t] = b0 - excl;
+            __syncthreads();
+            auto apply = [&](u32 i, u32 j, u32 c) {
+                if (c < cmin || c > cmax) return;  // (rows of B ascend: only the part inside the mask row's span can hit)
+                u32 s = table_slot(c, bits);
+                while (true) {
+                    const u32 q = (tab[s >> 1] >> ((s & 1u) * 16u)) & 0xFFFFu;
+                    if (q == 0xFFFFu) return;
+                    const u32 v = col[q];
+                    if ((v & kColMask) == c) {
+                        const T prod = g.a_val[ab + i] * g.b_val[j];
+                        atomicAdd(&acc[q], (double)prod);
+                        if (!(v & kHitBit)) atomicOr(&col[q], kHitBit);
+                        ++hits;
+                        return;
+                    }
+                    s = (s + 1u) & (slots - 1u);
+                }
+            };
+            for (u32 p = t; p < total; p += 4u * THREADS) {
+                u32 i[4], j[4], c[4];
+#pragma unroll
+                for (u32 u = 0; u < 4; ++u) {
+                    const u32 q = p + u * THREADS;
+                    i[u] = q < total ? batch_entry(end, nb, q) : 0u;
+                    j[u] = off[i[u]] + q;
+                    c[u] = q < total ? g.b_col[j[u]] : kNoColumn;
+                }
+#pragma unroll
+                for (u32 u = 0; u < 4; ++u) apply(i[u], j[u], c[u]);
+            }
+            __syncthreads();  // the next batch overwrites end / off
+        }
+        u32 cnt = 0;
+        for (u32 p = t; p < n; p += THREADS)
+            if (col[p] & kHitBit) {
+                const size_t at = size_t(m0 - g.base_m) + p;
+                g.acc[at] = acc[p];
+                if (g.hit) g.hit[at] = 1;
+                ++cnt;
+            }
+        if (g.row_cnt) {
+            cnt = wave_reduce_add(cnt);
+            if (lane_id() == 0 && cnt) atomicAdd(&g.row_cnt[row], cnt);
+        }
+        __syncthreads();  // the next row overwrites the table
+    }
+    __syncthreads();
+    add_hits(hits, &s_hits, g.st);
+}
+
+// ------------------------------------------------------------------------------------------------ global class
+// One workgroup per row; the mask row is searched where it lies, a product is added to its accumulator with a global
+// atomic, the hit byte is a plain store of 1 (every writer stores the same).  Serves a handful of rows: correct first.
+template <typename T>
+__global__ __launch_bounds__(1024) void masked_global_kernel(const MaskedArgs<T> g)
+{
+    SPECK_POISON();
+    constexpr u32 THREADS = 1024;
+    __shared__ u32 s_end[THREADS], s_off[THREADS];
+    __shared__ u32 s_scan[THREADS / 64 + 1];
+    __shared__ unsigned long long s_hits;
+    const u32 t = threadIdx.x;
+    if (t == 0) s_hits = 0;
+    const u32 n_list = g.st->cnt[LIST_GLOBAL];
+    u64 hits = 0;
+    for (u32 e = blockIdx.x; e < n_list; e += gridDim.x) {
+        const u32 row = *list_at(g.lists, g.rows, LIST_GLOBAL, e);
+        const u32 m0 = g.m_ro[row], n = g.m_ro[row + 1] - m0;
+        const u32 a0 = g.a_ro[row], a1 = g.a_ro[row + 1];
+        const u32* mc = g.m_col + m0;
+        const size_t at0 = size_t(m0 - g.base_m);
+        const u32 cmin = mc[0], cmax = mc[n - 1];
+        for (u32 ab = a0; ab < a1; ab += THREADS) {
+            const u32 nb = min(THREADS, a1 - ab);
+            u32 len = 0, b0 = 0;
+            if (t < nb) {
+                const u32 k = g.a_col[ab + t];
+                b0 = g.b_ro[k];
+                len = g.b_ro[k + 1] - b0;
+            }
+            u32 total;
+            const u32 excl = block_exclusive_scan<THREADS>(len, s_scan, &total);
+            s_end[t] = excl + len;
+            s_off[t] = b0 - excl;
+            __syncthreads();
+            auto apply = [&](u32 i, u32 j, u32 c) {
+                if (c < cmin || c > cmax) return;
+                u32 lo = 0, hi = n;
+                while (lo < hi) {
+                    const u32 mid = (lo + hi) >> 1;
+                    if (mc[mid] < c) lo = mid + 1; else hi = mid;
+                }
+                if (lo >= n || mc[lo] != c) return;
+                const T prod = g.a_val[ab + i] * g.b_val[j];
+                atomicAdd(&g.acc[at0 + lo], (double)prod);
+                if (g.hit) g.hit[at0 + lo] = 1;
+                ++hits;
+            };
+            for (u32 p = t; p < total; p += 4u * THREADS) {
+                u32 i[4], j[4], c[4];
+#pragma unroll
+                for (u32 u = 0; u < 4; ++u) {
+                    const u32 q = p + u * THREADS;
+                    i[u] = q < total ? batch_entry(s_end, nb, q) : 0u;
+                    j[u] = s_off[i[u]] + q;
+                    c[u] = q < total ? g.b_col[j[u]] : kNoColumn;
+                }
+#pragma unroll
+                for (u32 u = 0; u < 4; ++u) apply(i[u], j[u], c[u]);
+            }
+            __syncthreads();  // the next batch overwrites end / off
+        }
+        if (g.row_cnt) {
+            __threadfence_block();
+            __syncthreads();  // the row's hit bytes are complete
+            u32 cnt = 0;
+            for (u32 p = t; p < n; p += THREADS) cnt += g.hit[at0 + p] ? 1u : 0u;
+            cnt = wave_reduce_add(cnt);
+            if (lane_id() == 0 && cnt) atomicAdd(&g.row_cnt[row], cnt);
+        }
+    }
+    __syncthreads();
+    add_hits(hits, &s_hits, g.st);
+}
+
+// ------------------------------------------------------------------------------------------------ finish
+// STRUCTURE: hits per row -> exclusive scan (1024 rows per workgroup, the workgroup sums scanned by one workgroup) -> the
+// hit entries of every row moved to their place, L lanes per row.
+__global__ __launch_bounds__(1024) void masked_block_sums_kernel(const u32* __restrict__ row_cnt, u32 rows, u32* __restrict__ block_sums)
+{
+    SPECK_POISON();
+    __shared__ u32 s_scan[1024 / 64 + 1];
+    const u32 r = blockIdx.x * 1024u + threadIdx.x;
+    u32 total;
+    (void)block_exclusive_scan<1024>(r < rows ? row_cnt[r] : 0u, s_scan, &total);
+    if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(1024) void masked_scan_sums_kernel(u32* __restrict__ block_sums, u32 n)
+{
+    SPECK_POISON();
+    __shared__ u32 s_scan[1024 / 64 + 1];
+    u32 carry = 0;
+    for (u32 i0 = 0; i0 < n; i0 += 1024) {
+        const u32 i = i0 + threadIdx.x;
+        const u32 v = i < n ? block_sums[i] : 0u;
+        u32 total;
+        const u32 ex = block_exclusive_scan<1024>(v, s_scan, &total);
+        if (i < n) block_sums[i] = carry + ex;
+        carry += total;
+    }
+}
+
+__global__ __launch_bounds__(1024) void masked_offsets_kernel(const u32* __restrict__ row_cnt, u32 rows, const u32* __restrict__ block_sums,
+                                                              u32* __restrict__ new_ro, MaskedStatus* __restrict__ st)
+{
+    SPECK_POISON();
+    __shared__ u32 s_scan[1024 / 64 + 1];
+    const u32 r = blockIdx.x * 1024u + threadIdx.x;
+    const u32 len = r < rows ? row_cnt[r] : 0u;
+    u32 total;
+    const u32 ex = block_exclusive_scan<1024>(len, s_scan, &total);
+    const u32 off = block_sums[blockIdx.x] + ex;
+    if (r < rows) new_ro[r] = off;
+    if (r + 1 == rows) {
+        new_ro[rows] = off + len;
+        st->nnz_out = off + len;
+    }
+}
+
+// The compaction needs no rows: C's entries are M's entries with a hit, in M's order, so an entry's place is the number of
+// hits in front of it -- a scan over the hit bytes, 4096 entries per workgroup (a word of four bytes per thread), the
+// workgroup sums scanned by masked_scan_sums_kernel.  (First form: eight lanes per row looking up the row's new offset --
+// 0.37 ms for the 1 M short rows of the webbase stand-in.)
+constexpr u32 kCompactTile = 4096;
+
+__device__ __forceinline__ u32 hit_word(const u32* __restrict__ hit32, u64 e0, u64 n)
+{
+    if (e0 >= n) return 0u;
+    u32 w = hit32[e0 >> 2] & 0x01010101u;
+    if (e0 + 4 > n) w &= 0xFFFFFFFFu >> (8u * (u32)(e0 + 4 - n));  // (the bytes behind the last entry were never written)
+    return w;
+}
+
+__global__ __launch_bounds__(1024) void masked_tile_sums_kernel(const u32* __restrict__ hit32, u64 n, u32* __restrict__ tile_sums)
+{
+    SPECK_POISON();
+    __shared__ u32 s_scan[1024 / 64 + 1];
+    const u64 e0 = (u64(blockIdx.x) * 1024 + threadIdx.x) * 4;
+    u32 total;
+    (void)block_exclusive_scan<1024>((u32)__popc(hit_word(hit32, e0, n)), s_scan, &total);
+    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
+}
+
+template <typename T>
+__global__ __launch_bounds__(1024) void masked_compact_kernel(const u32* __restrict__ hit32, u64 n, const u32* __restrict__ tile_sums,
+                                                              const u32* __restrict__ m_col, const double* __restrict__ acc,
+                                                              u32* __restrict__ c_col, T* __restrict__ c_val)
+{
+    SPECK_POISON();
+    __shared__ u32 s_scan[1024 / 64 + 1];
+    const u64 e0 = (u64(blockIdx.x) * 1024 + threadIdx.x) * 4;
+    const u32 w = hit_word(hit32, e0, n);
+    u32 total;
+    u32 to = tile_sums[blockIdx.x] + block_exclusive_scan<1024>((u32)__popc(w), s_scan, &total);
+#pragma unroll
+    for (u32 k = 0; k < 4; ++k)
+        if ((w >> (8u * k)) & 1u) {
+            c_col[to] = m_col[e0 + k];
+            c_val[to] = (T)acc[e0 + k];
+            ++to;
+        }
+}
+
+// FULL_PATTERN: C.row_offsets = M.row_offsets rebased to 0; the values rounded where the accumulators are not C's own
+__global__ __launch_bounds__(256) void masked_rebase_kernel(const u32* __restrict__ m_ro, u32 rows, u32* __restrict__ c_ro)
+{
+    SPECK_POISON();
+    const u32 base = m_ro[0];
+    for (u64 r = u64(blockIdx.x) * 256 + threadIdx.x; r <= rows; r += u64(gridDim.x) * 256) c_ro[r] = m_ro[r] - base;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void masked_round_kernel(const double* __restrict__ acc, u64 n, T* __restrict__ out)
+{
+    SPECK_POISON();
+    for (u64 i = u64(blockIdx.x) * 256 + threadIdx.x; i < n; i += u64(gridDim.x) * 256) out[i] = (T)acc[i];
+}
+
+// ------------------------------------------------------------------------------------------------ host
+int ensure(void** p, size_t* have, size_t want)
+{
+    if (*have >= want && *p) return SPECK_OK;
+    if (*p) (void)guarded_free(*p);
+    *p = nullptr, *have = 0;
+    HIP_TRY(guarded_malloc(p, want));
+    *have = want;
+    return SPECK_OK;
+}
+
+inline size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
+
+u32 grid_of(u64 work, u32 cap) { return (u32)std::max<u64>(1, std::min<u64>(work, cap)); }
+
+// dynamic LDS of the LDS class: accumulators | columns | table | batch
+constexpr u32 lds_bytes(u32 cap, u32 threads) { return cap * 16u + threads * 8u; }
+
+// The buffers C will own once the call has completed, by the multiply's rule: row_offsets reused when C->rows == rows(A),
+// data / col_ids re-allocated only when C->nnz differs.  Nothing of C changes before publish().
+struct COut {
+    u32* ro = nullptr;
+    u32* col = nullptr;
+    void* val = nullptr;
+    bool own_ro = false, own_data = false;
+    void discard()
+    {
+        if (own_ro && ro) (void)guarded_free(ro);
+        if (own_data && col) (void)guarded_free(col);
+        if (own_data && val) (void)guarded_free(val);
+        *this = COut{};
+    }
+};
+
+int prepare_c(const speck_dcsr* C, u64 rows, u64 nnz_out, size_t vsize, COut* out)
+{
+    if (C->rows == rows && C->row_offsets) out->ro = C->row_offsets;
+    else {
+        HIP_TRY(guarded_malloc(reinterpret_cast<void**>(&out->ro), (size_t(rows) + 1) * sizeof(u32)));
+        out->own_ro = true;
+    }
+    if (C->nnz != nnz_out || !C->data || !C->col_ids) {
+        out->own_data = true;
+        const hipError_t e1 = guarded_malloc(&out->val, std::max<size_t>(nnz_out, 1) * vsize);
+        const hipError_t e2 = e1 == hipSuccess ? guarded_malloc(reinterpret_cast<void**>(&out->col), std::max<size_t>(nnz_out, 1) * 4) : e1;
+        if (e1 != hipSuccess || e2 != hipSuccess) {
+            (void)hipGetLastError();
+            out->discard();
+            return SPECK_ERR_OOM;
+        }
+    } else {
+        out->val = C->data;
+        out->col = C->col_ids;
+    }
+    return SPECK_OK;
+}
+
+void publish_c(speck_dcsr* C, u64 rows, u64 cols, u64 nnz_out, COut* out)
+{
+    if (out->own_data) {
+        if (C->data) (void)guarded_free(C->data);
+        if (C->col_ids) (void)guarded_free(C->col_ids);
+    }
+    if (C->row_offsets && C->row_offsets != out->ro) (void)guarded_free(C->row_offsets);
+    C->rows = rows, C->cols = cols, C->nnz = nnz_out;
+    C->data = out->val, C->col_ids = out->col, C->row_offsets = out->ro;
+    *out = COut{};
+}
+
+template <typename T>
+int masked_run(MaskedScratch* sc, hipStream_t s, const speck_dcsr* A, const speck_dcsr* B, const speck_dcsr* M, speck_dcsr* C,
+               bool full, speck_masked_info* info, COut* out)
+{
+    const u32 rows = (u32)A->rows;
+    const u64 nnz_m = M->nnz;
+    if (rows == 0) {
+        int rc = prepare_c(C, 0, 0, sizeof(T), out);
+        if (rc != SPECK_OK) return rc;
+        HIP_TRY(hipMemsetAsync(out->ro, 0, sizeof(u32), s));
+        HIP_TRY(hipStreamSynchronize(s));
+        publish_c(C, 0, B->cols, 0, out);
+        return SPECK_OK;
+    }
+
+    // status | lists (four regions of `rows` words) | hits per row | new row offsets | workgroup sums of the scan
+    const u32 nblk = (rows + 1023) / 1024;
+    const size_t list_bytes = up256(size_t(4) * rows * 4), row_bytes = up256((size_t(rows) + 1) * 4), sum_bytes = up256(size_t(nblk) * 4);
+    int rc = ensure(&sc->fixed, &sc->fixed_bytes, 256 + list_bytes + 2 * row_bytes + sum_bytes);
+    if (rc != SPECK_OK) return rc;
+    unsigned char* fb = static_cast<unsigned char*>(sc->fixed);
+    MaskedStatus* st = reinterpret_cast<MaskedStatus*>(fb);
+    u32* lists = reinterpret_cast<u32*>(fb + 256);
+    u32* row_cnt = reinterpret_cast<u32*>(fb + 256 + list_bytes);
+    u32* new_ro = reinterpret_cast<u32*>(fb + 256 + list_bytes + row_bytes);
+    u32* block_sums = reinterpret_cast<u32*>(fb + 256 + list_bytes + 2 * row_bytes);
+    static_assert(sizeof(MaskedStatus) <= 256, "status block");
+    // accumulators | hit bytes | hits per tile of the compaction
+    const bool acc_in_c = full && std::is_same<T, double>::value;
+    const u32 ntiles = (u32)((nnz_m + kCompactTile - 1) / kCompactTile);
+    const size_t acc_bytes = acc_in_c ? 0 : up256(nnz_m * 8), hit_bytes = full ? 0 : up256(nnz_m);
+    const size_t tile_bytes = full ? 0 : up256(size_t(ntiles) * 4);
+    if (acc_bytes + hit_bytes + tile_bytes) {
+        rc = ensure(&sc->var, &sc->var_bytes, acc_bytes + hit_bytes + tile_bytes);
+        if (rc != SPECK_OK) return rc;
+    }
+    unsigned char* vb = static_cast<unsigned char*>(sc->var);
+
+    // ---- the verdict on A, M (this file) and B (the multiply's check), read before anything else starts
+    HIP_TRY(hipMemsetAsync(st, 0, sizeof(MaskedStatus), s));
+    if ((A->nnz + nnz_m) / rows >= 32)
+        SPECK_LAUNCH(masked_classify_kernel<256>, dim3((rows + 255) / 256), dim3(256), 0, s, A->row_offsets, A->col_ids, A->nnz,
+                     B->row_offsets, (u32)B->rows, (u32)B->cols, B->nnz, M->row_offsets, M->col_ids, nnz_m, rows, sc->group_max,
+                     sc->lds_max, lists, st);
+    else
+        SPECK_LAUNCH(masked_classify_kernel<1024>, dim3((rows + 1023) / 1024), dim3(1024), 0, s, A->row_offsets, A->col_ids, A->nnz,
+                     B->row_offsets, (u32)B->rows, (u32)B->cols, B->nnz, M->row_offsets, M->col_ids, nnz_m, rows, sc->group_max,
+                     sc->lds_max, lists, st);
+    launch_validate_b(s, B->row_offsets, B->col_ids, (u32)B->rows, (u32)B->cols, B->nnz, &st->verdict_b);
+    MaskedStatus h{};
+    HIP_TRY(hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (take_launch_error()) return SPECK_ERR_HIP;
+    if (h.invalid) return SPECK_ERR_INVALID;
+    if (h.unsorted || (h.verdict_b & 4u)) return SPECK_ERR_UNSORTED;
+    if (h.too_many) return SPECK_ERR_DIM_LIMIT;
+
+    // ---- one product walk per row with work
+    if (full) {
+        rc = prepare_c(C, rows, nnz_m, sizeof(T), out);
+        if (rc != SPECK_OK) return rc;
+    }
+    double* acc = acc_in_c ? static_cast<double*>(out->val) : reinterpret_cast<double*>(vb);
+    u8* hit = full ? nullptr : vb + acc_bytes;
+    if (nnz_m) {
+        HIP_TRY(hipMemsetAsync(acc, 0, nnz_m * 8, s));
+        if (hit) HIP_TRY(hipMemsetAsync(hit, 0, nnz_m, s));
+    }
+    if (!full) HIP_TRY(hipMemsetAsync(row_cnt, 0, (size_t(rows) + 1) * 4, s));
+    const MaskedArgs<T> g{A->row_offsets, A->col_ids, static_cast<const T*>(A->data), B->row_offsets, B->col_ids,
+                          static_cast<const T*>(B->data), M->row_offsets, M->col_ids, rows, h.base_m, lists, st, acc, hit,
+                          full ? nullptr : row_cnt};
+    // (grids: what a CU keeps resident x 256 CUs at most -- the kernels stride over their lists)
+    // The classes hold disjoint rows and are bound by latency more than by throughput (a launch lasts as long as its
+    // heaviest rows): the narrow groups stay on the call's stream, the others run beside them on side streams.
+    const bool work[4] = {h.cnt[LIST_G8] != 0, (h.cnt[LIST_G16] | h.cnt[LIST_G32]) != 0, h.cnt[LIST_G64] != 0,
+                          (h.cnt[LIST_LDS_S] | h.cnt[LIST_LDS_L] | h.cnt[LIST_GLOBAL]) != 0};
+    const bool forked = work[0] + work[1] + work[2] + work[3] >= 2;
+    hipStream_t on[4] = {s, s, s, s};
+    if (forked) {
+        if (!sc->fork) {
+            HIP_TRY(hipEventCreateWithFlags(&sc->fork, hipEventDisableTiming));
+            for (int i = 0; i < 3; ++i) {
+                HIP_TRY(hipStreamCreateWithFlags(&sc->side[i], hipStreamNonBlocking));
+                HIP_TRY(hipEventCreateWithFlags(&sc->join[i], hipEventDisableTiming));
+            }
+        }
+        HIP_TRY(hipEventRecord(sc->fork, s));
+        for (int i = 1; i < 4; ++i)
+            if (work[i]) {
+                on[i] = sc->side[i - 1];
+                HIP_TRY(hipStreamWaitEvent(on[i], sc->fork, 0));
+            }
+    }
+    if (h.cnt[LIST_G8]) SPECK_LAUNCH((masked_group_kernel<T, 8>), dim3(grid_of((h.cnt[LIST_G8] + 31) / 32, 2048)), dim3(256), 0, on[0], g);
+    if (h.cnt[LIST_G16]) SPECK_LAUNCH((masked_group_kernel<T, 16>), dim3(grid_of((h.cnt[LIST_G16] + 15) / 16, 2048)), dim3(256), 0, on[1], g);
+    if (h.cnt[LIST_G32]) SPECK_LAUNCH((masked_group_kernel<T, 32>), dim3(grid_of((h.cnt[LIST_G32] + 7) / 8, 2048)), dim3(256), 0, on[1], g);
+    if (h.cnt[LIST_G64]) SPECK_LAUNCH((masked_group_kernel<T, 64>), dim3(grid_of((h.cnt[LIST_G64] + 3) / 4, 2048)), dim3(256), 0, on[2], g);
+    if (h.cnt[LIST_LDS_S])
+        SPECK_LAUNCH((masked_lds_kernel<T, 256>), dim3(grid_of(h.cnt[LIST_LDS_S], 2048)), dim3(256), lds_bytes(kLdsSmall, 256), on[3], g,
+                     (u32)LIST_LDS_S, kLdsSmall);
+    if (h.cnt[LIST_LDS_L]) {
+        // more than 64 KiB of LDS needs the opt-in (with every launch, as numeric.hip does: it belongs to the current device)
+        note_launch_status(hipFuncSetAttribute(reinterpret_cast<const void*>(&masked_lds_kernel<T, 1024>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(kLdsMax, 1024)),
+                           "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+        SPECK_LAUNCH((masked_lds_kernel<T, 1024>), dim3(grid_of(h.cnt[LIST_LDS_L], 512)), dim3(1024), lds_bytes(kLdsMax, 1024), on[3], g,
+                     (u32)LIST_LDS_L, kLdsMax);
+    }
+    if (h.cnt[LIST_GLOBAL]) SPECK_LAUNCH(masked_global_kernel<T>, dim3(grid_of(h.cnt[LIST_GLOBAL], 512)), dim3(1024), 0, on[3], g);
+    if (forked)
+        for (int i = 1; i < 4; ++i)
+            if (work[i]) {
+                HIP_TRY(hipEventRecord(sc->join[i - 1], on[i]));
+                HIP_TRY(hipStreamWaitEvent(s, sc->join[i - 1], 0));
+            }
+
+    // ---- finish
+    u64 nnz_out = nnz_m;
+    if (!full) {
+        SPECK_LAUNCH(masked_block_sums_kernel, dim3(nblk), dim3(1024), 0, s, row_cnt, rows, block_sums);
+        SPECK_LAUNCH(masked_scan_sums_kernel, dim3(1), dim3(1024), 0, s, block_sums, nblk);
+        SPECK_LAUNCH(masked_offsets_kernel, dim3(nblk), dim3(1024), 0, s, row_cnt, rows, block_sums, new_ro, st);
+    }
+    HIP_TRY(hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (take_launch_error()) return SPECK_ERR_HIP;
+    if (!full) {
+        nnz_out = h.nnz_out;
+        rc = prepare_c(C, rows, nnz_out, sizeof(T), out);
+        if (rc != SPECK_OK) return rc;
+        if (nnz_out) {
+            const u32* hit32 = reinterpret_cast<const u32*>(hit);
+            u32* tile_sums = reinterpret_cast<u32*>(vb + acc_bytes + hit_bytes);
+            SPECK_LAUNCH(masked_tile_sums_kernel, dim3(ntiles), dim3(1024), 0, s, hit32, nnz_m, tile_sums);
+            SPECK_LAUNCH(masked_scan_sums_kernel, dim3(1), dim3(1024), 0, s, tile_sums, ntiles);
+            SPECK_LAUNCH(masked_compact_kernel<T>, dim3(ntiles), dim3(1024), 0, s, hit32, nnz_m, tile_sums, M->col_ids + h.base_m, acc,
+                         out->col, static_cast<T*>(out->val));
+        }
+        HIP_TRY(hipMemcpyAsync(out->ro, new_ro, (size_t(rows) + 1) * 4, hipMemcpyDeviceToDevice, s));
+    } else {
+        SPECK_LAUNCH(masked_rebase_kernel, dim3(grid_of((u64(rows) + 256) / 256, 4096)), dim3(256), 0, s, M->row_offsets, rows, out->ro);
+        if (nnz_m) {
+            HIP_TRY(hipMemcpyAsync(out->col, M->col_ids + h.base_m, nnz_m * 4, hipMemcpyDeviceToDevice, s));
+            if (!acc_in_c)
+                SPECK_LAUNCH(masked_round_kernel<T>, dim3(grid_of((nnz_m + 255) / 256, 8192)), dim3(256), 0, s, acc, nnz_m,
+                             static_cast<T*>(out->val));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    if (take_launch_error()) return SPECK_ERR_HIP;
+    publish_c(C, rows, B->cols, nnz_out, out);
+    if (info) {
+        info->rows_idle = h.idle;
+        info->rows_class[0] = u64(h.cnt[LIST_G8]) + h.cnt[LIST_G16] + h.cnt[LIST_G32] + h.cnt[LIST_G64];
+        info->rows_class[1] = u64(h.cnt[LIST_LDS_S]) + h.cnt[LIST_LDS_L];
+        info->rows_class[2] = h.cnt[LIST_GLOBAL];
+        info->products = h.products;
+        info->hits = h.hits;
+        info->nnz_out = nnz_out;
+    }
+    return SPECK_OK;
+}
+
+// debug option guard_bytes: the canary zones of the temporaries and of C's buffers after the call
+int check_masked_guards(const MaskedScratch* sc, hipStream_t s, const speck_dcsr* C, int rc)
+{
+    if (!guard_bytes()) return rc;
+    std::vector<GuardZone> z;
+    const void* whole[] = {sc->fixed, sc->var, C->data, C->col_ids, C->row_offsets};
+    static const char* names[] = {"masked lists", "masked accumulators", "C.data", "C.col_ids", "C.row_offsets"};
+    std::vector<int> owner;
+    for (int i = 0; i < 5; ++i) {
+        const size_t before = z.size();
+        if (whole[i]) guard_zones_of(whole[i], &z);
+        for (size_t k = before; k < z.size(); ++k) owner.push_back(i);
+    }
+    int bad = -1;
+    size_t at = 0;
+    const int n = guard_check(z, s, &bad, &at);
+    if (n == 0) return rc;
+    if (n < 0) return rc == SPECK_OK ? SPECK_ERR_HIP : rc;
+    std::fprintf(stderr, "speck_amd: guard_bytes: %d canary zone(s) touched by the masked product; first: %s, byte %zu\n", n,
+                 names[owner[bad]], at);
+    return rc == SPECK_OK ? SPECK_ERR_HIP : rc;
+}
+
+bool csr_args_ok(const speck_dcsr* X, bool needs_values)
+{
+    if (X->rows && !X->row_offsets) return false;
+    if (X->nnz && (!X->col_ids || (needs_values && !X->data))) return false;
+    return true;
+}
+
+bool shares_buffer(const speck_dcsr* C, const speck_dcsr* X)
+{
+    const void* mine[] = {C->data, C->col_ids, C->row_offsets};
+    const void* theirs[] = {X->data, X->col_ids, X->row_offsets};
+    for (const void* p : mine)
+        for (const void* q : theirs)
+            if (p && p == q) return true;
+    return false;
+}
+
+template <typename T>
+int masked_impl(speck_config* cfg, const speck_dcsr* A, const speck_dcsr* B, const speck_dcsr* M, speck_dcsr* C, int flags,
+                speck_masked_info* info)
+{
+    if (!A || !B || !M || !C) return SPECK_ERR_INVALID;
+    if (flags != SPECK_MASK_STRUCTURE && flags != SPECK_MASK_FULL_PATTERN) return SPECK_ERR_INVALID;
+    if (A->cols != B->rows || M->rows != A->rows || M->cols != B->cols) return SPECK_ERR_INVALID;
+    if (A->rows > (1ull << 27) || A->cols > (1ull << 27) || B->cols > (1ull << 27)) return SPECK_ERR_DIM_LIMIT;
+    if (A->nnz >= (1ull << 32) || B->nnz >= (1ull << 32) || M->nnz >= (1ull << 32)) return SPECK_ERR_INVALID;
+    if (!csr_args_ok(A, true) || !csr_args_ok(B, true) || !csr_args_ok(M, false)) return SPECK_ERR_INVALID;
+    if (shares_buffer(C, A) || shares_buffer(C, B) || shares_buffer(C, M)) return SPECK_ERR_INVALID;
+    if (info) *info = speck_masked_info{};
+    if (!cfg) {  // (a config exists only where a device does)
+        int n = 0;
+        if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
+            (void)hipGetLastError();
+            return SPECK_ERR_NO_DEVICE;
+        }
+    }
+    MaskedScratch own;
+    MaskedScratch* sc = cfg ? masked_scratch(cfg) : &own;
+    const hipStream_t s = cfg ? sort_stream(cfg) : nullptr;
+    (void)take_launch_error();
+    COut out;
+    int rc = masked_run<T>(sc, s, A, B, M, C, flags == SPECK_MASK_FULL_PATTERN, info, &out);
+    if (rc != SPECK_OK) {
+        (void)hipStreamSynchronize(s);
+        out.discard();  // (what was allocated for C and never handed over)
+        if (info) *info = speck_masked_info{};
+    }
+    rc = check_masked_guards(sc, s, C, rc);
+    if (!cfg) {
+        (void)hipStreamSynchronize(s);
+        own.release();
+    }
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int speck_multiply_masked_f64(speck_config* cfg, const speck_dcsr* A, const speck_dcsr* B, const speck_dcsr* M, speck_dcsr* C,
+                              int flags, speck_masked_info* info)
+{
+    return masked_impl<double>(cfg, A, B, M, C, flags, info);
+}
+
+int speck_multiply_masked_f32(speck_config* cfg, const speck_dcsr* A, const speck_dcsr* B, const speck_dcsr* M, speck_dcsr* C,
+                              int flags, speck_masked_info* info)
+{
+    return masked_impl<float>(cfg, A, B, M, C, flags, info);
+}
+
+}  // extern "C"

@@ -30,6 +30,7 @@
 #include "guards.hpp"
 #include "launch.hpp"
 #include "row_groups.hpp"
+#include "masked.hpp"
 #include "sort_rows.hpp"
 
 using namespace speck;
@@ -240,6 +241,7 @@ struct speck_config {
     // layout the arena's were last filled for
     std::vector<GuardZone> arena_zones, gpool_zones, nfpool_zones;
     SortScratch sort;  // temporaries and class limits of speck_sort_rows_* (sort_rows.hip)
+    MaskedScratch masked;  // ... and of speck_multiply_masked_* (masked.hip)
     const void* zones_arena = nullptr;
     u64 zones_m = 0, zones_nnz = 0, zones_gap = 0;
     bool gpool_zones_filled = false;
@@ -1923,6 +1925,7 @@ int multiply_impl(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, spe
 namespace speck {
 SortScratch* sort_scratch(speck_config* c) { return &c->sort; }
 hipStream_t sort_stream(speck_config* c) { return main_stream(c); }
+MaskedScratch* masked_scratch(speck_config* c) { return &c->masked; }
 }  // namespace speck
 
 extern "C" {
@@ -2036,6 +2039,7 @@ int speck_config_destroy(speck_config* c)
     if (c->gpool) (void)guarded_free(c->gpool);
     if (c->nfpool) (void)guarded_free(c->nfpool);
     c->sort.release();
+    c->masked.release();
     if (c->pred.off) (void)guarded_free(c->pred.off);
     if (c->gpred.off) (void)guarded_free(c->gpred.off);
     if (c->d_stats) (void)hipFree(c->d_stats);
@@ -2117,9 +2121,12 @@ int speck_config_set_option(speck_config* c, const char* name, int64_t value)
         c->gpool = nullptr, c->gpool_bytes = 0, c->gpool_zones.clear(), c->spill = SpillBuffers{};
         c->spec_valid = false;
         c->sort.release();
+        c->masked.release();
     }
     else if (n == "sort_reg_max") c->sort.reg_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_REG_MAX);
     else if (n == "sort_lds_max") c->sort.lds_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_LDS_MAX);
+    else if (n == "mask_group_max") c->masked.group_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_MASK_GROUP_MAX);
+    else if (n == "mask_lds_max") c->masked.lds_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_MASK_LDS_MAX);
     else if (n == "walk_debug") set_walk_debug((u32)value & 0xFFFFu, (u32)(value >> 16));  // (tile rows | flags << 16)
     else if (n == "verify_inputs") c->verify_inputs = value != 0, c->snap_for_arena = false, forget(false);
     else if (n == "num_verify") c->num_verify = (int)value, forget(false);
