@@ -31,8 +31,9 @@ struct CsrView {
 // Symbolic classes: chosen from the analysis pass' per-row upper bound `ops` (= exact
 // product count), the A-row length and the reachable column range.
 enum SymClass : u8 {
-    SYM_G16 = 0,    // 16 lanes per row, 64-key LDS set       (ops <= 51)
-    SYM_W256 = 1,   // one wave per row, 256-key set          (ops <= 204)
+    SYM_G16 = 0,    // 16 lanes per row: <= 64 products from <= 16 entries of A, cols(B) <= 2^26, sorted in registers
+                    //   (esc.hpp) -- a register class, no key set
+    SYM_W256 = 1,   // 32 lanes per row, 512-key set          (ops <= 204)
     SYM_W1K = 2,    // one wave per row, 1024-key set         (ops <= 819)
     SYM_B4K = 3,    // workgroup(256) per row, 4096-key set   (ops <= 3276)
     SYM_B16K = 4,   // workgroup(512) per row, 16384-key set  (ops <= 13107)
@@ -45,8 +46,9 @@ enum SymClass : u8 {
     SYM_GH = 9,     // key set in GLOBAL memory (one workgroup(1024) per row, table in the scratch pool): rows wider
                     //   than one SYM_BM2 window with few products per window -- every window of the bitmap costs a
                     //   fixed ~8 us, a global compare-and-swap a fraction of a nanosecond at 4096 in flight
-    SYM_G8 = 10,    // 8 lanes per row (8 rows per wave), 32-key LDS set (ops <= 25)
-    SYM_W128 = 11,  // 16 lanes per row (four rows per wave), 128-key LDS set (ops <= 102)
+    SYM_G8 = 10,    // 8 lanes per row (8 rows per wave): <= 32 products from <= 8 entries of A, sorted in registers
+                    //   (esc.hpp) -- a register class, no key set
+    SYM_W128 = 11,  // 16 lanes per row (four rows per wave), 256-key LDS set (ops <= 102)
     SYM_R32 = 12,   // 32 lanes per row (two rows per wave): <= 128 products from <= 32 entries of A, columns sorted in
                     //   registers (esc_wide.hpp) -- no key set
     SYM_R64 = 13,   // a wave per row: <= 256 products from <= 64 entries of A, sorted in registers
@@ -56,19 +58,22 @@ enum SymClass : u8 {
 // Numeric classes: chosen from the EXACT nnz of the C row (symbolic result).
 enum NumClass : u8 {
     NUM_DIRECT = 0,  // A row has one entry: C row = a * B row (already sorted); 16 lanes/row
-    NUM_G16 = 1,     // 16 lanes per row, 64-entry table, rank sort        (nnz <= 42)
-    NUM_W128 = 2,    // wave per row, 128-entry table, rank sort           (nnz <= 85)
+    NUM_G16 = 1,     // 16 lanes per row: <= 64 products from <= 16 entries of A, cols(B) <= 2^26 -- expand / sort /
+                     //   compress in registers (esc.hpp), whatever the nnz
+    NUM_W128 = 2,    // 32 lanes per row, 128-entry table, rank sort       (nnz <= 85)
     NUM_W512 = 3,    // wave per row, 512-entry table, 2-level bitmap sort (nnz <= 341)
-    NUM_B2K = 4,     // workgroup(256), 2048-entry table, bitmap sort      (nnz <= 1365)
-    NUM_B8K = 5,     // workgroup(512), 8192-entry table, bitmap sort      (nnz <= 5461)
+    NUM_B2K = 4,     // workgroup(256), 2048-entry table, bitmap sort      (nnz <= 1740: load 0.85)
+    NUM_B8K = 5,     // workgroup(512), 8192-entry table, bitmap sort      (nnz <= 6963: load 0.85; rows of <= 3481
+                     //   entries in a launch of their own with a 4096-entry table)
     NUM_D1 = 6,      // dense column-window accumulator, narrow column range, workgroup(256)
     NUM_D2 = 7,      // dense accumulator, 16 Ki columns/window, multi-window, workgroup(1024)
     NUM_G = 8,       // global-memory hash spill (heavy rows with a very wide column range)
     NUM_W256 = 9,    // half a wave per row (two rows per wave), 256-entry table, 2-level bitmap sort (nnz <= 170):
                      //   the lower half of what used to be NUM_W512, at twice the rows in flight per wave
     NUM_NFCOPY = 10, // row already computed by the symbolic phase (SYM_NF): copy scratch slot -> C
-    NUM_G8 = 11,     // 8 lanes per row (8 rows per wave), 32-entry table, rank sort   (nnz <= 21): the small-row
-                     //   kernel is latency x occupancy bound -- twice the rows in flight per wave
+    NUM_G8 = 11,     // 8 lanes per row (8 rows per wave): <= 32 products from <= 8 entries of A -- expand / sort /
+                     //   compress in registers (esc.hpp), whatever the nnz: the small-row kernel is latency x
+                     //   occupancy bound -- twice the rows in flight per wave
     NUM_R32 = 12,    // 32 lanes per row: <= 128 products from <= 32 entries of A, column range < 2^25 -- expand / sort /
                      //   compress in registers (esc_wide.hpp), whatever the nnz
     NUM_R64 = 13,    // a wave per row: <= 256 products from <= 64 entries, column range < 2^24
@@ -79,6 +84,8 @@ enum NumClass : u8 {
 // Key sets of the sub-wave symbolic classes: TWICE the slots the 4/5 rule of the reference (Multiply.cu:263) would give
 // them -- a key costs 4 bytes, the LDS of these launches is nowhere near the limit, and at a load <= 0.4 the probing
 // loops (whose length is the longest chain of the wave) mostly do not start (mac_econ stand-in -2.5 %).
+// (kSymG8* / kSymG16* are not read by the classifier: SYM_G8 / SYM_G16 are register classes, taken by kNumEscMaxOps /
+//  kNumEsc16MaxOps products and kNumEscMaxLen / kNumEsc16MaxLen entries of A)
 constexpr u32 kSymG8Cap = 64, kSymG8MaxOps = 25;
 constexpr u32 kSymG16Cap = 128, kSymG16MaxOps = 51;
 constexpr u32 kSymW128Cap = 256, kSymW128MaxOps = 102;
@@ -111,7 +118,14 @@ constexpr u32 kSymBm2Words = 32768;   // 128 KiB -> 1048576 columns per window
 #define SPECK_LOAD_TINY_PCT 67
 #endif
 constexpr u32 max_nnz_of(u32 cap, u32 pct) { return pct == 67 ? cap * 2 / 3 : cap * pct / 100; }
-// log2 of the table a row with `nnz` entries gets (before the class clamps it to [group width, capacity])
+// log2 of the table a row with `nnz` entries gets (before the class clamps it to [group width, capacity]): the smallest
+// power of two, two slots at least, with
+//   pct == 67:  nnz + floor(nnz / 2) <= 2^bits  -- load <= 2/3 for an even nnz; an odd nnz may sit one entry above it
+//               (43 entries in 64 slots, 11 in 16, 3 in 4: load <= 3/4 at the worst), so the largest nnz that gets `cap`
+//               slots is max_nnz_of(cap, 67) + 1 where log2(cap) is even and max_nnz_of(cap, 67) where it is odd -- a
+//               table never fills either way, and every class limit (max_nnz_of of its capacity) gets its capacity;
+//   otherwise:  100 * nnz <= pct * 2^bits       -- exactly: max_nnz_of(cap, pct) is the largest nnz that gets `cap`.
+// (pinned for every nnz up to 8192 by tests/test_edges_host.py)
 __host__ __device__ inline u32 table_bits(u32 nnz, u32 pct)
 {
     const u32 want = pct == 67 ? nnz + (nnz >> 1) : (u32)((u64(nnz) * 100 + pct - 1) / pct);
@@ -157,9 +171,10 @@ struct ClassifyParams {
     u32 esc32, esc64;       // the wide register classes (32 / 64 lanes per row, 128 / 256 products)
     u32 esc_fused;          // replayed sequence with direct placement: the rows of the register classes are finished
                             //   in the symbolic phase (esc_rows.hpp) -- the numeric phase only accounts for them
-    u32 num_g8;             // rows of <= kNumG8MaxNnz entries: 8 lanes per row (else they join NUM_G16)
-    u32 sym_g8;             // rows of <= kSymG8MaxOps products: 8 lanes per row (else they join SYM_G16)
-    u32 sym_w128;           // rows of 52..102 products: 16 lanes per row (else they join SYM_W256)
+    u32 num_g8;             // rows of <= kNumEscMaxOps products from <= kNumEscMaxLen entries of A: 8 lanes per row (else
+    u32 sym_g8;             //   they join the next register class that takes them: NUM_G16 / SYM_G16, ...)
+    u32 sym_w128;           // rows of <= kSymW128MaxOps products that no register class takes: 16 lanes per row (else they
+                            //   join SYM_W256)
     u32 nf_min_ops;         // numeric-first (SYM_NF) for rows with range <= kNumD1Cols and at least this many
                             //   products; 0 = off
     u32 gh_per_window;      // SYM_GH instead of a multi-window SYM_BM2 when the row holds fewer products than this

@@ -603,8 +603,9 @@ __device__ __forceinline__ void num_hash_body(unsigned char* smem, const Product
         if (rec.nnz <= NLO || rec.nnz > NMAX) {  // the other launch's row (uniform for the group)
             continue;
         }
-        // table of this row: the smallest power of two >= 1.5 nnz (load <= 2/3), at least one slot
-        // per lane; the class limit guarantees it fits (nnz <= 2/3 CAP)
+        // table of this row: table_bits (device_common.hpp) -- the smallest power of two >= nnz + floor(nnz / 2) in the
+        // sub-wave / wave classes (load <= 2/3, an odd nnz at most one entry above it), >= nnz / 0.85 in the workgroup
+        // classes -- at least one slot per lane; the class limit guarantees it fits (nnz <= max_nnz_of(CAP))
         u32 bits = table_bits(rec.nnz, G::kIsBlock ? SPECK_LOAD_PCT : SPECK_LOAD_TINY_PCT);
         bits = min(max(bits, (u32)__builtin_ctz(G::SIZE)), (u32)__builtin_ctz(CAP));
         if constexpr (G::SIZE >= 64) bits = (u32)__builtin_amdgcn_readfirstlane((int)bits);
