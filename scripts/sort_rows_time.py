@@ -64,6 +64,7 @@ def main():
             w_col, w_val = p_col.clone(), p_val.clone()
             M = sa.dCSR.from_device(C.rows, C.cols, C.nnz, ro.data_ptr(), w_col.data_ptr(), w_val.data_ptr(),
                                     keep=(ro, w_col, w_val), host_row_offsets=C.row_offsets)
+            torch.cuda.synchronize()   # (the shuffle ran on torch's current stream: the timed stream does not wait for it)
             s = torch.cuda.Stream(device=dev)
             cfg.set_stream(s.cuda_stream)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -124,7 +125,9 @@ def main():
             rec = dict(kind=kind, scale=args.scale, rows=C.rows, nnz=C.nnz, rows_in_order=info.rows_in_order,
                        rows_reg=info.rows_sorted[0], rows_lds=info.rows_sorted[1], rows_global=info.rows_sorted[2],
                        keep_ms=med["keep"], sum_ms=med["sum"], transpose2_ms=med["transpose2"], early_exit_ms=med["early_exit"],
-                       keep_min_max=(min(ms["keep"]), max(ms["keep"])), transpose2_min_max=(min(ms["transpose2"]), max(ms["transpose2"])),
+                       keep_min_max=(min(ms["keep"]), max(ms["keep"])), sum_min_max=(min(ms["sum"]), max(ms["sum"])),
+                       early_exit_min_max=(min(ms["early_exit"]), max(ms["early_exit"])),
+                       transpose2_min_max=(min(ms["transpose2"]), max(ms["transpose2"])),
                        keep_hbm_frac=full / (med["keep"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
                        sum_hbm_frac=full / (med["sum"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
                        early_exit_hbm_frac=early / (med["early_exit"] * 1e-3) / 1e9 / HBM_PEAK_GBS,

@@ -331,7 +331,33 @@ struct __attribute__((aligned(32))) RowRec {
     u32 ops;         // intermediate products of the row
     u32 row;         // row of A / C
 };
+
+// Two lists in one region of `rows` elements: list k lives in region k / 2, the even one grows up from the region's first
+// element, the odd one down from its last.  The lists of a region hold different rows, so they cannot meet -- and a
+// producer places an element knowing only how many of its list come before it.  (The class records of the multiply,
+// launch.hpp; the row lists of the row sort and the masked product.)
+template <typename T>
+__host__ __device__ __forceinline__ T* two_sided_at(T* lists, u32 rows, u32 k, u32 i)
+{
+    T* region = lists + size_t(k >> 1) * rows;
+    return (k & 1u) ? region + (rows - 1u - i) : region + i;
+}
+
 #ifdef __HIPCC__
+// The first i in [0, n) with end[i] > p, or n: `end` ascends.  With the ends of consecutive rows (row_offsets + 1) that
+// is the row entry p belongs to; with an inclusive scan of lengths, the item product p belongs to.  P is the width the
+// caller's positions have (u64 in the classifying passes, u32 in the product walk): the compare is never widened.
+template <typename P>
+__device__ __forceinline__ u32 first_end_beyond(const u32* end, u32 n, P p)
+{
+    u32 lo = 0, hi = n;
+    while (lo < hi) {
+        const u32 mid = (lo + hi) >> 1;
+        if (end[mid] <= p) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
 // ---- wave64 primitives ---------------------------------------------------------
 __device__ __forceinline__ u32 lane_id() { return __lane_id(); }
 

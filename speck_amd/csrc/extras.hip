@@ -15,20 +15,9 @@
 #include <cmath>
 #include <cstdio>
 
-#include "../../include/speck_c_api.h"
-#include "device_common.hpp"
+#include "host_common.hpp"
 
 using namespace speck;
-
-#define HIP_TRY(expr)                                                                     \
-    do {                                                                                  \
-        hipError_t _e = (expr);                                                           \
-        if (_e != hipSuccess) {                                                           \
-            std::fprintf(stderr, "speck_amd: HIP error %s at %s:%d\n", hipGetErrorString(_e), \
-                         __FILE__, __LINE__);                                             \
-            return (_e == hipErrorOutOfMemory) ? SPECK_ERR_OOM : SPECK_ERR_HIP;           \
-        }                                                                                 \
-    } while (0)
 
 namespace {
 

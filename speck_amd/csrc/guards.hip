@@ -6,6 +6,8 @@
 #include <mutex>
 #include <unordered_map>
 
+#include "../../include/speck_c_api.h"
+
 namespace speck {
 namespace {
 
@@ -136,6 +138,32 @@ int guard_check(const std::vector<GuardZone>& zones, hipStream_t s, int* first_b
     (void)hipFree(d_z);
     (void)hipFree(d_bad);
     return rc;
+}
+
+int guard_check_buffers(const void* const* buffers, const char* const* names, int n, hipStream_t s, const char* whose, int rc,
+                        std::vector<GuardZone> z)
+{
+    if (!guard_bytes()) return rc;
+    const size_t inner = z.size();
+    std::vector<int> owner;  // of the zones behind the inner ones
+    for (int i = 0; i < n; ++i) {
+        const size_t before = z.size();
+        if (buffers[i]) guard_zones_of(buffers[i], &z);
+        owner.resize(owner.size() + (z.size() - before), i);
+    }
+    int bad = -1;
+    size_t at = 0;
+    const int touched = guard_check(z, s, &bad, &at);
+    if (touched == 0) return rc;
+    if (touched > 0) {
+        const char* what = (size_t)bad < inner ? "between two regions of the arena / a pool" : names[owner[bad - inner]];
+        if (whose)
+            std::fprintf(stderr, "speck_amd: guard_bytes: %d canary zone(s) touched%s; first: %s, byte %zu\n", touched, whose, what, at);
+        else
+            std::fprintf(stderr, "speck_amd: guard_bytes: %d canary zone(s) touched; first: zone %d (%s, %s the buffer), byte %zu\n",
+                         touched, bad, what, (size_t)bad >= inner && ((bad - inner) & 1u) == 0 ? "in front of" : "behind", at);
+    }
+    return rc == SPECK_OK ? SPECK_ERR_HIP : rc;
 }
 
 }  // namespace speck

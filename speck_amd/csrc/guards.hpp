@@ -31,5 +31,12 @@ void guard_zones_of(const void* user_ptr, std::vector<GuardZone>* out);
 // fill zones with the pattern (on `s`) / count the zones that hold anything else (blocking); first_bad: its index
 hipError_t guard_fill(const std::vector<GuardZone>& zones, hipStream_t s);
 int guard_check(const std::vector<GuardZone>& zones, hipStream_t s, int* first_bad, size_t* first_bad_offset);
+// The check at the end of a call, whole (nothing when the option is off): the zones of the `n` buffers (null ones are
+// skipped) and the caller's `inner` zones -- those it carved inside a buffer -- are checked behind the work on `s`; the
+// first touched one goes to stderr under the buffer's name.  `whose` names the operation (" by the row sort"; nullptr:
+// the multiply, which says more about the place).  Returns rc, or SPECK_ERR_HIP where rc was SPECK_OK and a zone was
+// touched or the check itself failed.
+int guard_check_buffers(const void* const* buffers, const char* const* names, int n, hipStream_t s, const char* whose, int rc,
+                        std::vector<GuardZone> inner = {});
 
 }  // namespace speck

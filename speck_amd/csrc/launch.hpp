@@ -23,14 +23,10 @@ u32 scan_tiles(u32 m);
 // phase (seven regions; round 5 sized them for kMaxClasses = 16: an eighth region nobody addressed).
 constexpr u32 kListRegions = (((u32)SYM_CLASSES > (u32)NUM_CLASSES ? (u32)SYM_CLASSES : (u32)NUM_CLASSES) + 1u) / 2u;
 __host__ __device__ inline size_t class_list_records(u32 m) { return size_t(kListRegions) * (m ? m : 1u); }
-__host__ __device__ __forceinline__ RowRec* class_rec_at(RowRec* lists, u32 m, u32 cls, u32 i)
+template <typename Rec>  // RowRec or const RowRec
+__host__ __device__ __forceinline__ Rec* class_rec_at(Rec* lists, u32 m, u32 cls, u32 i)
 {
-    RowRec* region = lists + size_t(cls >> 1) * m;
-    return (cls & 1u) ? region + (m - 1u - i) : region + i;
-}
-__host__ __device__ __forceinline__ const RowRec* class_rec_at(const RowRec* lists, u32 m, u32 cls, u32 i)
-{
-    return class_rec_at(const_cast<RowRec*>(lists), m, cls, i);
+    return two_sided_at(lists, m, cls, i);
 }
 
 // analysis + symbolic binning (ONE kernel, stages.hip).  sym_cls == nullptr: the per-row quantities and the totals only.

@@ -14,45 +14,28 @@
 //                            an open-addressed table of 16-bit positions over the row's columns, built once, probed read-only.
 //   masked_global_kernel     a workgroup per longer row: binary search in the mask row where it lies, global atomic adds.
 //   (all three walk a row's products flattened, a batch of entries of A at a time: "the product walk" below)
-//   finish                   STRUCTURE: hits per row -> scan -> the new row offsets; a scan over the hit bytes -> one
-//                            streaming compaction.  FULL_PATTERN: the accumulators
+//   finish                   STRUCTURE: hits per row -> the shared scan (scan.hpp) -> the new row offsets; the same scan
+//                            over the hit bytes -> one streaming compaction.  FULL_PATTERN: the accumulators
 //                            are C's values (fp64: accumulated in place), offsets rebased, column ids copied.
 // A hit is marked in bit 31 of the column's LDS copy (columns are < 2^27).  As in the multiply a product is rounded to T,
 // the sum is kept in double and rounded once.  Every kernel but the classifying pass starts after the host has read the
 // verdict on all three inputs; nothing of C is written before that.
+// The host side stands on host_common.hpp (scratch buffers, stream, error macro) and guards.hpp (the check after the call).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdio>
 #include <type_traits>
-#include <vector>
 
-#include "../../include/speck_c_api.h"
-#include "device_common.hpp"
-#include "guards.hpp"
 #include "launch.hpp"
 #include "masked.hpp"
-#include "sort_rows.hpp"
+#include "scan.hpp"
 
 using namespace speck;
-
-#define HIP_TRY(expr)                                                                     \
-    do {                                                                                  \
-        hipError_t _e = (expr);                                                           \
-        if (_e != hipSuccess) {                                                           \
-            std::fprintf(stderr, "speck_amd: HIP error %s at %s:%d\n", hipGetErrorString(_e), \
-                         __FILE__, __LINE__);                                             \
-            return (_e == hipErrorOutOfMemory) ? SPECK_ERR_OOM : SPECK_ERR_HIP;           \
-        }                                                                                 \
-    } while (0)
 
 namespace speck {
 void MaskedScratch::release()
 {
-    if (fixed) (void)guarded_free(fixed);
-    if (var) (void)guarded_free(var);
-    fixed = var = nullptr;
-    fixed_bytes = var_bytes = 0;
+    fixed.release(), var.release();
     for (int i = 0; i < 3; ++i) {
         if (side[i]) (void)hipStreamDestroy(side[i]);
         if (join[i]) (void)hipEventDestroy(join[i]);
@@ -83,13 +66,7 @@ struct MaskedStatus {
     unsigned long long products, hits, nnz_out;
 };
 
-// list k lives in region k / 2 (`rows` words each), the even one grows up from the region's first word, the odd one down
-// from its last (the lists hold different rows: they cannot meet)
-__host__ __device__ __forceinline__ u32* list_at(u32* lists, u32 rows, u32 k, u32 i)
-{
-    u32* region = lists + size_t(k >> 1) * rows;
-    return (k & 1u) ? region + (rows - 1u - i) : region + i;
-}
+// (the seven lists share four regions of `rows` words: two_sided_at, device_common.hpp)
 
 template <typename T>
 struct MaskedArgs {
@@ -107,17 +84,6 @@ struct MaskedArgs {
 };
 
 // ------------------------------------------------------------------------------------------------ check + classify
-
-// the row of entry i of a tile: the first one whose end lies beyond i
-__device__ __forceinline__ u32 row_of(const u32* s_ro, u32 nr, u64 i)
-{
-    u32 a = 0, b = nr;
-    while (a < b) {
-        const u32 mid = (a + b) >> 1;
-        if (s_ro[mid + 1] <= i) a = mid + 1; else b = mid;
-    }
-    return a;
-}
 
 // TILE rows and TILE threads per workgroup: 1024 where rows are short, 256 where a row holds 16 entries or more on
 // average (a tile should hold enough entries to pay for its barriers, and there should be enough tiles for the machine:
@@ -169,7 +135,7 @@ __global__ __launch_bounds__(kTileRows) void masked_classify_kernel(const u32* _
         for (u64 i = lo + t; i < hi; i += kTileRows) {
             const u32 c = m_col[i];
             unsorted |= c >= b_cols;
-            if (i > lo && m_col[i - 1] >= c) unsorted |= i > s_mro[row_of(s_mro, nr, i)];
+            if (i > lo && m_col[i - 1] >= c) unsorted |= i > s_mro[first_end_beyond(s_mro + 1, nr, i)];  // (not the first entry of its row)
         }
     }
     // the tile's entries of A: below rows(B); the products they stand for, where their row has a mask row
@@ -186,7 +152,7 @@ __global__ __launch_bounds__(kTileRows) void masked_classify_kernel(const u32* _
             }
             const u32 b0 = b_ro[k], b1 = b_ro[k + 1];
             const u64 len = b1 > b0 ? min(u64(b1 - b0), b_nnz) : 0ull;  // (B's own check speaks later: clamped)
-            const u32 r = row_of(s_aro, nr, i);
+            const u32 r = first_end_beyond(s_aro + 1, nr, i);  // the row of entry i
             if (s_mro[r + 1] > s_mro[r]) {
                 products += len;
                 if (s_ops[r] < (1u << 20)) atomicAdd(&s_ops[r], (u32)min(len, u64(1u << 20)));
@@ -237,7 +203,7 @@ __global__ __launch_bounds__(kTileRows) void masked_classify_kernel(const u32* _
     if (t == MASK_LISTS && s_cnt[t]) atomicAdd(&st->idle, s_cnt[t]);
     if (t == MASK_LISTS + 1 && s_products) atomicAdd(&st->products, s_products);
     __syncthreads();
-    if (cls >= 0 && cls < MASK_LISTS) *list_at(lists, rows, (u32)cls, s_first[cls] + rank) = r0 + t;
+    if (cls >= 0 && cls < MASK_LISTS) *two_sided_at(lists, rows, (u32)cls, s_first[cls] + rank) = r0 + t;
 }
 
 // ------------------------------------------------------------------------------------------------ the product walk
@@ -248,15 +214,7 @@ __global__ __launch_bounds__(kTileRows) void masked_classify_kernel(const u32* _
 // entry of A, and no lane idles on a short row of B.  (First form: teams of eight lanes per entry of A, one entry after
 // the other -- a row of 256 entries of A cost 32 such chains, 120 us for a handful of rows of the scircuit stand-in.)
 // `end[i]`: products of the batch up to and including entry i;  `off[i]`: first entry of its B row - products before it.
-__device__ __forceinline__ u32 batch_entry(const u32* end, u32 n, u32 p)
-{
-    u32 lo = 0, hi = n;  // the first entry whose end lies beyond p
-    while (lo < hi) {
-        const u32 mid = (lo + hi) >> 1;
-        if (end[mid] <= p) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
+// (the entry of product p: first_end_beyond(end, nb, p), device_common.hpp)
 
 // one counter per workgroup reaches the status block (atomics of every wave on one word serialise: see the classifying pass)
 __device__ __forceinline__ void add_hits(u64 hits, unsigned long long* s_hits, MaskedStatus* st)
@@ -293,7 +251,7 @@ __global__ __launch_bounds__(256) void masked_group_kernel(const MaskedArgs<T> g
     const u32 n_list = g.st->cnt[K];
     u64 hits = 0;
     for (u32 e = blockIdx.x * NG + gid; e < n_list; e += gridDim.x * NG) {
-        const u32 row = *list_at(g.lists, g.rows, K, e);
+        const u32 row = *two_sided_at(g.lists, g.rows, K, e);
         const u32 m0 = g.m_ro[row], n = min(g.m_ro[row + 1] - m0, NP);
         const u32 a0 = g.a_ro[row], a1 = g.a_ro[row + 1];
 #pragma unroll
@@ -365,7 +323,7 @@ __global__ __launch_bounds__(256) void masked_group_kernel(const MaskedArgs<T> g
 #pragma unroll
                     for (u32 u = 0; u < 4; ++u) {
                         const u32 q = p + u * L;
-                        i[u] = q < total ? batch_entry(end, nb, q) : 0u;
+                        i[u] = q < total ? first_end_beyond(end, nb, q) : 0u;
                         j[u] = off[i[u]] + q;
                         c[u] = q < total ? g.b_col[j[u]] : kNoColumn;
                     }
@@ -420,7 +378,7 @@ __global__ __launch_bounds__(THREADS) void masked_lds_kernel(const MaskedArgs<T>
     const u32 n_list = g.st->cnt[list];
     u64 hits = 0;
     for (u32 e = blockIdx.x; e < n_list; e += gridDim.x) {
-        const u32 row = *list_at(g.lists, g.rows, list, e);
+        const u32 row = *two_sided_at(g.lists, g.rows, list, e);
         const u32 m0 = g.m_ro[row], n = min(g.m_ro[row + 1] - m0, cap);
         const u32 a0 = g.a_ro[row], a1 = g.a_ro[row + 1];
         u32 bits = 4;
@@ -481,7 +439,7 @@ __global__ __launch_bounds__(THREADS) void masked_lds_kernel(const MaskedArgs<T>
 #pragma unroll
                 for (u32 u = 0; u < 4; ++u) {
                     const u32 q = p + u * THREADS;
-                    i[u] = q < total ? batch_entry(end, nb, q) : 0u;
+                    i[u] = q < total ? first_end_beyond(end, nb, q) : 0u;
                     j[u] = off[i[u]] + q;
                     c[u] = q < total ? g.b_col[j[u]] : kNoColumn;
                 }
@@ -524,7 +482,7 @@ __global__ __launch_bounds__(1024) void masked_global_kernel(const MaskedArgs<T>
     const u32 n_list = g.st->cnt[LIST_GLOBAL];
     u64 hits = 0;
     for (u32 e = blockIdx.x; e < n_list; e += gridDim.x) {
-        const u32 row = *list_at(g.lists, g.rows, LIST_GLOBAL, e);
+        const u32 row = *two_sided_at(g.lists, g.rows, LIST_GLOBAL, e);
         const u32 m0 = g.m_ro[row], n = g.m_ro[row + 1] - m0;
         const u32 a0 = g.a_ro[row], a1 = g.a_ro[row + 1];
         const u32* mc = g.m_col + m0;
@@ -561,7 +519,7 @@ __global__ __launch_bounds__(1024) void masked_global_kernel(const MaskedArgs<T>
 #pragma unroll
                 for (u32 u = 0; u < 4; ++u) {
                     const u32 q = p + u * THREADS;
-                    i[u] = q < total ? batch_entry(s_end, nb, q) : 0u;
+                    i[u] = q < total ? first_end_beyond(s_end, nb, q) : 0u;
                     j[u] = s_off[i[u]] + q;
                     c[u] = q < total ? g.b_col[j[u]] : kNoColumn;
                 }
@@ -584,83 +542,43 @@ __global__ __launch_bounds__(1024) void masked_global_kernel(const MaskedArgs<T>
 }
 
 // ------------------------------------------------------------------------------------------------ finish
-// STRUCTURE: hits per row -> exclusive scan (1024 rows per workgroup, the workgroup sums scanned by one workgroup) -> the
-// hit entries of every row moved to their place, L lanes per row.
-__global__ __launch_bounds__(1024) void masked_block_sums_kernel(const u32* __restrict__ row_cnt, u32 rows, u32* __restrict__ block_sums)
-{
-    SPECK_POISON();
-    __shared__ u32 s_scan[1024 / 64 + 1];
-    const u32 r = blockIdx.x * 1024u + threadIdx.x;
-    u32 total;
-    (void)block_exclusive_scan<1024>(r < rows ? row_cnt[r] : 0u, s_scan, &total);
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(1024) void masked_scan_sums_kernel(u32* __restrict__ block_sums, u32 n)
-{
-    SPECK_POISON();
-    __shared__ u32 s_scan[1024 / 64 + 1];
-    u32 carry = 0;
-    for (u32 i0 = 0; i0 < n; i0 += 1024) {
-        const u32 i = i0 + threadIdx.x;
-        const u32 v = i < n ? block_sums[i] : 0u;
-        u32 total;
-        const u32 ex = block_exclusive_scan<1024>(v, s_scan, &total);
-        if (i < n) block_sums[i] = carry + ex;
-        carry += total;
-    }
-}
-
-__global__ __launch_bounds__(1024) void masked_offsets_kernel(const u32* __restrict__ row_cnt, u32 rows, const u32* __restrict__ block_sums,
-                                                              u32* __restrict__ new_ro, MaskedStatus* __restrict__ st)
-{
-    SPECK_POISON();
-    __shared__ u32 s_scan[1024 / 64 + 1];
-    const u32 r = blockIdx.x * 1024u + threadIdx.x;
-    const u32 len = r < rows ? row_cnt[r] : 0u;
-    u32 total;
-    const u32 ex = block_exclusive_scan<1024>(len, s_scan, &total);
-    const u32 off = block_sums[blockIdx.x] + ex;
-    if (r < rows) new_ro[r] = off;
-    if (r + 1 == rows) {
-        new_ro[rows] = off + len;
-        st->nnz_out = off + len;
-    }
-}
+// STRUCTURE: hits per row -> the shared exclusive scan (scan.hpp): the new row offsets, nnz(C) into the status block.
+struct MaskedRowCount {
+    const u32* row_cnt;
+    __device__ u32 operator()(u32 r) const { return row_cnt[r]; }
+};
 
 // The compaction needs no rows: C's entries are M's entries with a hit, in M's order, so an entry's place is the number of
-// hits in front of it -- a scan over the hit bytes, 4096 entries per workgroup (a word of four bytes per thread), the
-// workgroup sums scanned by masked_scan_sums_kernel.  (First form: eight lanes per row looking up the row's new offset --
-// 0.37 ms for the 1 M short rows of the webbase stand-in.)
+// hits in front of it -- the shared scan over the hit bytes, a word of four per item (4096 entries per workgroup), as far
+// as the scanned workgroup sums; the kernel below places the four entries of a thread itself.  (First form: eight lanes
+// per row looking up the row's new offset -- 0.37 ms for the 1 M short rows of the webbase stand-in.)
 constexpr u32 kCompactTile = 4096;
 
-__device__ __forceinline__ u32 hit_word(const u32* __restrict__ hit32, u64 e0, u64 n)
-{
-    if (e0 >= n) return 0u;
-    u32 w = hit32[e0 >> 2] & 0x01010101u;
-    if (e0 + 4 > n) w &= 0xFFFFFFFFu >> (8u * (u32)(e0 + 4 - n));  // (the bytes behind the last entry were never written)
-    return w;
-}
-
-__global__ __launch_bounds__(1024) void masked_tile_sums_kernel(const u32* __restrict__ hit32, u64 n, u32* __restrict__ tile_sums)
-{
-    SPECK_POISON();
-    __shared__ u32 s_scan[1024 / 64 + 1];
-    const u64 e0 = (u64(blockIdx.x) * 1024 + threadIdx.x) * 4;
-    u32 total;
-    (void)block_exclusive_scan<1024>((u32)__popc(hit_word(hit32, e0, n)), s_scan, &total);
-    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
-}
+struct MaskedHitWord {
+    const u32* hit32;
+    u64 n;  // entries of M
+    // the hit bytes of entries 4 i .. 4 i + 3, a bit each
+    __device__ __forceinline__ u32 word(u32 i) const
+    {
+        const u64 e0 = u64(i) * 4;
+        if (e0 >= n) return 0u;
+        u32 w = hit32[i] & 0x01010101u;
+        if (e0 + 4 > n) w &= 0xFFFFFFFFu >> (8u * (u32)(e0 + 4 - n));  // (the bytes behind the last entry were never written)
+        return w;
+    }
+    __device__ __forceinline__ u32 operator()(u32 i) const { return (u32)__popc(word(i)); }
+};
 
 template <typename T>
-__global__ __launch_bounds__(1024) void masked_compact_kernel(const u32* __restrict__ hit32, u64 n, const u32* __restrict__ tile_sums,
+__global__ __launch_bounds__(1024) void masked_compact_kernel(const MaskedHitWord f, const u32* __restrict__ tile_sums,
                                                               const u32* __restrict__ m_col, const double* __restrict__ acc,
                                                               u32* __restrict__ c_col, T* __restrict__ c_val)
 {
     SPECK_POISON();
     __shared__ u32 s_scan[1024 / 64 + 1];
-    const u64 e0 = (u64(blockIdx.x) * 1024 + threadIdx.x) * 4;
-    const u32 w = hit_word(hit32, e0, n);
+    const u32 i = blockIdx.x * 1024u + threadIdx.x;
+    const u64 e0 = u64(i) * 4;
+    const u32 w = f.word(i);
     u32 total;
     u32 to = tile_sums[blockIdx.x] + block_exclusive_scan<1024>((u32)__popc(w), s_scan, &total);
 #pragma unroll
@@ -688,20 +606,6 @@ __global__ __launch_bounds__(256) void masked_round_kernel(const double* __restr
 }
 
 // ------------------------------------------------------------------------------------------------ host
-int ensure(void** p, size_t* have, size_t want)
-{
-    if (*have >= want && *p) return SPECK_OK;
-    if (*p) (void)guarded_free(*p);
-    *p = nullptr, *have = 0;
-    HIP_TRY(guarded_malloc(p, want));
-    *have = want;
-    return SPECK_OK;
-}
-
-inline size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
-
-u32 grid_of(u64 work, u32 cap) { return (u32)std::max<u64>(1, std::min<u64>(work, cap)); }
-
 // dynamic LDS of the LDS class: accumulators | columns | table | batch
 constexpr u32 lds_bytes(u32 cap, u32 threads) { return cap * 16u + threads * 8u; }
 
@@ -774,9 +678,9 @@ int masked_run(MaskedScratch* sc, hipStream_t s, const speck_dcsr* A, const spec
     // status | lists (four regions of `rows` words) | hits per row | new row offsets | workgroup sums of the scan
     const u32 nblk = (rows + 1023) / 1024;
     const size_t list_bytes = up256(size_t(4) * rows * 4), row_bytes = up256((size_t(rows) + 1) * 4), sum_bytes = up256(size_t(nblk) * 4);
-    int rc = ensure(&sc->fixed, &sc->fixed_bytes, 256 + list_bytes + 2 * row_bytes + sum_bytes);
+    int rc = sc->fixed.ensure(256 + list_bytes + 2 * row_bytes + sum_bytes);
     if (rc != SPECK_OK) return rc;
-    unsigned char* fb = static_cast<unsigned char*>(sc->fixed);
+    unsigned char* fb = static_cast<unsigned char*>(sc->fixed.p);
     MaskedStatus* st = reinterpret_cast<MaskedStatus*>(fb);
     u32* lists = reinterpret_cast<u32*>(fb + 256);
     u32* row_cnt = reinterpret_cast<u32*>(fb + 256 + list_bytes);
@@ -789,10 +693,10 @@ int masked_run(MaskedScratch* sc, hipStream_t s, const speck_dcsr* A, const spec
     const size_t acc_bytes = acc_in_c ? 0 : up256(nnz_m * 8), hit_bytes = full ? 0 : up256(nnz_m);
     const size_t tile_bytes = full ? 0 : up256(size_t(ntiles) * 4);
     if (acc_bytes + hit_bytes + tile_bytes) {
-        rc = ensure(&sc->var, &sc->var_bytes, acc_bytes + hit_bytes + tile_bytes);
+        rc = sc->var.ensure(acc_bytes + hit_bytes + tile_bytes);
         if (rc != SPECK_OK) return rc;
     }
-    unsigned char* vb = static_cast<unsigned char*>(sc->var);
+    unsigned char* vb = static_cast<unsigned char*>(sc->var.p);
 
     // ---- the verdict on A, M (this file) and B (the multiply's check), read before anything else starts
     HIP_TRY(hipMemsetAsync(st, 0, sizeof(MaskedStatus), s));
@@ -875,11 +779,7 @@ int masked_run(MaskedScratch* sc, hipStream_t s, const speck_dcsr* A, const spec
 
     // ---- finish
     u64 nnz_out = nnz_m;
-    if (!full) {
-        SPECK_LAUNCH(masked_block_sums_kernel, dim3(nblk), dim3(1024), 0, s, row_cnt, rows, block_sums);
-        SPECK_LAUNCH(masked_scan_sums_kernel, dim3(1), dim3(1024), 0, s, block_sums, nblk);
-        SPECK_LAUNCH(masked_offsets_kernel, dim3(nblk), dim3(1024), 0, s, row_cnt, rows, block_sums, new_ro, st);
-    }
+    if (!full) launch_exclusive_scan(s, MaskedRowCount{row_cnt}, rows, block_sums, new_ro, &st->nnz_out);
     HIP_TRY(hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     if (take_launch_error()) return SPECK_ERR_HIP;
@@ -888,11 +788,10 @@ int masked_run(MaskedScratch* sc, hipStream_t s, const speck_dcsr* A, const spec
         rc = prepare_c(C, rows, nnz_out, sizeof(T), out);
         if (rc != SPECK_OK) return rc;
         if (nnz_out) {
-            const u32* hit32 = reinterpret_cast<const u32*>(hit);
+            const MaskedHitWord words{reinterpret_cast<const u32*>(hit), nnz_m};
             u32* tile_sums = reinterpret_cast<u32*>(vb + acc_bytes + hit_bytes);
-            SPECK_LAUNCH(masked_tile_sums_kernel, dim3(ntiles), dim3(1024), 0, s, hit32, nnz_m, tile_sums);
-            SPECK_LAUNCH(masked_scan_sums_kernel, dim3(1), dim3(1024), 0, s, tile_sums, ntiles);
-            SPECK_LAUNCH(masked_compact_kernel<T>, dim3(ntiles), dim3(1024), 0, s, hit32, nnz_m, tile_sums, M->col_ids + h.base_m, acc,
+            launch_exclusive_scan(s, words, (u32)((nnz_m + 3) / 4), tile_sums, nullptr, nullptr);
+            SPECK_LAUNCH(masked_compact_kernel<T>, dim3(ntiles), dim3(1024), 0, s, words, tile_sums, M->col_ids + h.base_m, acc,
                          out->col, static_cast<T*>(out->val));
         }
         HIP_TRY(hipMemcpyAsync(out->ro, new_ro, (size_t(rows) + 1) * 4, hipMemcpyDeviceToDevice, s));
@@ -923,24 +822,9 @@ int masked_run(MaskedScratch* sc, hipStream_t s, const speck_dcsr* A, const spec
 // debug option guard_bytes: the canary zones of the temporaries and of C's buffers after the call
 int check_masked_guards(const MaskedScratch* sc, hipStream_t s, const speck_dcsr* C, int rc)
 {
-    if (!guard_bytes()) return rc;
-    std::vector<GuardZone> z;
-    const void* whole[] = {sc->fixed, sc->var, C->data, C->col_ids, C->row_offsets};
+    const void* whole[] = {sc->fixed.p, sc->var.p, C->data, C->col_ids, C->row_offsets};
     static const char* names[] = {"masked lists", "masked accumulators", "C.data", "C.col_ids", "C.row_offsets"};
-    std::vector<int> owner;
-    for (int i = 0; i < 5; ++i) {
-        const size_t before = z.size();
-        if (whole[i]) guard_zones_of(whole[i], &z);
-        for (size_t k = before; k < z.size(); ++k) owner.push_back(i);
-    }
-    int bad = -1;
-    size_t at = 0;
-    const int n = guard_check(z, s, &bad, &at);
-    if (n == 0) return rc;
-    if (n < 0) return rc == SPECK_OK ? SPECK_ERR_HIP : rc;
-    std::fprintf(stderr, "speck_amd: guard_bytes: %d canary zone(s) touched by the masked product; first: %s, byte %zu\n", n,
-                 names[owner[bad]], at);
-    return rc == SPECK_OK ? SPECK_ERR_HIP : rc;
+    return guard_check_buffers(whole, names, 5, s, " by the masked product", rc);
 }
 
 bool csr_args_ok(const speck_dcsr* X, bool needs_values)
@@ -972,16 +856,10 @@ int masked_impl(speck_config* cfg, const speck_dcsr* A, const speck_dcsr* B, con
     if (!csr_args_ok(A, true) || !csr_args_ok(B, true) || !csr_args_ok(M, false)) return SPECK_ERR_INVALID;
     if (shares_buffer(C, A) || shares_buffer(C, B) || shares_buffer(C, M)) return SPECK_ERR_INVALID;
     if (info) *info = speck_masked_info{};
-    if (!cfg) {  // (a config exists only where a device does)
-        int n = 0;
-        if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-            (void)hipGetLastError();
-            return SPECK_ERR_NO_DEVICE;
-        }
-    }
+    if (!cfg && !device_present()) return SPECK_ERR_NO_DEVICE;
     MaskedScratch own;
     MaskedScratch* sc = cfg ? masked_scratch(cfg) : &own;
-    const hipStream_t s = cfg ? sort_stream(cfg) : nullptr;
+    const hipStream_t s = cfg ? call_stream(cfg) : nullptr;
     (void)take_launch_error();
     COut out;
     int rc = masked_run<T>(sc, s, A, B, M, C, flags == SPECK_MASK_FULL_PATTERN, info, &out);

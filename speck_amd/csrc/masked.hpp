@@ -1,12 +1,6 @@
 // masked.hpp -- what speck_multiply_masked_* (masked.hip) needs from a config (pipeline.hip owns the structure).
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstddef>
-
-#include "device_common.hpp"
-
-struct speck_config;
+#include "host_common.hpp"
 
 namespace speck {
 
@@ -16,10 +10,7 @@ namespace speck {
 // the partial sums of their scan), `var` from nnz(M) (one double accumulator and one hit byte per mask entry).  Both sizes
 // are known before the first kernel.  Released with the config.
 struct MaskedScratch {
-    void* fixed = nullptr;
-    size_t fixed_bytes = 0;
-    void* var = nullptr;
-    size_t var_bytes = 0;
+    DeviceBuffer fixed, var;
     // the class kernels work on disjoint rows: they run side by side, on three streams of the call's own between a fork
     // and a join on the config's stream (created with the first call that has two classes to run)
     hipStream_t side[3] = {nullptr, nullptr, nullptr};

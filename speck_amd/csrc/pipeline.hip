@@ -25,25 +25,14 @@
 #include <vector>
 
 #include "../../include/speck_c_api.h"
-#include "device_common.hpp"
 #include "chain3.hpp"
-#include "guards.hpp"
+#include "host_common.hpp"
 #include "launch.hpp"
 #include "row_groups.hpp"
 #include "masked.hpp"
 #include "sort_rows.hpp"
 
 using namespace speck;
-
-#define HIP_TRY(expr)                                                                       \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess) {                                                             \
-            std::fprintf(stderr, "speck_amd: HIP error %s at %s:%d (%s)\n",                 \
-                         hipGetErrorString(_e), __FILE__, __LINE__, #expr);                 \
-            return (_e == hipErrorOutOfMemory) ? SPECK_ERR_OOM : SPECK_ERR_HIP;             \
-        }                                                                                   \
-    } while (0)
 
 // the launches enqueued since the last check went out (launch.hpp, SPECK_LAUNCH: a failed launch is latched where it
 // happens -- the runtime's own "last error" is overwritten by the next successful call)
@@ -1924,7 +1913,7 @@ int multiply_impl(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, spe
 
 namespace speck {
 SortScratch* sort_scratch(speck_config* c) { return &c->sort; }
-hipStream_t sort_stream(speck_config* c) { return main_stream(c); }
+hipStream_t call_stream(speck_config* c) { return main_stream(c); }
 MaskedScratch* masked_scratch(speck_config* c) { return &c->masked; }
 }  // namespace speck
 
@@ -2189,29 +2178,14 @@ int speck_last_stats(const speck_config* c, speck_stats* out)
 static int check_guards(speck_config* c, const speck_dcsr* C, int rc)
 {
     if (!guard_bytes() || !c) return rc;
-    std::vector<GuardZone> z = c->arena_zones;
-    z.insert(z.end(), c->gpool_zones.begin(), c->gpool_zones.end());
-    z.insert(z.end(), c->nfpool_zones.begin(), c->nfpool_zones.end());
-    const size_t inner = z.size();
+    std::vector<GuardZone> inner = c->arena_zones;
+    inner.insert(inner.end(), c->gpool_zones.begin(), c->gpool_zones.end());
+    inner.insert(inner.end(), c->nfpool_zones.begin(), c->nfpool_zones.end());
     const void* whole[] = {c->arena, c->snap, c->pred.off, c->gpred.off, c->nfpool, c->gpool,
                            C ? C->data : nullptr, C ? C->col_ids : nullptr, C ? C->row_offsets : nullptr};
     static const char* names[] = {"arena", "input snapshot", "row-offset copy", "row-offset copy (sequence)", "scratch pool",
                                   "spill pool", "C.data", "C.col_ids", "C.row_offsets"};
-    std::vector<int> owner;
-    for (int i = 0; i < 9; ++i) {
-        const size_t before = z.size();
-        if (whole[i]) guard_zones_of(whole[i], &z);
-        for (size_t k = before; k < z.size(); ++k) owner.push_back(i);
-    }
-    int bad = -1;
-    size_t at = 0;
-    const int n = guard_check(z, main_stream(c), &bad, &at);
-    if (n == 0) return rc;
-    if (n < 0) return rc == SPECK_OK ? SPECK_ERR_HIP : rc;
-    const char* what = (size_t)bad < inner ? "between two regions of the arena / a pool" : names[owner[bad - inner]];
-    std::fprintf(stderr, "speck_amd: guard_bytes: %d canary zone(s) touched; first: zone %d (%s, %s the buffer), byte %zu\n", n, bad,
-                 what, (size_t)bad >= inner && ((bad - inner) & 1u) == 0 ? "in front of" : "behind", at);
-    return rc == SPECK_OK ? SPECK_ERR_HIP : rc;
+    return guard_check_buffers(whole, names, 9, main_stream(c), nullptr, rc, std::move(inner));
 }
 
 int speck_multiply_f64(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, speck_dcsr* C,

@@ -14,44 +14,21 @@
 //                          column << 32 | position; the values are gathered into registers, a barrier, then stored.
 //   sort_global_kernel     one workgroup per longer row: stable LSD radix sort (8-bit digits, ranks from ballots as in the
 //                          transpose's radix_scatter_kernel, tiles taken in order) between the row and a temporary.
-//   compaction             (SUM_DUPLICATES, when a row shrank) row lengths minus duplicates -> scan -> the runs summed
-//                          in double while the rows move to a temporary -> copied back.
+//   compaction             (SUM_DUPLICATES, when a row shrank) row lengths minus duplicates -> the shared scan
+//                          (scan.hpp) -> the runs summed in double while the rows move to a temporary -> copied back.
+// The host side stands on host_common.hpp (scratch buffers, stream, error macro) and guards.hpp (the check after the call).
 // Every kernel that writes M starts after the host has read the verdict of the classifying pass.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdio>
-#include <vector>
 
-#include "../../include/speck_c_api.h"
-#include "device_common.hpp"
 #include "esc.hpp"
 #include "esc_wide.hpp"
-#include "guards.hpp"
 #include "launch.hpp"
+#include "scan.hpp"
 #include "sort_rows.hpp"
 
 using namespace speck;
-
-#define HIP_TRY(expr)                                                                     \
-    do {                                                                                  \
-        hipError_t _e = (expr);                                                           \
-        if (_e != hipSuccess) {                                                           \
-            std::fprintf(stderr, "speck_amd: HIP error %s at %s:%d\n", hipGetErrorString(_e), \
-                         __FILE__, __LINE__);                                             \
-            return (_e == hipErrorOutOfMemory) ? SPECK_ERR_OOM : SPECK_ERR_HIP;           \
-        }                                                                                 \
-    } while (0)
-
-namespace speck {
-void SortScratch::release()
-{
-    if (fixed) (void)guarded_free(fixed);
-    if (var) (void)guarded_free(var);
-    fixed = var = nullptr;
-    fixed_bytes = var_bytes = 0;
-}
-}  // namespace speck
 
 namespace {
 
@@ -70,13 +47,7 @@ struct SortStatus {
     unsigned long long temp_cursor;     // next free entry of the long-row temporaries
 };
 
-// the lists share three regions of `rows` words: list k lives in region k / 2, the even one grows up from the region's
-// first word, the odd one down from its last (the lists of a region hold different rows: they cannot meet)
-__host__ __device__ __forceinline__ u32* list_at(u32* lists, u32 rows, u32 k, u32 i)
-{
-    u32* region = lists + size_t(k >> 1) * rows;
-    return (k & 1u) ? region + (rows - 1u - i) : region + i;
-}
+// (the six lists share three regions of `rows` words: two_sided_at, device_common.hpp)
 
 // ------------------------------------------------------------------------------------------------ check + classify
 // 128 or 512 rows (the host picks by the average row length: a tile should hold enough entries to pay for its barriers,
@@ -135,11 +106,7 @@ __global__ __launch_bounds__(kClassifyThreads) void sort_classify_kernel(const u
             bad_col |= c[k] >= cols;
             if (i > lo && p[k] >= c[k]) {
                 if (i < seen_lo || i >= seen_hi) {  // (a long row: the row of the thread's previous find, as a rule)
-                    u32 a = 0, b = nr;  // the row of entry i: the first one whose end lies beyond i
-                    while (a < b) {
-                        const u32 mid = (a + b) >> 1;
-                        if (s_ro[mid + 1] <= i) a = mid + 1; else b = mid;
-                    }
+                    const u32 a = first_end_beyond(s_ro + 1, nr, i);  // the row of entry i
                     if (i > s_ro[a]) {  // (not the first entry of its row)
                         seen_lo = s_ro[a], seen_hi = s_ro[a + 1];
                         if (!s_flag[a]) s_flag[a] = 1;
@@ -171,7 +138,7 @@ __global__ __launch_bounds__(kClassifyThreads) void sort_classify_kernel(const u
         u32 first = 0;
         if (lane == leader) first = atomicAdd(&st->cnt[k], (u32)__popcll(m));
         first = (u32)__shfl((int)first, (int)leader);
-        if (cls == k) *list_at(lists, rows, k, first + (u32)__popcll(m & lanemask_lt())) = r0 + t;
+        if (cls == k) *two_sided_at(lists, rows, k, first + (u32)__popcll(m & lanemask_lt())) = r0 + t;
     }
     if (cls == LIST_GLOBAL) atomicAdd(&st->global_entries, (unsigned long long)len);
 }
@@ -205,7 +172,7 @@ __global__ __launch_bounds__(256) void sort_reg_kernel(const u32* __restrict__ r
     T* mine = s_val + gid * NP;
     const u32 n_list = st->cnt[K];
     for (u32 e = blockIdx.x * NG + gid; e < n_list; e += gridDim.x * NG) {
-        const u32 row = *list_at(lists, rows, K, e);
+        const u32 row = *two_sided_at(lists, rows, K, e);
         const u32 a0 = ro[row], n = min(ro[row + 1] - a0, NP);
         u32 c[PER];
         T v[PER];
@@ -226,7 +193,7 @@ __global__ __launch_bounds__(256) void sort_reg_kernel(const u32* __restrict__ r
         cmax = group_max<L>(cmax);
         if (cmax - cmin >= kSortRangeMax) {  // the key does not hold the row's columns: the LDS class takes it
             if (gl == 0) {
-                *list_at(lists, rows, LIST_LDS, atomicAdd(&st->cnt[LIST_LDS], 1u)) = row;
+                *two_sided_at(lists, rows, LIST_LDS, atomicAdd(&st->cnt[LIST_LDS], 1u)) = row;
                 atomicAdd(&st->deferred, 1u);
             }
             continue;
@@ -281,7 +248,7 @@ __global__ __launch_bounds__(256) void sort_lds_kernel(const u32* __restrict__ r
     const u32 t = threadIdx.x;
     const u32 n_list = st->cnt[LIST_LDS];
     for (u32 e = blockIdx.x; e < n_list; e += gridDim.x) {
-        const u32 row = *list_at(lists, rows, LIST_LDS, e);
+        const u32 row = *two_sided_at(lists, rows, LIST_LDS, e);
         const u32 a0 = ro[row], n = min(ro[row + 1] - a0, kSortLdsMax);
         u32 n2 = 2;
         while (n2 < n) n2 <<= 1;
@@ -355,7 +322,7 @@ __global__ __launch_bounds__(256) void sort_global_kernel(const u32* __restrict_
     const u32 t = threadIdx.x, lane = lane_id(), wid = t >> 6;
     const u32 n_list = st->cnt[LIST_GLOBAL];
     for (u32 e = blockIdx.x; e < n_list; e += gridDim.x) {
-        const u32 row = *list_at(lists, rows, LIST_GLOBAL, e);
+        const u32 row = *two_sided_at(lists, rows, LIST_GLOBAL, e);
         const u32 a0 = ro[row], n = ro[row + 1] - a0;
         if (t == 0) {
             s_off = atomicAdd(&st->temp_cursor, (unsigned long long)n);
@@ -462,46 +429,11 @@ __global__ __launch_bounds__(256) void sort_global_kernel(const u32* __restrict_
 // Rows move LEFT inside one buffer: in parallel that is a read / write race between rows, so the rows go through a
 // temporary (new columns, new values: nnz_out entries each) and are copied back with two device-to-device copies; the new
 // row offsets are built in a temporary as well and copied over row_offsets last.
-__global__ __launch_bounds__(1024) void sort_newlen_kernel(const u32* __restrict__ ro, const u32* __restrict__ row_dups, u32 rows,
-                                                           u32* __restrict__ block_sums)
-{
-    SPECK_POISON();
-    __shared__ u32 s_scan[1024 / 64 + 1];
-    const u32 r = blockIdx.x * 1024u + threadIdx.x;
-    const u32 len = r < rows ? ro[r + 1] - ro[r] - row_dups[r] : 0u;
-    u32 total;
-    (void)block_exclusive_scan<1024>(len, s_scan, &total);
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(1024) void sort_scan_sums_kernel(u32* __restrict__ block_sums, u32 n)
-{
-    SPECK_POISON();
-    __shared__ u32 s_scan[1024 / 64 + 1];
-    u32 carry = 0;
-    for (u32 i0 = 0; i0 < n; i0 += 1024) {
-        const u32 i = i0 + threadIdx.x;
-        const u32 v = i < n ? block_sums[i] : 0u;
-        u32 total;
-        const u32 ex = block_exclusive_scan<1024>(v, s_scan, &total);
-        if (i < n) block_sums[i] = carry + ex;
-        carry += total;
-    }
-}
-
-__global__ __launch_bounds__(1024) void sort_newoff_kernel(const u32* __restrict__ ro, const u32* __restrict__ row_dups, u32 rows,
-                                                           const u32* __restrict__ block_sums, u32* __restrict__ new_ro)
-{
-    SPECK_POISON();
-    __shared__ u32 s_scan[1024 / 64 + 1];
-    const u32 r = blockIdx.x * 1024u + threadIdx.x;
-    const u32 len = r < rows ? ro[r + 1] - ro[r] - row_dups[r] : 0u;
-    u32 total;
-    const u32 ex = block_exclusive_scan<1024>(len, s_scan, &total);
-    const u32 off = block_sums[blockIdx.x] + ex;
-    if (r < rows) new_ro[r] = off;
-    if (r + 1 == rows) new_ro[rows] = off + len;
-}
+// what a row keeps: the count the shared scan (scan.hpp) turns into the new row offsets
+struct SortNewLen {
+    const u32 *ro, *row_dups;
+    __device__ u32 operator()(u32 r) const { return ro[r + 1] - ro[r] - row_dups[r]; }
+};
 
 // a wave per row: the first entry of every run of equal columns carries the run's sum to its new place
 template <typename T>
@@ -538,20 +470,6 @@ __global__ __launch_bounds__(256) void sort_compact_kernel(const u32* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------ host
-int ensure(void** p, size_t* have, size_t want)
-{
-    if (*have >= want && *p) return SPECK_OK;
-    if (*p) (void)guarded_free(*p);
-    *p = nullptr, *have = 0;
-    HIP_TRY(guarded_malloc(p, want));
-    *have = want;
-    return SPECK_OK;
-}
-
-inline size_t up256(size_t b) { return (b + 255) & ~size_t(255); }
-
-u32 grid_rows(u64 work, u32 cap) { return (u32)std::max<u64>(1, std::min<u64>(work, cap)); }
-
 template <typename T>
 int sort_rows_run(SortScratch* sc, hipStream_t s, speck_dcsr* M, int flags, speck_sort_info* info)
 {
@@ -564,9 +482,9 @@ int sort_rows_run(SortScratch* sc, hipStream_t s, speck_dcsr* M, int flags, spec
 
     // status | lists (three regions of `rows` words) | duplicates per row (SUM only)
     const size_t list_bytes = up256(size_t(3) * rows * 4), dup_bytes = up256(size_t(rows) * 4);
-    int rc = ensure(&sc->fixed, &sc->fixed_bytes, 256 + list_bytes + dup_bytes);
+    int rc = sc->fixed.ensure(256 + list_bytes + dup_bytes);
     if (rc != SPECK_OK) return rc;
-    unsigned char* fb = static_cast<unsigned char*>(sc->fixed);
+    unsigned char* fb = static_cast<unsigned char*>(sc->fixed.p);
     SortStatus* st = reinterpret_cast<SortStatus*>(fb);
     u32* lists = reinterpret_cast<u32*>(fb + 256);
     u32* row_dups = reinterpret_cast<u32*>(fb + 256 + list_bytes);
@@ -598,10 +516,10 @@ int sort_rows_run(SortScratch* sc, hipStream_t s, speck_dcsr* M, int flags, spec
     const size_t g4 = up256(ge * 4), gv = up256(ge * sizeof(T));
     const size_t copy_c = keep_copy ? up256(nnz * 4) : 0, copy_v = keep_copy ? up256(nnz * sizeof(T)) : 0;
     if (3 * g4 + gv + copy_c + copy_v) {
-        rc = ensure(&sc->var, &sc->var_bytes, 3 * g4 + gv + copy_c + copy_v);
+        rc = sc->var.ensure(3 * g4 + gv + copy_c + copy_v);
         if (rc != SPECK_OK) return rc;
     }
-    unsigned char* vb = static_cast<unsigned char*>(sc->var);
+    unsigned char* vb = static_cast<unsigned char*>(sc->var.p);
     u32* saved_col = reinterpret_cast<u32*>(vb + 3 * g4 + gv);
     T* saved_val = reinterpret_cast<T*>(vb + 3 * g4 + gv + copy_c);
     if (keep_copy) {
@@ -613,25 +531,25 @@ int sort_rows_run(SortScratch* sc, hipStream_t s, speck_dcsr* M, int flags, spec
 
     const u32 reg_rows = h.cnt[LIST_R8] + h.cnt[LIST_R16] + h.cnt[LIST_R32] + h.cnt[LIST_R64];
     if (h.cnt[LIST_R8])
-        SPECK_LAUNCH((sort_reg_kernel<T, 8>), dim3(grid_rows((h.cnt[LIST_R8] + 31) / 32, 16384)), dim3(256), 0, s, ro, col, val, rows,
+        SPECK_LAUNCH((sort_reg_kernel<T, 8>), dim3(grid_of((h.cnt[LIST_R8] + 31) / 32, 16384)), dim3(256), 0, s, ro, col, val, rows,
                      lists, st, rd);
     if (h.cnt[LIST_R16])
-        SPECK_LAUNCH((sort_reg_kernel<T, 16>), dim3(grid_rows((h.cnt[LIST_R16] + 15) / 16, 16384)), dim3(256), 0, s, ro, col, val,
+        SPECK_LAUNCH((sort_reg_kernel<T, 16>), dim3(grid_of((h.cnt[LIST_R16] + 15) / 16, 16384)), dim3(256), 0, s, ro, col, val,
                      rows, lists, st, rd);
     if (h.cnt[LIST_R32])
-        SPECK_LAUNCH((sort_reg_kernel<T, 32>), dim3(grid_rows((h.cnt[LIST_R32] + 7) / 8, 16384)), dim3(256), 0, s, ro, col, val, rows,
+        SPECK_LAUNCH((sort_reg_kernel<T, 32>), dim3(grid_of((h.cnt[LIST_R32] + 7) / 8, 16384)), dim3(256), 0, s, ro, col, val, rows,
                      lists, st, rd);
     if (h.cnt[LIST_R64])
-        SPECK_LAUNCH((sort_reg_kernel<T, 64>), dim3(grid_rows((h.cnt[LIST_R64] + 3) / 4, 16384)), dim3(256), 0, s, ro, col, val, rows,
+        SPECK_LAUNCH((sort_reg_kernel<T, 64>), dim3(grid_of((h.cnt[LIST_R64] + 3) / 4, 16384)), dim3(256), 0, s, ro, col, val, rows,
                      lists, st, rd);
     // (the register kernels may hand rows on: the LDS launch is sized for all of them and reads the list length there)
     if (h.cnt[LIST_LDS] + reg_rows)
-        SPECK_LAUNCH(sort_lds_kernel<T>, dim3(grid_rows(u64(h.cnt[LIST_LDS]) + reg_rows, 8192)), dim3(256), 0, s, ro, col, val, rows,
+        SPECK_LAUNCH(sort_lds_kernel<T>, dim3(grid_of(u64(h.cnt[LIST_LDS]) + reg_rows, 8192)), dim3(256), 0, s, ro, col, val, rows,
                      lists, st, rd);
     if (h.cnt[LIST_GLOBAL]) {
         unsigned end_bit = 1;
         while (end_bit < 32 && (1ull << end_bit) < (cols ? cols : 1)) ++end_bit;
-        SPECK_LAUNCH(sort_global_kernel<T>, dim3(grid_rows(h.cnt[LIST_GLOBAL], 2048)), dim3(256), 0, s, ro, col, val, rows, lists, st,
+        SPECK_LAUNCH(sort_global_kernel<T>, dim3(grid_of(h.cnt[LIST_GLOBAL], 2048)), dim3(256), 0, s, ro, col, val, rows, lists, st,
                      rd, reinterpret_cast<u32*>(vb), reinterpret_cast<u32*>(vb + g4), reinterpret_cast<u32*>(vb + 2 * g4),
                      reinterpret_cast<T*>(vb + 3 * g4), ge, (u32)end_bit);
     }
@@ -656,17 +574,15 @@ int sort_rows_run(SortScratch* sc, hipStream_t s, speck_dcsr* M, int flags, spec
     const u64 nnz_out = nnz - h.dups;
     const u32 nblk = (rows + 1023) / 1024;
     const size_t b_sums = up256(size_t(nblk) * 4), b_ro = up256((size_t(rows) + 1) * 4), b_col = up256(nnz_out * 4);
-    rc = ensure(&sc->var, &sc->var_bytes, b_sums + b_ro + b_col + up256(nnz_out * sizeof(T)));
+    rc = sc->var.ensure(b_sums + b_ro + b_col + up256(nnz_out * sizeof(T)));
     if (rc != SPECK_OK) return rc;
-    vb = static_cast<unsigned char*>(sc->var);
+    vb = static_cast<unsigned char*>(sc->var.p);
     u32* block_sums = reinterpret_cast<u32*>(vb);
     u32* new_ro = reinterpret_cast<u32*>(vb + b_sums);
     u32* out_col = reinterpret_cast<u32*>(vb + b_sums + b_ro);
     T* out_val = reinterpret_cast<T*>(vb + b_sums + b_ro + b_col);
-    SPECK_LAUNCH(sort_newlen_kernel, dim3(nblk), dim3(1024), 0, s, ro, row_dups, rows, block_sums);
-    SPECK_LAUNCH(sort_scan_sums_kernel, dim3(1), dim3(1024), 0, s, block_sums, nblk);
-    SPECK_LAUNCH(sort_newoff_kernel, dim3(nblk), dim3(1024), 0, s, ro, row_dups, rows, block_sums, new_ro);
-    SPECK_LAUNCH(sort_compact_kernel<T>, dim3(grid_rows((u64(rows) + 3) / 4, 16384)), dim3(256), 0, s, ro, col, val, new_ro, rows,
+    launch_exclusive_scan(s, SortNewLen{ro, row_dups}, rows, block_sums, new_ro, nullptr);
+    SPECK_LAUNCH(sort_compact_kernel<T>, dim3(grid_of((u64(rows) + 3) / 4, 16384)), dim3(256), 0, s, ro, col, val, new_ro, rows,
                  out_col, out_val);
     HIP_TRY(hipMemcpyAsync(col, out_col, nnz_out * 4, hipMemcpyDeviceToDevice, s));
     HIP_TRY(hipMemcpyAsync(val, out_val, nnz_out * sizeof(T), hipMemcpyDeviceToDevice, s));
@@ -681,24 +597,9 @@ int sort_rows_run(SortScratch* sc, hipStream_t s, speck_dcsr* M, int flags, spec
 // debug option guard_bytes: the canary zones of M's buffers and of the temporaries after the call
 int check_sort_guards(const SortScratch* sc, hipStream_t s, const speck_dcsr* M, int rc)
 {
-    if (!guard_bytes()) return rc;
-    std::vector<GuardZone> z;
-    const void* whole[] = {sc->fixed, sc->var, M->data, M->col_ids, M->row_offsets};
+    const void* whole[] = {sc->fixed.p, sc->var.p, M->data, M->col_ids, M->row_offsets};
     static const char* names[] = {"sort lists", "sort temporaries", "M.data", "M.col_ids", "M.row_offsets"};
-    std::vector<int> owner;
-    for (int i = 0; i < 5; ++i) {
-        const size_t before = z.size();
-        if (whole[i]) guard_zones_of(whole[i], &z);
-        for (size_t k = before; k < z.size(); ++k) owner.push_back(i);
-    }
-    int bad = -1;
-    size_t at = 0;
-    const int n = guard_check(z, s, &bad, &at);
-    if (n == 0) return rc;
-    if (n < 0) return rc == SPECK_OK ? SPECK_ERR_HIP : rc;
-    std::fprintf(stderr, "speck_amd: guard_bytes: %d canary zone(s) touched by the row sort; first: %s, byte %zu\n", n,
-                 names[owner[bad]], at);
-    return rc == SPECK_OK ? SPECK_ERR_HIP : rc;
+    return guard_check_buffers(whole, names, 5, s, " by the row sort", rc);
 }
 
 template <typename T>
@@ -712,17 +613,11 @@ int sort_rows_impl(speck_config* cfg, speck_dcsr* M, int flags, speck_sort_info*
         *info = speck_sort_info{};
         info->nnz_out = M->nnz;
     }
-    if (!cfg) {  // (a config exists only where a device does)
-        int n = 0;
-        if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) {
-            (void)hipGetLastError();
-            return SPECK_ERR_NO_DEVICE;
-        }
-    }
+    if (!cfg && !device_present()) return SPECK_ERR_NO_DEVICE;
     if (M->rows == 0) return SPECK_OK;
     SortScratch own;
     SortScratch* sc = cfg ? sort_scratch(cfg) : &own;
-    const hipStream_t s = cfg ? sort_stream(cfg) : nullptr;
+    const hipStream_t s = cfg ? call_stream(cfg) : nullptr;
     (void)take_launch_error();
     int rc = sort_rows_run<T>(sc, s, M, flags, info);
     rc = check_sort_guards(sc, s, M, rc);

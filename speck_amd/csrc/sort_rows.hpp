@@ -1,12 +1,6 @@
 // sort_rows.hpp -- what speck_sort_rows_* (sort_rows.hip) needs from a config (pipeline.hip owns the structure).
 #pragma once
-#include <hip/hip_runtime.h>
-
-#include <cstddef>
-
-#include "device_common.hpp"
-
-struct speck_config;
+#include "host_common.hpp"
 
 namespace speck {
 
@@ -15,16 +9,12 @@ namespace speck {
 // (status block, class lists, duplicates per row), `var` from what the classifying pass found (long-row ping-pong
 // buffers, compaction targets, the copy a refused view is restored from).  Released with the config.
 struct SortScratch {
-    void* fixed = nullptr;
-    size_t fixed_bytes = 0;
-    void* var = nullptr;
-    size_t var_bytes = 0;
+    DeviceBuffer fixed, var;
     u32 reg_max = 256;    // options sort_reg_max / sort_lds_max (clamped to SPECK_SORT_REG_MAX / SPECK_SORT_LDS_MAX)
     u32 lds_max = 4096;
-    void release();
+    void release() { fixed.release(), var.release(); }
 };
 
 SortScratch* sort_scratch(speck_config* c);
-hipStream_t sort_stream(speck_config* c);
 
 }  // namespace speck

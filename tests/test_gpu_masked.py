@@ -501,3 +501,69 @@ def test_no_canary_zone_is_touched(dtype):
     finally:
         cfg.set_option("guard_bytes", 0)
         cfg.cleanup()
+
+# ---------------------------------------------------------------------------------------------------- 10: the scans at their edges
+def scan_case(rows, last_row_cols=7):
+    """A: one entry per row, column r mod 16, value r mod 7 + 1.  B: 16 x 8, row k holds columns k mod 8 and (k + 3) mod 8
+    (ascending) with the values 2 k + 1 and 2 k + 2.  M: columns 0 .. 3 in every row, 0 .. last_row_cols - 1 in the last
+    one.  C = the mask entries that meet the B row of their row's entry of A, a * b: exact in either precision.  Built and
+    expected without a Python loop over the rows."""
+    r = np.arange(rows)
+    A = po.HostCSR(rows, 16, np.arange(rows + 1, dtype=np.uint32), (r % 16).astype(np.uint32), (r % 7 + 1).astype(np.float64))
+    k = np.arange(16)
+    b_ci = np.sort(np.stack([k % 8, (k + 3) % 8], axis=1), axis=1)
+    b_va = np.stack([2 * k + 1, 2 * k + 2], axis=1).astype(np.float64)
+    B = po.HostCSR(16, 8, (2 * np.arange(17)).astype(np.uint32), b_ci.ravel().astype(np.uint32), b_va.ravel())
+    dense_b = np.zeros((16, 8))
+    dense_b[k[:, None], b_ci] = b_va
+    m_len = np.full(rows, 4)
+    m_len[-1] = last_row_cols
+    m_ro = np.zeros(rows + 1, dtype=np.uint32)
+    m_ro[1:] = np.cumsum(m_len)
+    m_row = np.repeat(r, m_len)
+    m_ci = (np.arange(int(m_ro[-1])) - m_ro[:-1].astype(np.int64)[m_row]).astype(np.uint32)
+    M = po.HostCSR(rows, 8, m_ro, m_ci, np.ones(len(m_ci)))
+    b_at = dense_b[m_row % 16, m_ci]
+    hit = b_at != 0
+    e_ro = np.zeros(rows + 1, dtype=np.uint32)
+    e_ro[1:] = np.cumsum(np.bincount(m_row[hit], minlength=rows))
+    return A, B, M, (e_ro, m_ci[hit], (A.data[m_row] * b_at)[hit])
+
+
+def check_scan_case(cfg, dtype, rows, last_row_cols=7):
+    A, B, M, (e_ro, e_ci, e_va) = scan_case(rows, last_row_cols)
+    dC, info = sa.multiply_masked(to_dev(as_dtype(A, dtype)), to_dev(as_dtype(B, dtype)), to_dev(M), cfg)
+    got = dC.to_host()
+    assert (got.rows, got.cols, got.nnz) == (rows, 8, len(e_ci))
+    assert info.nnz_out == len(e_ci) and info.hits == len(e_ci) and info.products == 2 * rows
+    assert got.row_offsets.tobytes() == e_ro.tobytes(), "row_offsets differ"
+    assert got.col_ids.tobytes() == e_ci.tobytes(), "col_ids differ"
+    assert got.data.dtype == np.dtype(dtype) and got.data.tobytes() == e_va.astype(dtype).tobytes(), "values differ"
+
+
+SCAN_ROWS = [1023, 1024, 1025, 2049, 1024 * 1024 + 1]
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("rows", SCAN_ROWS)
+def test_structure_scans_across_workgroup_boundaries(cfg, dtype, rows):
+    """Both scans of the STRUCTURE finish at their boundaries: 1024 rows per workgroup of the row scan (one short, exact,
+    one more, two and a row, more than 1024 workgroups: the second trip over the workgroup sums) and, with nnz(M) =
+    4 rows + 3, the same for the 4096-entry tiles of the compaction -- 4 194 311 entries at the largest: past 1024 tiles and
+    no multiple of four, so the last word of hit bytes is masked."""
+    check_scan_case(cfg, dtype, rows)
+
+
+@pytest.mark.parametrize("nnz_m", [4095, 4096, 4097])
+def test_structure_compaction_at_the_first_tile_boundary(cfg, nnz_m):
+    check_scan_case(cfg, np.float64, 1024, last_row_cols=4 + nnz_m - 4096)
+
+
+def test_structure_scans_with_canary_zones():
+    cfg = sa.spECKConfig.initialize(0)
+    try:
+        cfg.set_option("guard_bytes", 4096)
+        check_scan_case(cfg, np.float64, 1025)
+    finally:
+        cfg.set_option("guard_bytes", 0)
+        cfg.cleanup()

@@ -250,6 +250,47 @@ def test_duplicates_summed_random_values(cfg, dtype):
         assert ((got.data == ref) | (got.data == lo) | (got.data == hi)).all()
 
 
+# ---------------------------------------------------------------------------------------------------- the scan at its edges
+def two_entry_rows(rows):
+    """every row two entries, by r mod 3: (5, 3) out of order, (4, 4) a duplicate to merge, (1, 2) in order; the values
+    1 .. 2 rows.  Returns the matrix and what SUM_DUPLICATES has to leave, both built without a Python loop."""
+    kind = np.arange(rows) % 3
+    ci = np.array([[5, 3], [4, 4], [1, 2]], dtype=np.uint32)[kind].ravel()
+    va = np.arange(1, 2 * rows + 1, dtype=np.float64)
+    ro = (2 * np.arange(rows + 1)).astype(np.uint32)
+    first, second = va[0::2], va[1::2]
+    e_ci = np.array([[3, 5], [4, 4], [1, 2]], dtype=np.uint32)[kind]
+    e_va = np.stack([np.where(kind == 0, second, np.where(kind == 1, first + second, first)),
+                     np.where(kind == 0, first, second)], axis=1)
+    keep = np.ones((rows, 2), dtype=bool)
+    keep[kind == 1, 1] = False                                   # the merged row keeps one entry
+    e_ro = np.zeros(rows + 1, dtype=np.uint32)
+    e_ro[1:] = np.cumsum(keep.sum(axis=1))
+    return (ro, ci, va), (e_ro, e_ci[keep], e_va[keep]), kind
+
+
+SCAN_ROWS = [1023, 1024, 1025, 2049, 1024 * 1024 + 1]
+
+
+@pytest.mark.parametrize("rows", SCAN_ROWS)
+def test_compaction_scan_across_workgroup_boundaries(cfg, rows):
+    """The new row offsets come from a device-wide scan of 1024 rows per workgroup whose workgroup sums are scanned 1024
+    at a time: one row short of a workgroup, exactly one, one more, two and a row, and one more than 1024 workgroups (the
+    second trip of the loop over the sums).  Integers below 2^23: every sum is exact."""
+    (ro, ci, va), (e_ro, e_ci, e_va), kind = two_entry_rows(rows)
+    merged = int((kind == 1).sum())
+    d = upload(ro, ci, va, 8)
+    info = sa.sort_rows(d, cfg, sum_duplicates=True)
+    got = d.to_host()
+    assert d.nnz == 2 * rows - merged and info.nnz_out == d.nnz and info.duplicates == merged
+    assert info.rows_in_order == int((kind == 2).sum()) and sum(info.rows_sorted) == rows - info.rows_in_order
+    assert same_bytes(got.row_offsets, e_ro)
+    assert same_bytes(got.col_ids, e_ci)
+    assert same_bytes(got.data, e_va)
+    again = sa.sort_rows(d, cfg, sum_duplicates=True)
+    assert again.rows_in_order == rows and again.duplicates == 0 and again.nnz_out == d.nnz and sum(again.rows_sorted) == 0
+
+
 # ---------------------------------------------------------------------------------------------------- views
 def test_row_range_view(cfg):
     ro, ci, va, cols = duplicate_matrix(np.float64, lambda rng, n: np.arange(n, dtype=np.float64), seed=33)
