@@ -301,6 +301,67 @@ int speck_multiply_masked_f64(speck_config *cfg, const speck_dcsr *A, const spec
 int speck_multiply_masked_f32(speck_config *cfg, const speck_dcsr *A, const speck_dcsr *B, const speck_dcsr *M,
                               speck_dcsr *C, int flags, speck_masked_info *info);
 
+/* ---- filter (new: the reference has no counterpart): C = the entries of A that every selected predicate keeps -- the
+ *      strict lower triangle of a matrix that is already on the device (triangle counting: L o (L L)), "keep (i,j) in M"
+ *      behind a full product and its complement (frontiers, new edges only), the explicit zeros a product leaves where its
+ *      terms cancel, everything below a tolerance.  Every row of C is the row of A without the dropped entries, IN INPUT ORDER;
+ *      column ids and values are copied bit for bit (-0.0, NaN payloads and subnormals survive).  Rows of A need NOT be
+ *      sorted or free of duplicates.
+ *  flags selects the predicates; an entry is kept iff EVERY selected one holds; SPECK_SELECT_NOT_x negates predicate x.
+ *      flags == 0 keeps everything (speck_dcsr_copy with the offsets rebased).  A NOT_x bit without x, or an unknown bit:
+ *      SPECK_ERR_INVALID.
+ *  SPECK_SELECT_BAND: band_lo <= (int64)col - (int64)(row_base + i) <= band_hi, i the row inside A.  band_lo = INT64_MIN /
+ *      band_hi = INT64_MAX leave that side open: tril(k) is hi = k, triu(k) is lo = k, the diagonal lo = hi = 0, off the
+ *      diagonal the same with NOT_BAND.  band_lo > band_hi, or row_base > 2^62: SPECK_ERR_INVALID.  row_base is the global
+ *      index of A's first row where A is a row-range view of a larger matrix, else 0; the other predicates ignore it.
+ *  SPECK_SELECT_ABS: !(|v| <= abs_threshold), compared in double for both value types (a float is widened; the threshold
+ *      is never rounded).  Written that way a NaN VALUE IS KEPT: a filter must not hide one.  With NOT_ABS the test is
+ *      |v| <= abs_threshold, and a NaN is dropped.  abs_threshold = 0 drops exactly +0.0 and -0.0.  The threshold is >= 0 and
+ *      may be +inf; NaN or negative: SPECK_ERR_INVALID.
+ *  SPECK_SELECT_PATTERN: (i,j) is an entry of *pattern, a matrix of rows(A) x cols(A) of which only the pattern is read
+ *      (data may be NULL).  A row of it that is not strictly ascending or holds an id >= cols: SPECK_ERR_UNSORTED (the
+ *      remedy is speck_sort_rows_*, as for the mask of the masked product).  A and pattern may both be row-range views
+ *      with absolute offsets.
+ *  Offsets of A / pattern descending or leaving [row_offsets[0], row_offsets[0] + nnz], a column id of A >= cols, NULL
+ *      buffers with nnz > 0, a NULL pattern or one of another shape, C sharing a buffer with A or pattern:
+ *      SPECK_ERR_INVALID.  rows, cols <= 2^27 (SPECK_ERR_DIM_LIMIT), nnz < 2^32.
+ *  Ownership of C as speck_multiply_* and speck_multiply_masked_* document it: row_offsets reused when C->rows == A->rows,
+ *      data / col_ids re-allocated only when C->nnz differs from the result's (a result of 0 entries owns buffers of one
+ *      entry).  On any error the struct, its allocations AND the contents of C are untouched.  One pass checks the inputs and
+ *      marks the entries; it clamps and never follows an offset or id it has not checked, and every kernel that writes C
+ *      starts after the host has read its verdict.
+ *  There is NO in-place mode: rows moving left inside one buffer in parallel race (a workgroup overwrites entries another
+ *      has not read yet), and the way round it that the row sort takes -- compact into a temporary, copy back -- costs the
+ *      memory of the second matrix anyway.
+ *  Runs on the config's stream (speck_config_set_stream is honoured) and returns with C complete.  Temporaries are grow-only
+ *      buffers of the config's own (not the multiply's arena: a select between two identical multiplies does not disturb
+ *      the second one's reuse sequence), released with it; cfg == NULL is allowed as for speck_sort_rows_*.  With the debug
+ *      option guard_bytes the canary zones of the temporaries and of C are checked after the call.
+ *  The marking pass walks tiles of SPECK_SELECT_TILE_ROWS_LONG rows where a row of A (and of pattern) holds
+ *      SPECK_SELECT_LONG_ROW_AVG entries or more on average, of SPECK_SELECT_TILE_ROWS_SHORT rows elsewhere. ---- */
+enum { SPECK_SELECT_BAND = 1, SPECK_SELECT_ABS = 2, SPECK_SELECT_PATTERN = 4,
+       SPECK_SELECT_NOT_BAND = 16, SPECK_SELECT_NOT_ABS = 32, SPECK_SELECT_NOT_PATTERN = 64 };
+#define SPECK_SELECT_TILE_ROWS_LONG 256
+#define SPECK_SELECT_TILE_ROWS_SHORT 1024
+#define SPECK_SELECT_LONG_ROW_AVG 32
+typedef struct speck_select_params {
+    uint32_t flags;              /* SPECK_SELECT_* */
+    int64_t band_lo, band_hi;    /* BAND */
+    uint64_t row_base;           /* BAND: global index of A's first row */
+    double abs_threshold;        /* ABS */
+    const speck_dcsr *pattern;   /* PATTERN */
+} speck_select_params;
+typedef struct speck_select_info {
+    uint64_t kept;               /* entries of A that went to C */
+    uint64_t dropped;            /* ... and that did not */
+    uint64_t rows_unchanged;     /* rows that kept every entry (empty rows among them) */
+    uint64_t nnz_out;            /* nnz(C) = kept */
+} speck_select_info;
+int speck_select_f64(speck_config *cfg, const speck_dcsr *A, const speck_select_params *p, speck_dcsr *C,
+                     speck_select_info *info /* may be NULL */);
+int speck_select_f32(speck_config *cfg, const speck_dcsr *A, const speck_select_params *p, speck_dcsr *C,
+                     speck_select_info *info);
+
 /* ---- row-sharded multi-GPU (new: the reference is single-GPU, source/Executor.cpp:25).  One process per GPU;
  *      rank p multiplies the row range [b_p, b_{p+1}) of A (a view with absolute offsets, boundaries from
  *      speck_partition_rows) with a replicated B, then ONE exchange concatenates the shards on a root rank:

@@ -54,6 +54,17 @@ class CMaskedInfo(C.Structure):
                 ("nnz_out", C.c_uint64)]
 
 
+class CSelectParams(C.Structure):
+    # include/speck_c_api.h: speck_select_params
+    _fields_ = [("flags", C.c_uint32), ("band_lo", C.c_int64), ("band_hi", C.c_int64), ("row_base", C.c_uint64),
+                ("abs_threshold", C.c_double), ("pattern", C.POINTER(DCsr))]
+
+
+class CSelectInfo(C.Structure):
+    # include/speck_c_api.h: speck_select_info
+    _fields_ = [("kept", C.c_uint64), ("dropped", C.c_uint64), ("rows_unchanged", C.c_uint64), ("nnz_out", C.c_uint64)]
+
+
 # every symbol include/speck_c_api.h declares, with its ctypes signature
 _P = C.POINTER
 _SIGS = {
@@ -87,6 +98,8 @@ _SIGS = {
     "speck_sort_rows_f32": (C.c_int, [C.c_void_p, _P(DCsr), C.c_int, _P(CSortInfo)]),
     "speck_multiply_masked_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), _P(DCsr), _P(DCsr), C.c_int, _P(CMaskedInfo)]),
     "speck_multiply_masked_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), _P(DCsr), _P(DCsr), C.c_int, _P(CMaskedInfo)]),
+    "speck_select_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(CSelectParams), _P(DCsr), _P(CSelectInfo)]),
+    "speck_select_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(CSelectParams), _P(DCsr), _P(CSelectInfo)]),
     "speck_compare_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), C.c_int, C.c_double, _P(C.c_uint64)]),
     "speck_compare_bounded_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), _P(DCsr), C.c_double, _P(C.c_uint64),
                                             _P(C.c_uint64)]),

@@ -487,3 +487,78 @@ def multiply_masked(A, B, M, config, matOut=None, full_pattern=False):
               1 if full_pattern else 0, C.byref(info)), "multiply_masked")
     matOut._host_row_offsets = None  # (row_offsets were rewritten on the device)
     return matOut, MaskedInfo(info)
+
+
+# include/speck_c_api.h: SPECK_SELECT_* flags; SPECK_SELECT_TILE_ROWS_LONG / _SHORT (rows per tile of the marking pass: the
+# first where a row of A and of the pattern holds SELECT_LONG_ROW_AVG entries or more on average, the second elsewhere)
+SELECT_BAND, SELECT_ABS, SELECT_PATTERN = 1, 2, 4
+SELECT_NOT_BAND, SELECT_NOT_ABS, SELECT_NOT_PATTERN = 16, 32, 64
+SELECT_TILE_ROWS = (256, 1024)
+SELECT_LONG_ROW_AVG = 32
+_INT64_MIN, _INT64_MAX = -(1 << 63), (1 << 63) - 1
+
+
+class SelectInfo:
+    """speck_select_info: what a select call kept and dropped."""
+
+    def __init__(self, c):
+        self.kept = int(c.kept)
+        self.dropped = int(c.dropped)
+        self.rows_unchanged = int(c.rows_unchanged)
+        self.nnz_out = int(c.nnz_out)
+
+    def __repr__(self):
+        return (f"SelectInfo(kept={self.kept}, dropped={self.dropped}, rows_unchanged={self.rows_unchanged}, "
+                f"nnz_out={self.nnz_out})")
+
+
+def select(A, config, band=None, abs_gt=None, pattern=None, negate=(), row_base=0, matOut=None):
+    """C = the entries of A that every given predicate keeps, in input order, bit for bit (speck_select_f64 / _f32).
+    band=(lo, hi): lo <= col - (row_base + row) <= hi, None leaves a side open; abs_gt=t: not (|v| <= t), so a NaN is kept;
+    pattern=M: (row, col) is an entry of the device matrix M (only its pattern is read).  negate: those of "band", "abs",
+    "pattern" whose predicate is to be inverted.  No predicate: a copy.  config may be None.  Returns (matOut, SelectInfo)."""
+    L = _lib.load()
+    negate = (negate,) if isinstance(negate, str) else tuple(negate)
+    unknown = set(negate) - {"band", "abs", "pattern"}
+    if unknown:
+        raise ValueError(f"negate: unknown predicate(s) {sorted(unknown)}")
+    p = _lib.CSelectParams()
+    flags = 0
+    p.band_lo, p.band_hi = _INT64_MIN, _INT64_MAX
+    if band is not None:
+        lo, hi = band
+        p.band_lo = _INT64_MIN if lo is None else int(lo)
+        p.band_hi = _INT64_MAX if hi is None else int(hi)
+        flags |= SELECT_BAND
+    if abs_gt is not None:
+        p.abs_threshold = float(abs_gt)
+        flags |= SELECT_ABS
+    if pattern is not None:
+        p.pattern = C.pointer(pattern._c)
+        flags |= SELECT_PATTERN
+    for name, bit in (("band", SELECT_NOT_BAND), ("abs", SELECT_NOT_ABS), ("pattern", SELECT_NOT_PATTERN)):
+        if name in negate:
+            flags |= bit     # (without its predicate: the library refuses it)
+    p.flags = flags
+    p.row_base = int(row_base)
+    fn = L.speck_select_f32 if A.dtype == np.float32 else L.speck_select_f64
+    if matOut is None:
+        matOut = dCSR(A.dtype)
+    if matOut.dtype != A.dtype:
+        matOut.reset()
+        matOut.dtype = A.dtype
+    info = _lib.CSelectInfo()
+    _check(fn(config._h if config is not None else None, C.byref(A._c), C.byref(p), C.byref(matOut._c), C.byref(info)),
+           "select")
+    matOut._host_row_offsets = None  # (row_offsets were rewritten on the device)
+    return matOut, SelectInfo(info)
+
+
+def tril(A, config, k=0):
+    """The entries of A on and below the k-th diagonal (scipy.sparse.tril), made on the device."""
+    return select(A, config, band=(None, k))[0]
+
+
+def triu(A, config, k=0):
+    """The entries of A on and above the k-th diagonal (scipy.sparse.triu), made on the device."""
+    return select(A, config, band=(k, None))[0]

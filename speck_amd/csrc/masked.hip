@@ -15,7 +15,7 @@
 //   masked_global_kernel     a workgroup per longer row: binary search in the mask row where it lies, global atomic adds.
 //   (all three walk a row's products flattened, a batch of entries of A at a time: "the product walk" below)
 //   finish                   STRUCTURE: hits per row -> the shared scan (scan.hpp) -> the new row offsets; the same scan
-//                            over the hit bytes -> one streaming compaction.  FULL_PATTERN: the accumulators
+//                            over the hit bytes -> one streaming compaction (compact.hpp).  FULL_PATTERN: the accumulators
 //                            are C's values (fp64: accumulated in place), offsets rebased, column ids copied.
 // A hit is marked in bit 31 of the column's LDS copy (columns are < 2^27).  As in the multiply a product is rounded to T,
 // the sum is kept in double and rounded once.  Every kernel but the classifying pass starts after the host has read the
@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "compact.hpp"
 #include "launch.hpp"
 #include "masked.hpp"
 #include "scan.hpp"
@@ -548,47 +549,8 @@ struct MaskedRowCount {
     __device__ u32 operator()(u32 r) const { return row_cnt[r]; }
 };
 
-// The compaction needs no rows: C's entries are M's entries with a hit, in M's order, so an entry's place is the number of
-// hits in front of it -- the shared scan over the hit bytes, a word of four per item (4096 entries per workgroup), as far
-// as the scanned workgroup sums; the kernel below places the four entries of a thread itself.  (First form: eight lanes
-// per row looking up the row's new offset -- 0.37 ms for the 1 M short rows of the webbase stand-in.)
-constexpr u32 kCompactTile = 4096;
-
-struct MaskedHitWord {
-    const u32* hit32;
-    u64 n;  // entries of M
-    // the hit bytes of entries 4 i .. 4 i + 3, a bit each
-    __device__ __forceinline__ u32 word(u32 i) const
-    {
-        const u64 e0 = u64(i) * 4;
-        if (e0 >= n) return 0u;
-        u32 w = hit32[i] & 0x01010101u;
-        if (e0 + 4 > n) w &= 0xFFFFFFFFu >> (8u * (u32)(e0 + 4 - n));  // (the bytes behind the last entry were never written)
-        return w;
-    }
-    __device__ __forceinline__ u32 operator()(u32 i) const { return (u32)__popc(word(i)); }
-};
-
-template <typename T>
-__global__ __launch_bounds__(1024) void masked_compact_kernel(const MaskedHitWord f, const u32* __restrict__ tile_sums,
-                                                              const u32* __restrict__ m_col, const double* __restrict__ acc,
-                                                              u32* __restrict__ c_col, T* __restrict__ c_val)
-{
-    SPECK_POISON();
-    __shared__ u32 s_scan[1024 / 64 + 1];
-    const u32 i = blockIdx.x * 1024u + threadIdx.x;
-    const u64 e0 = u64(i) * 4;
-    const u32 w = f.word(i);
-    u32 total;
-    u32 to = tile_sums[blockIdx.x] + block_exclusive_scan<1024>((u32)__popc(w), s_scan, &total);
-#pragma unroll
-    for (u32 k = 0; k < 4; ++k)
-        if ((w >> (8u * k)) & 1u) {
-            c_col[to] = m_col[e0 + k];
-            c_val[to] = (T)acc[e0 + k];
-            ++to;
-        }
-}
+// The compaction needs no rows: C's entries are M's entries with a hit, in M's order -- KeepWord over the hit bytes and
+// compact_entries_kernel (compact.hpp), from the accumulators (double) to C's values (T).
 
 // FULL_PATTERN: C.row_offsets = M.row_offsets rebased to 0; the values rounded where the accumulators are not C's own
 __global__ __launch_bounds__(256) void masked_rebase_kernel(const u32* __restrict__ m_ro, u32 rows, u32* __restrict__ c_ro)
@@ -609,56 +571,7 @@ __global__ __launch_bounds__(256) void masked_round_kernel(const double* __restr
 // dynamic LDS of the LDS class: accumulators | columns | table | batch
 constexpr u32 lds_bytes(u32 cap, u32 threads) { return cap * 16u + threads * 8u; }
 
-// The buffers C will own once the call has completed, by the multiply's rule: row_offsets reused when C->rows == rows(A),
-// data / col_ids re-allocated only when C->nnz differs.  Nothing of C changes before publish().
-struct COut {
-    u32* ro = nullptr;
-    u32* col = nullptr;
-    void* val = nullptr;
-    bool own_ro = false, own_data = false;
-    void discard()
-    {
-        if (own_ro && ro) (void)guarded_free(ro);
-        if (own_data && col) (void)guarded_free(col);
-        if (own_data && val) (void)guarded_free(val);
-        *this = COut{};
-    }
-};
-
-int prepare_c(const speck_dcsr* C, u64 rows, u64 nnz_out, size_t vsize, COut* out)
-{
-    if (C->rows == rows && C->row_offsets) out->ro = C->row_offsets;
-    else {
-        HIP_TRY(guarded_malloc(reinterpret_cast<void**>(&out->ro), (size_t(rows) + 1) * sizeof(u32)));
-        out->own_ro = true;
-    }
-    if (C->nnz != nnz_out || !C->data || !C->col_ids) {
-        out->own_data = true;
-        const hipError_t e1 = guarded_malloc(&out->val, std::max<size_t>(nnz_out, 1) * vsize);
-        const hipError_t e2 = e1 == hipSuccess ? guarded_malloc(reinterpret_cast<void**>(&out->col), std::max<size_t>(nnz_out, 1) * 4) : e1;
-        if (e1 != hipSuccess || e2 != hipSuccess) {
-            (void)hipGetLastError();
-            out->discard();
-            return SPECK_ERR_OOM;
-        }
-    } else {
-        out->val = C->data;
-        out->col = C->col_ids;
-    }
-    return SPECK_OK;
-}
-
-void publish_c(speck_dcsr* C, u64 rows, u64 cols, u64 nnz_out, COut* out)
-{
-    if (out->own_data) {
-        if (C->data) (void)guarded_free(C->data);
-        if (C->col_ids) (void)guarded_free(C->col_ids);
-    }
-    if (C->row_offsets && C->row_offsets != out->ro) (void)guarded_free(C->row_offsets);
-    C->rows = rows, C->cols = cols, C->nnz = nnz_out;
-    C->data = out->val, C->col_ids = out->col, C->row_offsets = out->ro;
-    *out = COut{};
-}
+// (C's buffers by the multiply's rule: COut, prepare_c, publish_c -- compact.hpp)
 
 template <typename T>
 int masked_run(MaskedScratch* sc, hipStream_t s, const speck_dcsr* A, const speck_dcsr* B, const speck_dcsr* M, speck_dcsr* C,
@@ -788,10 +701,10 @@ int masked_run(MaskedScratch* sc, hipStream_t s, const speck_dcsr* A, const spec
         rc = prepare_c(C, rows, nnz_out, sizeof(T), out);
         if (rc != SPECK_OK) return rc;
         if (nnz_out) {
-            const MaskedHitWord words{reinterpret_cast<const u32*>(hit), nnz_m};
+            const KeepWord words{reinterpret_cast<const u32*>(hit), nnz_m};
             u32* tile_sums = reinterpret_cast<u32*>(vb + acc_bytes + hit_bytes);
             launch_exclusive_scan(s, words, (u32)((nnz_m + 3) / 4), tile_sums, nullptr, nullptr);
-            SPECK_LAUNCH(masked_compact_kernel<T>, dim3(ntiles), dim3(1024), 0, s, words, tile_sums, M->col_ids + h.base_m, acc,
+            SPECK_LAUNCH((compact_entries_kernel<double, T>), dim3(ntiles), dim3(1024), 0, s, words, tile_sums, M->col_ids + h.base_m, acc,
                          out->col, static_cast<T*>(out->val));
         }
         HIP_TRY(hipMemcpyAsync(out->ro, new_ro, (size_t(rows) + 1) * 4, hipMemcpyDeviceToDevice, s));
@@ -825,23 +738,6 @@ int check_masked_guards(const MaskedScratch* sc, hipStream_t s, const speck_dcsr
     const void* whole[] = {sc->fixed.p, sc->var.p, C->data, C->col_ids, C->row_offsets};
     static const char* names[] = {"masked lists", "masked accumulators", "C.data", "C.col_ids", "C.row_offsets"};
     return guard_check_buffers(whole, names, 5, s, " by the masked product", rc);
-}
-
-bool csr_args_ok(const speck_dcsr* X, bool needs_values)
-{
-    if (X->rows && !X->row_offsets) return false;
-    if (X->nnz && (!X->col_ids || (needs_values && !X->data))) return false;
-    return true;
-}
-
-bool shares_buffer(const speck_dcsr* C, const speck_dcsr* X)
-{
-    const void* mine[] = {C->data, C->col_ids, C->row_offsets};
-    const void* theirs[] = {X->data, X->col_ids, X->row_offsets};
-    for (const void* p : mine)
-        for (const void* q : theirs)
-            if (p && p == q) return true;
-    return false;
 }
 
 template <typename T>

@@ -30,6 +30,7 @@
 #include "launch.hpp"
 #include "row_groups.hpp"
 #include "masked.hpp"
+#include "select.hpp"
 #include "sort_rows.hpp"
 
 using namespace speck;
@@ -231,6 +232,7 @@ struct speck_config {
     std::vector<GuardZone> arena_zones, gpool_zones, nfpool_zones;
     SortScratch sort;  // temporaries and class limits of speck_sort_rows_* (sort_rows.hip)
     MaskedScratch masked;  // ... and of speck_multiply_masked_* (masked.hip)
+    SelectScratch select;  // ... and of speck_select_* (select.hip)
     const void* zones_arena = nullptr;
     u64 zones_m = 0, zones_nnz = 0, zones_gap = 0;
     bool gpool_zones_filled = false;
@@ -1915,6 +1917,8 @@ namespace speck {
 SortScratch* sort_scratch(speck_config* c) { return &c->sort; }
 hipStream_t call_stream(speck_config* c) { return main_stream(c); }
 MaskedScratch* masked_scratch(speck_config* c) { return &c->masked; }
+
+SelectScratch* select_scratch(speck_config* c) { return &c->select; }
 }  // namespace speck
 
 extern "C" {
@@ -2029,6 +2033,7 @@ int speck_config_destroy(speck_config* c)
     if (c->nfpool) (void)guarded_free(c->nfpool);
     c->sort.release();
     c->masked.release();
+    c->select.release();
     if (c->pred.off) (void)guarded_free(c->pred.off);
     if (c->gpred.off) (void)guarded_free(c->gpred.off);
     if (c->d_stats) (void)hipFree(c->d_stats);
@@ -2111,6 +2116,7 @@ int speck_config_set_option(speck_config* c, const char* name, int64_t value)
         c->spec_valid = false;
         c->sort.release();
         c->masked.release();
+        c->select.release();
     }
     else if (n == "sort_reg_max") c->sort.reg_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_REG_MAX);
     else if (n == "sort_lds_max") c->sort.lds_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_LDS_MAX);
