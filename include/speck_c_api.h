@@ -362,6 +362,52 @@ int speck_select_f64(speck_config *cfg, const speck_dcsr *A, const speck_select_
 int speck_select_f32(speck_config *cfg, const speck_dcsr *A, const speck_select_params *p, speck_dcsr *C,
                      speck_select_info *info);
 
+/* ---- addition (new: the reference has no counterpart): C = alpha A + beta B on two matrices that are already on the
+ *      device -- S + S^T (a graph symmetrised before tril and the triangle count), C + A B accumulated over several
+ *      products (Galerkin terms, the shards of a column-split product), the difference A - B of two results, alpha A alone.
+ *  SPECK_ADD_UNION is the only mode; any other flags value: SPECK_ERR_INVALID.  C(i,j) exists iff (i,j) is in A or in B --
+ *      structural, as in the multiply: an entry that cancels to 0.0 stays, and alpha == 0 or beta == 0 removes nothing and
+ *      shields nothing (0 * inf is NaN).  Rows of C strictly ascending, offsets from 0: C is a valid input of every
+ *      speck_multiply_*.
+ *  Values are computed in double for both value types T (alpha and beta are never rounded): an entry of A alone is
+ *      T(alpha a), one of B alone T(beta b), one of both T(alpha a + beta b) -- each product rounded to double, the sum
+ *      rounded to double, then once to T; no fused multiply-add.  Bit for bit alpha * a.astype(f64) + beta * b.astype(f64)
+ *      of numpy, cast to T.  Deterministic from run to run: every entry of C is written once by one thread, there are no
+ *      atomics on values.  Subnormal results are kept.
+ *  A and B under the multiply's rules for its B, checked with every call: a row of either that is not strictly ascending
+ *      or holds an id >= cols: SPECK_ERR_UNSORTED (the remedy is speck_sort_rows_*).  Offsets descending or leaving
+ *      [row_offsets[0], row_offsets[0] + nnz], rows(A) != rows(B) or cols(A) != cols(B), NULL buffers with nnz > 0, C sharing
+ *      a buffer with A or B: SPECK_ERR_INVALID.  rows, cols <= 2^27 (SPECK_ERR_DIM_LIMIT).  nnz(A) + nnz(B) >= 2^32:
+ *      SPECK_ERR_NNZ_OVERFLOW before anything runs -- conservative, an overlap might have fitted, but it is known without a
+ *      device and keeps every count in 32 bits.  A and B may be the SAME matrix, and they may be row-range views with
+ *      absolute offsets, each with its own base.
+ *  Ownership of C as speck_select_* documents it: row_offsets reused when C->rows == A->rows, data / col_ids re-allocated
+ *      only when C->nnz differs from the result's (a result of 0 entries owns buffers of one entry).  On any error the
+ *      struct, its allocations AND the contents of C are untouched.  One pass checks both inputs and marks the entries
+ *      that lie in both; it clamps and never follows an offset or id it has not checked, and every kernel that writes C
+ *      starts after the host has read its verdict (one read-back per call).  There is NO in-place A += B, for the reason
+ *      speck_select_* gives.
+ *  Runs on the config's stream (speck_config_set_stream is honoured) and returns with C complete.  Temporaries are grow-only
+ *      buffers of the config's own (not the multiply's arena: an add between two identical multiplies does not disturb the
+ *      second one's reuse sequence), released with it; cfg == NULL is allowed as for speck_sort_rows_*.  With the debug
+ *      option guard_bytes the canary zones of the temporaries and of C are checked after the call.
+ *  The marking pass walks tiles of SPECK_ADD_TILE_ROWS_LONG rows where a row of A and of B together hold
+ *      SPECK_ADD_LONG_ROW_AVG entries or more on average, of SPECK_ADD_TILE_ROWS_SHORT rows elsewhere; the pass that writes C
+ *      walks each operand in tiles of SPECK_ADD_TILE_ENTRIES entries. ---- */
+enum { SPECK_ADD_UNION = 0 };
+#define SPECK_ADD_TILE_ROWS_LONG 256
+#define SPECK_ADD_TILE_ROWS_SHORT 1024
+#define SPECK_ADD_LONG_ROW_AVG 32
+#define SPECK_ADD_TILE_ENTRIES 4096
+typedef struct speck_add_info {
+    uint64_t only_a, only_b, both;   /* entries of C that come from A alone / B alone / from both */
+    uint64_t nnz_out;                /* nnz(C) = only_a + only_b + both */
+} speck_add_info;
+int speck_add_f64(speck_config *cfg, double alpha, const speck_dcsr *A, double beta, const speck_dcsr *B, speck_dcsr *C,
+                  int flags, speck_add_info *info /* may be NULL */);
+int speck_add_f32(speck_config *cfg, double alpha, const speck_dcsr *A, double beta, const speck_dcsr *B, speck_dcsr *C,
+                  int flags, speck_add_info *info);
+
 /* ---- row-sharded multi-GPU (new: the reference is single-GPU, source/Executor.cpp:25).  One process per GPU;
  *      rank p multiplies the row range [b_p, b_{p+1}) of A (a view with absolute offsets, boundaries from
  *      speck_partition_rows) with a replicated B, then ONE exchange concatenates the shards on a root rank:

@@ -11,4 +11,5 @@ from .api import (  # noqa: F401
     multiply_masked, MaskedInfo, MASK_GROUP_MAX, MASK_LDS_MAX,
     select, tril, triu, SelectInfo, SELECT_TILE_ROWS, SELECT_LONG_ROW_AVG,
     SELECT_BAND, SELECT_ABS, SELECT_PATTERN, SELECT_NOT_BAND, SELECT_NOT_ABS, SELECT_NOT_PATTERN,
+    add, symmetrize, AddInfo, ADD_UNION, ADD_TILE_ROWS, ADD_LONG_ROW_AVG, ADD_TILE_ENTRIES,
 )

@@ -562,3 +562,52 @@ def tril(A, config, k=0):
 def triu(A, config, k=0):
     """The entries of A on and above the k-th diagonal (scipy.sparse.triu), made on the device."""
     return select(A, config, band=(k, None))[0]
+
+
+# include/speck_c_api.h: SPECK_ADD_UNION; SPECK_ADD_TILE_ROWS_LONG / _SHORT (rows per tile of the marking pass: the first
+# where a row of A and of B together hold ADD_LONG_ROW_AVG entries or more on average, the second elsewhere);
+# SPECK_ADD_TILE_ENTRIES (entries of an operand per tile of the pass that writes C)
+ADD_UNION = 0
+ADD_TILE_ROWS = (256, 1024)
+ADD_LONG_ROW_AVG = 32
+ADD_TILE_ENTRIES = 4096
+
+
+class AddInfo:
+    """speck_add_info: where the entries of the sum come from."""
+
+    def __init__(self, c):
+        self.only_a = int(c.only_a)
+        self.only_b = int(c.only_b)
+        self.both = int(c.both)
+        self.nnz_out = int(c.nnz_out)
+
+    def __repr__(self):
+        return f"AddInfo(only_a={self.only_a}, only_b={self.only_b}, both={self.both}, nnz_out={self.nnz_out})"
+
+
+def add(A, B, config, alpha=1.0, beta=1.0, matOut=None):
+    """C = alpha A + beta B on the union of the two patterns (speck_add_f64 / _f32): rows ascending, every value computed
+    in double and rounded once, an entry that cancels to 0.0 stays.  A and B have the same shape and value type and sorted
+    rows; they may be the same matrix.  config may be None.  Returns (matOut, AddInfo)."""
+    L = _lib.load()
+    if A.dtype != B.dtype:
+        raise ValueError("A and B must share a value type")
+    fn = L.speck_add_f32 if A.dtype == np.float32 else L.speck_add_f64
+    if matOut is None:
+        matOut = dCSR(A.dtype)
+    if matOut.dtype != A.dtype:
+        matOut.reset()
+        matOut.dtype = A.dtype
+    info = _lib.CAddInfo()
+    _check(fn(config._h if config is not None else None, float(alpha), C.byref(A._c), float(beta), C.byref(B._c),
+              C.byref(matOut._c), ADD_UNION, C.byref(info)), "add")
+    matOut._host_row_offsets = None  # (row_offsets were rewritten on the device)
+    return matOut, AddInfo(info)
+
+
+def symmetrize(A, config):
+    """A + A^T of a square device matrix, made on the device: add(A, transpose(A))."""
+    if A.rows != A.cols:
+        raise ValueError("symmetrize: A must be square")
+    return add(A, transpose(A, config), config)[0]

@@ -31,6 +31,7 @@
 #include "row_groups.hpp"
 #include "masked.hpp"
 #include "select.hpp"
+#include "add.hpp"
 #include "sort_rows.hpp"
 
 using namespace speck;
@@ -233,6 +234,7 @@ struct speck_config {
     SortScratch sort;  // temporaries and class limits of speck_sort_rows_* (sort_rows.hip)
     MaskedScratch masked;  // ... and of speck_multiply_masked_* (masked.hip)
     SelectScratch select;  // ... and of speck_select_* (select.hip)
+    AddScratch add;  // ... and of speck_add_* (add.hip)
     const void* zones_arena = nullptr;
     u64 zones_m = 0, zones_nnz = 0, zones_gap = 0;
     bool gpool_zones_filled = false;
@@ -1919,6 +1921,7 @@ hipStream_t call_stream(speck_config* c) { return main_stream(c); }
 MaskedScratch* masked_scratch(speck_config* c) { return &c->masked; }
 
 SelectScratch* select_scratch(speck_config* c) { return &c->select; }
+AddScratch* add_scratch(speck_config* c) { return &c->add; }
 }  // namespace speck
 
 extern "C" {
@@ -2034,6 +2037,7 @@ int speck_config_destroy(speck_config* c)
     c->sort.release();
     c->masked.release();
     c->select.release();
+    c->add.release();
     if (c->pred.off) (void)guarded_free(c->pred.off);
     if (c->gpred.off) (void)guarded_free(c->gpred.off);
     if (c->d_stats) (void)hipFree(c->d_stats);
@@ -2117,6 +2121,7 @@ int speck_config_set_option(speck_config* c, const char* name, int64_t value)
         c->sort.release();
         c->masked.release();
         c->select.release();
+        c->add.release();
     }
     else if (n == "sort_reg_max") c->sort.reg_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_REG_MAX);
     else if (n == "sort_lds_max") c->sort.lds_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_LDS_MAX);

@@ -58,6 +58,12 @@ static __global__ __launch_bounds__(1024) void scan_offsets_kernel(const F f, u3
     }
 }
 
+// the plainest F: the counts lie in an array (the filter's kept entries per row, the addition's entries of C per row)
+struct CountArray {
+    const u32* count;
+    __device__ u32 operator()(u32 i) const { return count[i]; }
+};
+
 // n >= 1 items; block_sums: (n + 1023) / 1024 words, left holding the scanned workgroup sums.  offsets_out: n + 1 words,
 // or nullptr -- the caller places the items itself, from the scanned sums (then total_out is not written either).
 template <typename F>

@@ -184,11 +184,6 @@ __global__ __launch_bounds__(kTileRows) void select_mark_kernel(const SelectArgs
     if (t == 64 && s_unchanged) atomicAdd(&g.st->unchanged, s_unchanged);
 }
 
-struct SelectRowCount {
-    const u32* row_cnt;
-    __device__ u32 operator()(u32 r) const { return row_cnt[r]; }
-};
-
 // ------------------------------------------------------------------------------------------------ host
 template <typename T>
 int select_run(SelectScratch* sc, hipStream_t s, const speck_dcsr* A, const speck_select_params* p, speck_dcsr* C,
@@ -239,7 +234,7 @@ int select_run(SelectScratch* sc, hipStream_t s, const speck_dcsr* A, const spec
         SPECK_LAUNCH((select_mark_kernel<T, kTileShort>), dim3((rows + kTileShort - 1) / kTileShort), dim3(kTileShort), 0, s, g);
     // (on a refused input the counts of a tile may be missing: the scan adds up whatever the words hold and addresses
     //  nothing through them)
-    launch_exclusive_scan(s, SelectRowCount{row_cnt}, rows, block_sums, new_ro, &st->nnz_out);
+    launch_exclusive_scan(s, CountArray{row_cnt}, rows, block_sums, new_ro, &st->nnz_out);
     SelectStatus h{};
     HIP_TRY(hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
