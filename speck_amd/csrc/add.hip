@@ -1,13 +1,13 @@
 // add.hip -- speck_add_*: C = alpha A + beta B on the union of the two patterns, rows ascending, every value computed in
 // double without a fused multiply-add and rounded once.  The reference has no counterpart.
 //
-//   add_mark_kernel    the filter's marking pass with a second operand: tiles of 256 or 1024 rows, the tile's offsets of A
-//                      and of B in LDS and checked first (monotone, inside their matrices), then a thread per entry of A and
-//                      per entry of B, four loads in flight: the entry against its predecessor in the row and against cols,
-//                      and a binary search for its column in the other operand's row, between that row's checked bounds --
-//                      no offset or id is used as an address before it was checked.  Writes one "also in the other operand"
-//                      byte and that lower bound per entry, and len A + len B - matches per row; the matches are counted
-//                      in LDS and reach the status block with one atomic per workgroup.
+//   add_mark_kernel    tiles of 256 or 1024 rows, the tile's offsets of A and of B in LDS and checked first (the offset
+//                      check: row_tiles.hpp), then a thread per entry of A and per entry of B, four loads in flight: the
+//                      entry against its predecessor in the row and against cols, and its lower bound in the other
+//                      operand's row, between that row's checked bounds -- no offset or id is used as an address before it
+//                      was checked.  Writes one "also in the other operand" byte and that lower bound per entry, and
+//                      len A + len B - matches per row; the matches are counted in LDS and reach the status block with one
+//                      atomic per workgroup.
 //   between            entries per row -> the shared scan (scan.hpp) -> the row offsets of C and nnz(C), queued behind the
 //                      marking pass (temporaries only): the host reads the verdict and nnz(C) in ONE read-back, and every
 //                      kernel that writes C starts after it.
@@ -19,8 +19,7 @@
 //                      item) + a block scan.  The lower bound is the one the marking pass stored (searching again was
 //                      measured and lost).  A matching entry of A carries alpha a + beta b, a matching entry
 //                      of B writes nothing: every place of C is written exactly once, no atomics on values.
-// The host side stands on host_common.hpp (scratch buffers, stream, error macro), compact.hpp (C's buffers, the argument
-// checks) and guards.hpp (the check after the call).
+// The host side is the side operations' own (side_call.hpp: scratch, status, the frame of the call; compact.hpp: C).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -29,7 +28,9 @@
 #include "add.hpp"
 #include "compact.hpp"
 #include "launch.hpp"
+#include "row_tiles.hpp"
 #include "scan.hpp"
+#include "side_call.hpp"
 
 using namespace speck;
 
@@ -62,15 +63,15 @@ struct AddMarkArgs {
 
 // ------------------------------------------------------------------------------------------------ check + mark
 // The entries of operand X in the tile's rows, a batch of kMarkUnroll per thread (every thread makes the same trips: the
-// waves stay whole for the ballot).  The row of an entry: first_end_beyond over the tile's offsets.  Its column is looked up
-// in Y's row between that row's checked bounds -- what Y holds there may be anything, it is compared and never followed.
+// waves stay whole for count_entry_in_row).  The row of an entry: first_end_beyond over the tile's offsets.  Its column is
+// looked up in Y's row between that row's checked bounds (lower_bound_in_row).
 // kCount (X = A): the matches per row into s_cnt.  Returns "a row of X is not strictly ascending below cols".
 template <u32 kTileRows, bool kCount>
 __device__ __forceinline__ bool add_mark_operand(const u32* __restrict__ x_col, const u32* s_xro, const u32* __restrict__ y_col,
                                                  const u32* s_yro, u32 nr, u32 cols, u32 base_x, u8* __restrict__ match,
                                                  u32* __restrict__ lbs, u32* s_cnt)
 {
-    const u32 t = threadIdx.x, lane = lane_id();
+    const u32 t = threadIdx.x;
     bool unsorted = false;
     const u64 lo = s_xro[0], hi = s_xro[nr];
     for (u64 b = lo; b < hi; b += u64(kTileRows) * kMarkUnroll) {
@@ -88,33 +89,21 @@ __device__ __forceinline__ bool add_mark_operand(const u32* __restrict__ x_col, 
             const u32 r = valid ? first_end_beyond(s_xro + 1, nr, i) : nr - 1u;  // the row of entry i (< nr: i < s_xro[nr])
             unsorted |= valid && (c[k] >= cols || (i > s_xro[r] && p[k] >= c[k]));
             // (offsets relative to y_col as they stand: absolute, checked by the caller)
-            u32 ylo = s_yro[r], yhi = valid ? s_yro[r + 1] : ylo;
-            const u32 yend = yhi;
-            while (ylo < yhi) {
-                const u32 mid = ylo + ((yhi - ylo) >> 1);
-                if (y_col[mid] < c[k]) ylo = mid + 1; else yhi = mid;
-            }
+            const u32 yend = valid ? s_yro[r + 1] : s_yro[r], ylo = lower_bound_in_row(y_col, s_yro[r], yend, c[k]);
             const bool m = ylo < yend && y_col[ylo] == c[k];
             if (valid) {
                 const u32 e = (u32)i - base_x;
                 match[e] = m ? 1 : 0;
                 lbs[e] = ylo;
             }
-            if (kCount) {
-                // a wave's entries are consecutive: where they lie in one row, one LDS atomic counts them
-                const u32 r_first = (u32)__builtin_amdgcn_readfirstlane((int)r), r_last = (u32)__builtin_amdgcn_readlane((int)r, 63);
-                if (r_first == r_last) {
-                    const u64 mm = __ballot(m);
-                    if (lane == 0 && mm) atomicAdd(&s_cnt[r_first], (u32)__popcll(mm));
-                } else if (m) atomicAdd(&s_cnt[r], 1u);
-            }
+            if (kCount) count_entry_in_row(s_cnt, r, m);
         }
     }
     return unsorted;
 }
 
 // kTileRows rows and kTileRows threads per workgroup: 1024 where rows are short, 256 where a row of A and of B together
-// hold 32 entries or more on average, as in the filter's marking pass.
+// hold 32 entries or more on average.
 template <u32 kTileRows>
 __global__ __launch_bounds__(kTileRows) void add_mark_kernel(const AddMarkArgs g)
 {
@@ -132,14 +121,10 @@ __global__ __launch_bounds__(kTileRows) void add_mark_kernel(const AddMarkArgs g
     s_cnt[t] = 0;
     if (t == 0 && blockIdx.x == 0) g.st->base_a = base_a, g.st->base_b = base_b;
     __syncthreads();
-    for (u32 i = t; i <= nr; i += kTileRows) {
-        const u32 oa = g.a_ro[r0 + i], ob = g.b_ro[r0 + i];
-        s_aro[i] = oa, s_bro[i] = ob;
-        if (oa < base_a || u64(oa - base_a) > g.a_nnz) s_bad = 1;
-        if (ob < base_b || u64(ob - base_b) > g.b_nnz) s_bad = 1;
-    }
+    tile_offsets_load<kTileRows>(g.a_ro, r0, nr, base_a, g.a_nnz, s_aro, &s_bad);
+    tile_offsets_load<kTileRows>(g.b_ro, r0, nr, base_b, g.b_nnz, s_bro, &s_bad);
     __syncthreads();
-    if (t < nr && (s_aro[t] > s_aro[t + 1] || s_bro[t] > s_bro[t + 1])) s_bad = 1;
+    if (tile_offsets_descend(s_aro, nr) || tile_offsets_descend(s_bro, nr)) s_bad = 1;
     __syncthreads();
     if (s_bad) {  // (nothing of col_ids is addressed through such offsets)
         if (t == 0) g.st->invalid = 1;
@@ -155,10 +140,7 @@ __global__ __launch_bounds__(kTileRows) void add_mark_kernel(const AddMarkArgs g
         both = s_cnt[t];
         g.row_cnt[r0 + t] = (s_aro[t + 1] - s_aro[t]) + (s_bro[t + 1] - s_bro[t]) - both;  // (both <= either length)
     }
-    both = wave_reduce_add(both);
-    if (lane_id() == 0 && both) atomicAdd(&s_both, (unsigned long long)both);
-    __syncthreads();
-    if (t == 0 && s_both) atomicAdd(&g.st->both, s_both);
+    block_counter_to(&g.st->both, both, &s_both);
 }
 
 // ------------------------------------------------------------------------------------------------ values
@@ -197,8 +179,8 @@ struct AddWriteArgs {
     T* c_val;
 };
 
-// 4096 entries of X per workgroup, four per thread, placed as compact_entries_kernel places its own.  Entry e of X (counted
-// from the first row on) in row r lands at
+// 4096 entries of X per workgroup, four per thread, numbered by the scan that compact_entries_kernel (compact.hpp) numbers
+// its own by.  Entry e of X (counted from the first row on) in row r lands at
 //     cro[r] + (its index in its row) + (its lower bound in Y's row - yro[r]) - (the matches in front of it in its row),
 // and with cro[r] = (xro[r] - xro[0]) + (yro[r] - yro[0]) - (the matches in the rows before r) every row offset cancels:
 //     place = e + (lower bound - yro[0]) - (the matches in front of it in X)
@@ -246,26 +228,13 @@ int add_run(AddScratch* sc, hipStream_t s, double alpha, const speck_dcsr* A, do
 {
     const u32 rows = (u32)A->rows;
     const u64 nnz_a = A->nnz, nnz_b = B->nnz;
-    if (rows == 0) {
-        int rc = prepare_c(C, 0, 0, sizeof(T), out);
-        if (rc != SPECK_OK) return rc;
-        HIP_TRY(hipMemsetAsync(out->ro, 0, sizeof(u32), s));
-        HIP_TRY(hipStreamSynchronize(s));
-        publish_c(C, 0, A->cols, 0, out);
-        return SPECK_OK;
-    }
+    if (rows == 0) return publish_empty_c(C, A->cols, sizeof(T), s, out);
 
     // status | entries of C per row | the row offsets of C | workgroup sums of the scan
-    const u32 nblk = (rows + 1023) / 1024;
-    const size_t row_bytes = up256((size_t(rows) + 1) * 4), sum_bytes = up256(size_t(nblk) * 4);
-    int rc = sc->fixed.ensure(256 + 2 * row_bytes + sum_bytes);
+    RowScratch<AddStatus> f;
+    int rc = carve_row_scratch(&sc->fixed, rows, 0, &f);
     if (rc != SPECK_OK) return rc;
-    unsigned char* fb = static_cast<unsigned char*>(sc->fixed.p);
-    AddStatus* st = reinterpret_cast<AddStatus*>(fb);
-    u32* row_cnt = reinterpret_cast<u32*>(fb + 256);
-    u32* new_ro = reinterpret_cast<u32*>(fb + 256 + row_bytes);
-    u32* block_sums = reinterpret_cast<u32*>(fb + 256 + 2 * row_bytes);
-    static_assert(sizeof(AddStatus) <= 256, "status block");
+    AddStatus* st = f.st;
     // per operand: match bytes | matches per tile of the write pass | lower bounds
     const u64 tiles_a = (nnz_a + kWriteTile - 1) / kWriteTile, tiles_b = (nnz_b + kWriteTile - 1) / kWriteTile;
     const size_t match_a_bytes = up256(std::max<u64>(nnz_a, 1)), match_b_bytes = up256(std::max<u64>(nnz_b, 1));
@@ -284,18 +253,17 @@ int add_run(AddScratch* sc, hipStream_t s, double alpha, const speck_dcsr* A, do
     // ---- the verdict on A and B, the marks and nnz(C): read before anything of C is written
     HIP_TRY(hipMemsetAsync(st, 0, sizeof(AddStatus), s));
     const AddMarkArgs g{A->row_offsets, A->col_ids, nnz_a, B->row_offsets, B->col_ids, nnz_b, rows, (u32)A->cols,
-                        match_a, match_b, lb_a, lb_b, row_cnt, st};
+                        match_a, match_b, lb_a, lb_b, f.row_cnt, st};
     if ((nnz_a + nnz_b) / rows >= SPECK_ADD_LONG_ROW_AVG)
         SPECK_LAUNCH((add_mark_kernel<kTileLong>), dim3((rows + kTileLong - 1) / kTileLong), dim3(kTileLong), 0, s, g);
     else
         SPECK_LAUNCH((add_mark_kernel<kTileShort>), dim3((rows + kTileShort - 1) / kTileShort), dim3(kTileShort), 0, s, g);
     // (on a refused input the counts of a tile may be missing: the scan adds up whatever the words hold and addresses
     //  nothing through them)
-    launch_exclusive_scan(s, CountArray{row_cnt}, rows, block_sums, new_ro, &st->nnz_out);
+    launch_exclusive_scan(s, CountArray{f.row_cnt}, rows, f.block_sums, f.new_ro, &st->nnz_out);
     AddStatus h{};
-    HIP_TRY(hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (take_launch_error()) return SPECK_ERR_HIP;
+    rc = read_status(s, st, &h);
+    if (rc != SPECK_OK) return rc;
     if (h.invalid) return SPECK_ERR_INVALID;
     if (h.unsorted) return SPECK_ERR_UNSORTED;
 
@@ -319,10 +287,8 @@ int add_run(AddScratch* sc, hipStream_t s, double alpha, const speck_dcsr* A, do
                                 out->col, static_cast<T*>(out->val)};
         SPECK_LAUNCH((add_write_kernel<T, false>), dim3((u32)((u64(h.entries_b) + kWriteTile - 1) / kWriteTile)), dim3(1024), 0, s, w);
     }
-    HIP_TRY(hipMemcpyAsync(out->ro, new_ro, (size_t(rows) + 1) * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (take_launch_error()) return SPECK_ERR_HIP;
-    publish_c(C, rows, A->cols, nnz_out, out);
+    rc = finish_rows(s, f.new_ro, rows, A->cols, nnz_out, C, out);
+    if (rc != SPECK_OK) return rc;
     if (info) {
         info->both = h.both;
         info->only_a = h.entries_a - h.both;
@@ -332,13 +298,7 @@ int add_run(AddScratch* sc, hipStream_t s, double alpha, const speck_dcsr* A, do
     return SPECK_OK;
 }
 
-// debug option guard_bytes: the canary zones of the temporaries and of C's buffers after the call
-int check_add_guards(const AddScratch* sc, hipStream_t s, const speck_dcsr* C, int rc)
-{
-    const void* whole[] = {sc->fixed.p, sc->var.p, C->data, C->col_ids, C->row_offsets};
-    static const char* names[] = {"add row counts", "add match bytes", "C.data", "C.col_ids", "C.row_offsets"};
-    return guard_check_buffers(whole, names, 5, s, " by the addition", rc);
-}
+const char* const kGuardNames[5] = {"add row counts", "add match bytes", "C.data", "C.col_ids", "C.row_offsets"};
 
 template <typename T>
 int add_impl(speck_config* cfg, double alpha, const speck_dcsr* A, double beta, const speck_dcsr* B, speck_dcsr* C, int flags,
@@ -354,23 +314,9 @@ int add_impl(speck_config* cfg, double alpha, const speck_dcsr* A, double beta, 
     if (shares_buffer(C, A) || shares_buffer(C, B)) return SPECK_ERR_INVALID;
     if (info) *info = speck_add_info{};
     if (!cfg && !device_present()) return SPECK_ERR_NO_DEVICE;
-    AddScratch own;
-    AddScratch* sc = cfg ? add_scratch(cfg) : &own;
-    const hipStream_t s = cfg ? call_stream(cfg) : nullptr;
-    (void)take_launch_error();
-    COut out;
-    int rc = add_run<T>(sc, s, alpha, A, beta, B, C, info, &out);
-    if (rc != SPECK_OK) {
-        (void)hipStreamSynchronize(s);
-        out.discard();  // (what was allocated for C and never handed over)
-        if (info) *info = speck_add_info{};
-    }
-    rc = check_add_guards(sc, s, C, rc);
-    if (!cfg) {
-        (void)hipStreamSynchronize(s);
-        own.release();
-    }
-    return rc;
+    return run_side_call(cfg, add_scratch, C, info, kGuardNames, " by the addition", [&](AddScratch* sc, hipStream_t s, COut* out) {
+        return add_run<T>(sc, s, alpha, A, beta, B, C, info, out);
+    });
 }
 
 }  // namespace

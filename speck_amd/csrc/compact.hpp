@@ -7,12 +7,14 @@
 //                            The values come from an array of S and go to one of T (the masked product's accumulators are
 //                            double whatever T is; the filter copies T to T, bit for bit)
 //   COut / prepare_c / publish_c   C's buffers by the multiply's rule; nothing of C changes before publish_c
+//   publish_empty_c / finish_rows / finish_subset   how a call ends: no rows; offsets copied, C published; compaction first
 //   csr_args_ok / shares_buffer    the argument checks both entry points make before anything touches a device
 #pragma once
 #include <algorithm>
 
 #include "host_common.hpp"
 #include "launch.hpp"
+#include "scan.hpp"
 
 namespace speck {
 
@@ -111,6 +113,42 @@ inline void publish_c(speck_dcsr* C, u64 rows, u64 cols, u64 nnz_out, COut* out)
     C->data = out->val, C->col_ids = out->col, C->row_offsets = out->ro;
     *out = COut{};
 }
+
+// a result without rows: one offset, 0
+inline int publish_empty_c(speck_dcsr* C, u64 cols, size_t vsize, hipStream_t s, COut* out)
+{
+    const int rc = prepare_c(C, 0, 0, vsize, out);
+    if (rc != SPECK_OK) return rc;
+    HIP_TRY(hipMemsetAsync(out->ro, 0, sizeof(u32), s));
+    HIP_TRY(hipStreamSynchronize(s));
+    publish_c(C, 0, cols, 0, out);
+    return SPECK_OK;
+}
+
+// the end of a call whose kernels (queued on `s`) fill `out`: the new row offsets copied over, the stream drained, C published
+inline int finish_rows(hipStream_t s, const u32* new_ro, u32 rows, u64 cols, u64 nnz_out, speck_dcsr* C, COut* out)
+{
+    HIP_TRY(hipMemcpyAsync(out->ro, new_ro, (size_t(rows) + 1) * 4, hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (take_launch_error()) return SPECK_ERR_HIP;
+    publish_c(C, rows, cols, nnz_out, out);
+    return SPECK_OK;
+}
+
+#ifdef __HIPCC__
+// ... that keeps a subset: the nnz_out entries of (src_col, src_val) whose keep byte is set compacted into `out` first
+template <typename S, typename T>
+int finish_subset(hipStream_t s, const KeepWord& words, u32* tile_sums, const u32* src_col, const S* src_val, const u32* new_ro,
+                  u32 rows, u64 cols, u64 nnz_out, speck_dcsr* C, COut* out)
+{
+    if (nnz_out) {
+        launch_exclusive_scan(s, words, (u32)((words.n + 3) / 4), tile_sums, nullptr, nullptr);
+        SPECK_LAUNCH((compact_entries_kernel<S, T>), dim3((u32)((words.n + kCompactTile - 1) / kCompactTile)), dim3(1024), 0, s, words,
+                     tile_sums, src_col, src_val, out->col, static_cast<T*>(out->val));
+    }
+    return finish_rows(s, new_ro, rows, cols, nnz_out, C, out);
+}
+#endif
 
 inline bool csr_args_ok(const speck_dcsr* X, bool needs_values)
 {

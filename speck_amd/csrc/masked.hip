@@ -2,9 +2,9 @@
 // reference has no counterpart.  The table a row accumulates in IS its mask row: its size is known before a product is
 // formed, it is sorted already, and a product's column is looked up with reads -- nothing is inserted, nothing is sorted.
 //
-//   masked_classify_kernel   one streaming pass over the rows: the input check of A and M (offsets monotone and inside
-//                            their matrices, ids of A < rows(B), mask rows strictly ascending and < cols(B) -- no offset
-//                            or id is used as an address before it was checked), the products of the rows with work, and
+//   masked_classify_kernel   one streaming pass over the rows: the input check of A and M (the offset check and the
+//                            mask's rows: row_tiles.hpp; ids of A < rows(B) -- no offset or id is used as an address
+//                            before it was checked), the products of the rows with work, and
 //                            those rows appended to one of seven lists by mask-row length (cursors aggregated per
 //                            workgroup).  B is checked by the multiply's own validate_b_kernel (stages.hip), behind it
 //                            on the same stream.
@@ -14,13 +14,13 @@
 //                            an open-addressed table of 16-bit positions over the row's columns, built once, probed read-only.
 //   masked_global_kernel     a workgroup per longer row: binary search in the mask row where it lies, global atomic adds.
 //   (all three walk a row's products flattened, a batch of entries of A at a time: "the product walk" below)
-//   finish                   STRUCTURE: hits per row -> the shared scan (scan.hpp) -> the new row offsets; the same scan
-//                            over the hit bytes -> one streaming compaction (compact.hpp).  FULL_PATTERN: the accumulators
+//   finish                   STRUCTURE: hits per row -> the shared scan (scan.hpp) -> the new row offsets; finish_subset
+//                            (compact.hpp): the same scan over the hit bytes -> one streaming compaction.  FULL_PATTERN: the accumulators
 //                            are C's values (fp64: accumulated in place), offsets rebased, column ids copied.
 // A hit is marked in bit 31 of the column's LDS copy (columns are < 2^27).  As in the multiply a product is rounded to T,
 // the sum is kept in double and rounded once.  Every kernel but the classifying pass starts after the host has read the
 // verdict on all three inputs; nothing of C is written before that.
-// The host side stands on host_common.hpp (scratch buffers, stream, error macro) and guards.hpp (the check after the call).
+// The host side is the side operations' own (side_call.hpp: scratch, status, the frame of the call; compact.hpp: C).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -29,7 +29,9 @@
 #include "compact.hpp"
 #include "launch.hpp"
 #include "masked.hpp"
+#include "row_tiles.hpp"
 #include "scan.hpp"
+#include "side_call.hpp"
 
 using namespace speck;
 
@@ -52,7 +54,6 @@ namespace {
 constexpr u32 kGroupMax = SPECK_MASK_GROUP_MAX, kLdsMax = SPECK_MASK_LDS_MAX;
 constexpr u32 kLdsSmall = 1024;      // LDS class: rows up to this many entries take the 256-thread launch
 constexpr u32 kHitBit = 0x80000000u, kColMask = 0x7FFFFFFFu;
-constexpr u32 kNoColumn = 0xFFFFFFFFu;  // above every column of a mask row: "no product"
 enum { LIST_G8 = 0, LIST_G16, LIST_G32, LIST_G64, LIST_LDS_S, LIST_LDS_L, LIST_GLOBAL, MASK_LISTS };
 static_assert(kGroupMax == 256 && kLdsMax <= 4096, "group widths / 16-bit table positions");
 
@@ -115,30 +116,16 @@ __global__ __launch_bounds__(kTileRows) void masked_classify_kernel(const u32* _
     s_ops[t] = 0;
     if (t == 0 && blockIdx.x == 0) st->base_m = base_m;
     __syncthreads();
-    for (u32 i = t; i <= nr; i += kTileRows) {
-        const u32 oa = a_ro[r0 + i], om = m_ro[r0 + i];
-        s_aro[i] = oa;
-        s_mro[i] = om;
-        if (oa < base_a || u64(oa - base_a) > a_nnz || om < base_m || u64(om - base_m) > m_nnz) s_bad = 1;
-    }
+    tile_offsets_load<kTileRows>(a_ro, r0, nr, base_a, a_nnz, s_aro, &s_bad);
+    tile_offsets_load<kTileRows>(m_ro, r0, nr, base_m, m_nnz, s_mro, &s_bad);
     __syncthreads();
-    if (t < nr && (s_aro[t] > s_aro[t + 1] || s_mro[t] > s_mro[t + 1])) s_bad = 1;
+    if (tile_offsets_descend(s_aro, nr) || tile_offsets_descend(s_mro, nr)) s_bad = 1;
     __syncthreads();
     if (s_bad) {  // (nothing of col_ids is addressed through such offsets)
         if (t == 0) st->invalid = 1;
         return;
     }
-    // the tile's mask entries: below cols(B), above their predecessor unless they start a row
-    bool unsorted = false;
-    {
-        const u64 lo = s_mro[0], hi = s_mro[nr];
-#pragma unroll 4
-        for (u64 i = lo + t; i < hi; i += kTileRows) {
-            const u32 c = m_col[i];
-            unsorted |= c >= b_cols;
-            if (i > lo && m_col[i - 1] >= c) unsorted |= i > s_mro[first_end_beyond(s_mro + 1, nr, i)];  // (not the first entry of its row)
-        }
-    }
+    const bool unsorted = !rows_ascending_below<kTileRows>(m_col, s_mro, nr, b_cols);
     // the tile's entries of A: below rows(B); the products they stand for, where their row has a mask row
     bool bad_a = false;
     u64 products = 0;
@@ -164,8 +151,7 @@ __global__ __launch_bounds__(kTileRows) void masked_classify_kernel(const u32* _
     if (unsorted) st->unsorted = 1;
     if (bad_a) st->invalid = 1;
     const u32 lane = lane_id();
-    products = wave_reduce_add(products);
-    if (lane == 0 && products) atomicAdd(&s_products, (unsigned long long)products);
+    wave_counter_to_lds(&s_products, products);
     int cls = -2;  // no row
     if (t < nr) {
         const u32 len = s_mro[t + 1] - s_mro[t];
@@ -202,7 +188,7 @@ __global__ __launch_bounds__(kTileRows) void masked_classify_kernel(const u32* _
     }
     if (t < MASK_LISTS && s_cnt[t]) s_first[t] = atomicAdd(&st->cnt[t], s_cnt[t]);
     if (t == MASK_LISTS && s_cnt[t]) atomicAdd(&st->idle, s_cnt[t]);
-    if (t == MASK_LISTS + 1 && s_products) atomicAdd(&st->products, s_products);
+    lds_counter_to_status(&st->products, &s_products, MASK_LISTS + 1u);
     __syncthreads();
     if (cls >= 0 && cls < MASK_LISTS) *two_sided_at(lists, rows, (u32)cls, s_first[cls] + rank) = r0 + t;
 }
@@ -215,16 +201,8 @@ __global__ __launch_bounds__(kTileRows) void masked_classify_kernel(const u32* _
 // entry of A, and no lane idles on a short row of B.  (First form: teams of eight lanes per entry of A, one entry after
 // the other -- a row of 256 entries of A cost 32 such chains, 120 us for a handful of rows of the scircuit stand-in.)
 // `end[i]`: products of the batch up to and including entry i;  `off[i]`: first entry of its B row - products before it.
-// (the entry of product p: first_end_beyond(end, nb, p), device_common.hpp)
-
-// one counter per workgroup reaches the status block (atomics of every wave on one word serialise: see the classifying pass)
-__device__ __forceinline__ void add_hits(u64 hits, unsigned long long* s_hits, MaskedStatus* st)
-{
-    hits = wave_reduce_add(hits);
-    if (lane_id() == 0 && hits) atomicAdd(s_hits, (unsigned long long)hits);
-    __syncthreads();
-    if (threadIdx.x == 0 && *s_hits) atomicAdd(&st->hits, *s_hits);
-}
+// The walk itself is walk_products (row_tiles.hpp); each class brings its `apply`: how a product's column is looked up in
+// the mask row, and where a hit is added.  The hits of a workgroup reach the status block with one atomic (block_counter_to).
 
 // ------------------------------------------------------------------------------------------------ group class
 // 256 threads = 256 / L groups; per group 4 L columns and 4 L doubles of LDS for the mask row, 2 L words and L values for
@@ -289,6 +267,7 @@ __global__ __launch_bounds__(256) void masked_group_kernel(const MaskedArgs<T> g
             //  for a search then -- cant stand-in 1.24 -> 1.47 ms, webbase triangles 0.74 -> 0.91 ms)
             auto apply = [&](u32 i, u32 j, u32 c) {
                 if (c < cmin || c > cmax) return;
+                // (not lower_bound_in_row: the words searched are LDS copies that carry the hit bit)
                 u32 lo = 0, hi = n;
                 while (lo < hi) {
                     const u32 mid = (lo + hi) >> 1;
@@ -318,20 +297,7 @@ __global__ __launch_bounds__(256) void masked_group_kernel(const MaskedArgs<T> g
                         for (u32 u = 0; u < 4; ++u) apply(i, j + u * 8u, c[u]);
                     }
                 }
-            } else {
-                for (u32 p = gl; p < total; p += 4u * L) {
-                    u32 i[4], j[4], c[4];
-#pragma unroll
-                    for (u32 u = 0; u < 4; ++u) {
-                        const u32 q = p + u * L;
-                        i[u] = q < total ? first_end_beyond(end, nb, q) : 0u;
-                        j[u] = off[i[u]] + q;
-                        c[u] = q < total ? g.b_col[j[u]] : kNoColumn;
-                    }
-#pragma unroll
-                    for (u32 u = 0; u < 4; ++u) apply(i[u], j[u], c[u]);
-                }
-            }
+            } else walk_products<L>(gl, end, off, nb, total, g.b_col, apply);
             wave_lds_fence();  // the next batch overwrites end / off
         }
         u32 cnt = 0;
@@ -350,7 +316,7 @@ __global__ __launch_bounds__(256) void masked_group_kernel(const MaskedArgs<T> g
         if (gl == 0 && g.row_cnt) g.row_cnt[row] = cnt;
         wave_lds_fence();  // the next row overwrites the slice
     }
-    add_hits(hits, &s_hits, g.st);
+    block_counter_to(&g.st->hits, hits, &s_hits);
 }
 
 // ------------------------------------------------------------------------------------------------ LDS class
@@ -435,18 +401,7 @@ __global__ __launch_bounds__(THREADS) void masked_lds_kernel(const MaskedArgs<T>
                     s = (s + 1u) & (slots - 1u);
                 }
             };
-            for (u32 p = t; p < total; p += 4u * THREADS) {
-                u32 i[4], j[4], c[4];
-#pragma unroll
-                for (u32 u = 0; u < 4; ++u) {
-                    const u32 q = p + u * THREADS;
-                    i[u] = q < total ? first_end_beyond(end, nb, q) : 0u;
-                    j[u] = off[i[u]] + q;
-                    c[u] = q < total ? g.b_col[j[u]] : kNoColumn;
-                }
-#pragma unroll
-                for (u32 u = 0; u < 4; ++u) apply(i[u], j[u], c[u]);
-            }
+            walk_products<THREADS>(t, end, off, nb, total, g.b_col, apply);
             __syncthreads();  // the next batch overwrites end / off
         }
         u32 cnt = 0;
@@ -464,7 +419,7 @@ __global__ __launch_bounds__(THREADS) void masked_lds_kernel(const MaskedArgs<T>
         __syncthreads();  // the next row overwrites the table
     }
     __syncthreads();
-    add_hits(hits, &s_hits, g.st);
+    block_counter_to(&g.st->hits, hits, &s_hits);
 }
 
 // ------------------------------------------------------------------------------------------------ global class
@@ -504,29 +459,14 @@ __global__ __launch_bounds__(1024) void masked_global_kernel(const MaskedArgs<T>
             __syncthreads();
             auto apply = [&](u32 i, u32 j, u32 c) {
                 if (c < cmin || c > cmax) return;
-                u32 lo = 0, hi = n;
-                while (lo < hi) {
-                    const u32 mid = (lo + hi) >> 1;
-                    if (mc[mid] < c) lo = mid + 1; else hi = mid;
-                }
+                const u32 lo = lower_bound_in_row(mc, 0u, n, c);
                 if (lo >= n || mc[lo] != c) return;
                 const T prod = g.a_val[ab + i] * g.b_val[j];
                 atomicAdd(&g.acc[at0 + lo], (double)prod);
                 if (g.hit) g.hit[at0 + lo] = 1;
                 ++hits;
             };
-            for (u32 p = t; p < total; p += 4u * THREADS) {
-                u32 i[4], j[4], c[4];
-#pragma unroll
-                for (u32 u = 0; u < 4; ++u) {
-                    const u32 q = p + u * THREADS;
-                    i[u] = q < total ? first_end_beyond(s_end, nb, q) : 0u;
-                    j[u] = s_off[i[u]] + q;
-                    c[u] = q < total ? g.b_col[j[u]] : kNoColumn;
-                }
-#pragma unroll
-                for (u32 u = 0; u < 4; ++u) apply(i[u], j[u], c[u]);
-            }
+            walk_products<THREADS>(t, s_end, s_off, nb, total, g.b_col, apply);
             __syncthreads();  // the next batch overwrites end / off
         }
         if (g.row_cnt) {
@@ -539,18 +479,12 @@ __global__ __launch_bounds__(1024) void masked_global_kernel(const MaskedArgs<T>
         }
     }
     __syncthreads();
-    add_hits(hits, &s_hits, g.st);
+    block_counter_to(&g.st->hits, hits, &s_hits);
 }
 
 // ------------------------------------------------------------------------------------------------ finish
-// STRUCTURE: hits per row -> the shared exclusive scan (scan.hpp): the new row offsets, nnz(C) into the status block.
-struct MaskedRowCount {
-    const u32* row_cnt;
-    __device__ u32 operator()(u32 r) const { return row_cnt[r]; }
-};
-
-// The compaction needs no rows: C's entries are M's entries with a hit, in M's order -- KeepWord over the hit bytes and
-// compact_entries_kernel (compact.hpp), from the accumulators (double) to C's values (T).
+// STRUCTURE: hits per row -> the shared exclusive scan (scan.hpp): the new row offsets, nnz(C) into the status block.  C's
+// entries are M's entries with a hit, in M's order: finish_subset (compact.hpp), from the accumulators (double) to T.
 
 // FULL_PATTERN: C.row_offsets = M.row_offsets rebased to 0; the values rounded where the accumulators are not C's own
 __global__ __launch_bounds__(256) void masked_rebase_kernel(const u32* __restrict__ m_ro, u32 rows, u32* __restrict__ c_ro)
@@ -571,35 +505,20 @@ __global__ __launch_bounds__(256) void masked_round_kernel(const double* __restr
 // dynamic LDS of the LDS class: accumulators | columns | table | batch
 constexpr u32 lds_bytes(u32 cap, u32 threads) { return cap * 16u + threads * 8u; }
 
-// (C's buffers by the multiply's rule: COut, prepare_c, publish_c -- compact.hpp)
-
 template <typename T>
 int masked_run(MaskedScratch* sc, hipStream_t s, const speck_dcsr* A, const speck_dcsr* B, const speck_dcsr* M, speck_dcsr* C,
                bool full, speck_masked_info* info, COut* out)
 {
     const u32 rows = (u32)A->rows;
     const u64 nnz_m = M->nnz;
-    if (rows == 0) {
-        int rc = prepare_c(C, 0, 0, sizeof(T), out);
-        if (rc != SPECK_OK) return rc;
-        HIP_TRY(hipMemsetAsync(out->ro, 0, sizeof(u32), s));
-        HIP_TRY(hipStreamSynchronize(s));
-        publish_c(C, 0, B->cols, 0, out);
-        return SPECK_OK;
-    }
+    if (rows == 0) return publish_empty_c(C, B->cols, sizeof(T), s, out);
 
     // status | lists (four regions of `rows` words) | hits per row | new row offsets | workgroup sums of the scan
-    const u32 nblk = (rows + 1023) / 1024;
-    const size_t list_bytes = up256(size_t(4) * rows * 4), row_bytes = up256((size_t(rows) + 1) * 4), sum_bytes = up256(size_t(nblk) * 4);
-    int rc = sc->fixed.ensure(256 + list_bytes + 2 * row_bytes + sum_bytes);
+    RowScratch<MaskedStatus> f;
+    int rc = carve_row_scratch(&sc->fixed, rows, size_t(4) * rows, &f);
     if (rc != SPECK_OK) return rc;
-    unsigned char* fb = static_cast<unsigned char*>(sc->fixed.p);
-    MaskedStatus* st = reinterpret_cast<MaskedStatus*>(fb);
-    u32* lists = reinterpret_cast<u32*>(fb + 256);
-    u32* row_cnt = reinterpret_cast<u32*>(fb + 256 + list_bytes);
-    u32* new_ro = reinterpret_cast<u32*>(fb + 256 + list_bytes + row_bytes);
-    u32* block_sums = reinterpret_cast<u32*>(fb + 256 + list_bytes + 2 * row_bytes);
-    static_assert(sizeof(MaskedStatus) <= 256, "status block");
+    MaskedStatus* st = f.st;
+    u32 *lists = f.lists, *row_cnt = f.row_cnt;
     // accumulators | hit bytes | hits per tile of the compaction
     const bool acc_in_c = full && std::is_same<T, double>::value;
     const u32 ntiles = (u32)((nnz_m + kCompactTile - 1) / kCompactTile);
@@ -613,19 +532,19 @@ int masked_run(MaskedScratch* sc, hipStream_t s, const speck_dcsr* A, const spec
 
     // ---- the verdict on A, M (this file) and B (the multiply's check), read before anything else starts
     HIP_TRY(hipMemsetAsync(st, 0, sizeof(MaskedStatus), s));
-    if ((A->nnz + nnz_m) / rows >= 32)
-        SPECK_LAUNCH(masked_classify_kernel<256>, dim3((rows + 255) / 256), dim3(256), 0, s, A->row_offsets, A->col_ids, A->nnz,
+    constexpr u32 kTL = kMaskTileRowsLong, kTS = kMaskTileRowsShort;  // (below: the tile of long rows, of short rows)
+    if ((A->nnz + nnz_m) / rows >= kMaskLongRowAvg)
+        SPECK_LAUNCH(masked_classify_kernel<kTL>, dim3((rows + kTL - 1) / kTL), dim3(kTL), 0, s, A->row_offsets, A->col_ids, A->nnz,
                      B->row_offsets, (u32)B->rows, (u32)B->cols, B->nnz, M->row_offsets, M->col_ids, nnz_m, rows, sc->group_max,
                      sc->lds_max, lists, st);
     else
-        SPECK_LAUNCH(masked_classify_kernel<1024>, dim3((rows + 1023) / 1024), dim3(1024), 0, s, A->row_offsets, A->col_ids, A->nnz,
+        SPECK_LAUNCH(masked_classify_kernel<kTS>, dim3((rows + kTS - 1) / kTS), dim3(kTS), 0, s, A->row_offsets, A->col_ids, A->nnz,
                      B->row_offsets, (u32)B->rows, (u32)B->cols, B->nnz, M->row_offsets, M->col_ids, nnz_m, rows, sc->group_max,
                      sc->lds_max, lists, st);
     launch_validate_b(s, B->row_offsets, B->col_ids, (u32)B->rows, (u32)B->cols, B->nnz, &st->verdict_b);
     MaskedStatus h{};
-    HIP_TRY(hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (take_launch_error()) return SPECK_ERR_HIP;
+    rc = read_status(s, st, &h);
+    if (rc != SPECK_OK) return rc;
     if (h.invalid) return SPECK_ERR_INVALID;
     if (h.unsorted || (h.verdict_b & 4u)) return SPECK_ERR_UNSORTED;
     if (h.too_many) return SPECK_ERR_DIM_LIMIT;
@@ -692,22 +611,17 @@ int masked_run(MaskedScratch* sc, hipStream_t s, const speck_dcsr* A, const spec
 
     // ---- finish
     u64 nnz_out = nnz_m;
-    if (!full) launch_exclusive_scan(s, MaskedRowCount{row_cnt}, rows, block_sums, new_ro, &st->nnz_out);
-    HIP_TRY(hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (take_launch_error()) return SPECK_ERR_HIP;
+    if (!full) launch_exclusive_scan(s, CountArray{row_cnt}, rows, f.block_sums, f.new_ro, &st->nnz_out);
+    rc = read_status(s, st, &h);
+    if (rc != SPECK_OK) return rc;
     if (!full) {
         nnz_out = h.nnz_out;
         rc = prepare_c(C, rows, nnz_out, sizeof(T), out);
         if (rc != SPECK_OK) return rc;
-        if (nnz_out) {
-            const KeepWord words{reinterpret_cast<const u32*>(hit), nnz_m};
-            u32* tile_sums = reinterpret_cast<u32*>(vb + acc_bytes + hit_bytes);
-            launch_exclusive_scan(s, words, (u32)((nnz_m + 3) / 4), tile_sums, nullptr, nullptr);
-            SPECK_LAUNCH((compact_entries_kernel<double, T>), dim3(ntiles), dim3(1024), 0, s, words, tile_sums, M->col_ids + h.base_m, acc,
-                         out->col, static_cast<T*>(out->val));
-        }
-        HIP_TRY(hipMemcpyAsync(out->ro, new_ro, (size_t(rows) + 1) * 4, hipMemcpyDeviceToDevice, s));
+        const KeepWord words{reinterpret_cast<const u32*>(hit), nnz_m};
+        rc = finish_subset<double, T>(s, words, reinterpret_cast<u32*>(vb + acc_bytes + hit_bytes), M->col_ids + h.base_m, acc,
+                                      f.new_ro, rows, B->cols, nnz_out, C, out);
+        if (rc != SPECK_OK) return rc;
     } else {
         SPECK_LAUNCH(masked_rebase_kernel, dim3(grid_of((u64(rows) + 256) / 256, 4096)), dim3(256), 0, s, M->row_offsets, rows, out->ro);
         if (nnz_m) {
@@ -716,10 +630,10 @@ int masked_run(MaskedScratch* sc, hipStream_t s, const speck_dcsr* A, const spec
                 SPECK_LAUNCH(masked_round_kernel<T>, dim3(grid_of((nnz_m + 255) / 256, 8192)), dim3(256), 0, s, acc, nnz_m,
                              static_cast<T*>(out->val));
         }
+        HIP_TRY(hipStreamSynchronize(s));
+        if (take_launch_error()) return SPECK_ERR_HIP;
+        publish_c(C, rows, B->cols, nnz_out, out);
     }
-    HIP_TRY(hipStreamSynchronize(s));
-    if (take_launch_error()) return SPECK_ERR_HIP;
-    publish_c(C, rows, B->cols, nnz_out, out);
     if (info) {
         info->rows_idle = h.idle;
         info->rows_class[0] = u64(h.cnt[LIST_G8]) + h.cnt[LIST_G16] + h.cnt[LIST_G32] + h.cnt[LIST_G64];
@@ -732,13 +646,7 @@ int masked_run(MaskedScratch* sc, hipStream_t s, const speck_dcsr* A, const spec
     return SPECK_OK;
 }
 
-// debug option guard_bytes: the canary zones of the temporaries and of C's buffers after the call
-int check_masked_guards(const MaskedScratch* sc, hipStream_t s, const speck_dcsr* C, int rc)
-{
-    const void* whole[] = {sc->fixed.p, sc->var.p, C->data, C->col_ids, C->row_offsets};
-    static const char* names[] = {"masked lists", "masked accumulators", "C.data", "C.col_ids", "C.row_offsets"};
-    return guard_check_buffers(whole, names, 5, s, " by the masked product", rc);
-}
+const char* const kGuardNames[5] = {"masked lists", "masked accumulators", "C.data", "C.col_ids", "C.row_offsets"};
 
 template <typename T>
 int masked_impl(speck_config* cfg, const speck_dcsr* A, const speck_dcsr* B, const speck_dcsr* M, speck_dcsr* C, int flags,
@@ -753,23 +661,10 @@ int masked_impl(speck_config* cfg, const speck_dcsr* A, const speck_dcsr* B, con
     if (shares_buffer(C, A) || shares_buffer(C, B) || shares_buffer(C, M)) return SPECK_ERR_INVALID;
     if (info) *info = speck_masked_info{};
     if (!cfg && !device_present()) return SPECK_ERR_NO_DEVICE;
-    MaskedScratch own;
-    MaskedScratch* sc = cfg ? masked_scratch(cfg) : &own;
-    const hipStream_t s = cfg ? call_stream(cfg) : nullptr;
-    (void)take_launch_error();
-    COut out;
-    int rc = masked_run<T>(sc, s, A, B, M, C, flags == SPECK_MASK_FULL_PATTERN, info, &out);
-    if (rc != SPECK_OK) {
-        (void)hipStreamSynchronize(s);
-        out.discard();  // (what was allocated for C and never handed over)
-        if (info) *info = speck_masked_info{};
-    }
-    rc = check_masked_guards(sc, s, C, rc);
-    if (!cfg) {
-        (void)hipStreamSynchronize(s);
-        own.release();
-    }
-    return rc;
+    return run_side_call(cfg, masked_scratch, C, info, kGuardNames, " by the masked product",
+                         [&](MaskedScratch* sc, hipStream_t s, COut* out) {
+                             return masked_run<T>(sc, s, A, B, M, C, flags == SPECK_MASK_FULL_PATTERN, info, out);
+                         });
 }
 
 }  // namespace

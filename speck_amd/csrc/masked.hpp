@@ -21,5 +21,7 @@ struct MaskedScratch {
 };
 
 MaskedScratch* masked_scratch(speck_config* c);
+// rows per tile of the classifying pass: the first where a row of A and of M together hold kMaskLongRowAvg entries or more
+constexpr u32 kMaskTileRowsLong = 256, kMaskTileRowsShort = 1024, kMaskLongRowAvg = 32;
 
 }  // namespace speck

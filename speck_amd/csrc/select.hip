@@ -3,18 +3,18 @@
 // bit for bit.  The reference has no counterpart.
 //
 //   select_mark_kernel   one streaming pass over the rows, tiles of 256 or 1024 rows with the tile's offsets in LDS and a
-//                        thread per entry, four loads in flight: the input check of A and of the pattern (offsets monotone
-//                        and inside their matrices, ids of A < cols, pattern rows strictly ascending and < cols -- no
-//                        offset or id is used as an address before it was checked) and the predicates.  Writes one keep
-//                        byte per entry and the kept entries per row; `kept` and `rows_unchanged` are counted in LDS and
-//                        reach the status block with one atomic per workgroup and counter.  The predicates are uniform
-//                        branches on the flags: a call that does not select ABS never loads a value, one that does not
-//                        select PATTERN never touches a pattern.
-//   finish               the masked product's: kept per row -> the shared scan (scan.hpp) -> the new row offsets and the
-//                        total; the same scan over the keep bytes -> one streaming compaction (compact.hpp).
+//                        thread per entry, four loads in flight: the input check of A and of the pattern (the offset
+//                        check and the pattern's rows: row_tiles.hpp; ids of A < cols -- no offset or id is used as an
+//                        address before it was checked) and the predicates.  Writes one keep byte per entry and the kept
+//                        entries per row; `kept` and `rows_unchanged` are counted in LDS and reach the status block with
+//                        one atomic per workgroup and counter.  The predicates are uniform branches on the flags: a call
+//                        that does not select ABS never loads a value, one that does not select PATTERN never touches a
+//                        pattern.
+//   finish               kept per row -> the shared scan (scan.hpp) -> the new row offsets and the total; finish_subset
+//                        (compact.hpp): the same scan over the keep bytes -> one streaming compaction.
 // The scan over the rows is queued behind the marking pass -- it writes temporaries only --, so the host reads the verdict
 // and nnz(C) in ONE read-back; every kernel that writes C starts after it.
-// The host side stands on host_common.hpp (scratch buffers, stream, error macro) and guards.hpp (the check after the call).
+// The host side is the side operations' own (side_call.hpp: scratch, status, the frame of the call; compact.hpp: C).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,8 +23,10 @@
 
 #include "compact.hpp"
 #include "launch.hpp"
+#include "row_tiles.hpp"
 #include "scan.hpp"
 #include "select.hpp"
+#include "side_call.hpp"
 
 using namespace speck;
 
@@ -63,9 +65,8 @@ struct SelectArgs {
 // ------------------------------------------------------------------------------------------------ check + mark
 // kTileRows rows and kTileRows threads per workgroup: 1024 where rows are short, 256 where a row holds 32 entries or more
 // on average (a tile should hold enough entries to pay for its barriers, and there should be enough tiles for the
-// machine), as in the masked product's classifying pass.  The row of an entry: first_end_beyond over the tile's offsets.
-// A PATTERN entry looks its column up in the pattern's row by binary search between that row's checked bounds: A's row
-// needs no order for it, and a long pattern row costs log2 dependent loads that hit L2.
+// machine).  The row of an entry: first_end_beyond over the tile's offsets.  A PATTERN entry looks its column up in the
+// pattern's row between that row's checked bounds (lower_bound_in_row): A's row needs no order for it.
 template <typename T, u32 kTileRows>
 __global__ __launch_bounds__(kTileRows) void select_mark_kernel(const SelectArgs<T> g)
 {
@@ -86,40 +87,20 @@ __global__ __launch_bounds__(kTileRows) void select_mark_kernel(const SelectArgs
     s_cnt[t] = 0;
     if (t == 0 && blockIdx.x == 0) g.st->base_a = base_a;
     __syncthreads();
-    for (u32 i = t; i <= nr; i += kTileRows) {
-        const u32 oa = g.a_ro[r0 + i];
-        s_aro[i] = oa;
-        if (oa < base_a || u64(oa - base_a) > g.a_nnz) s_bad = 1;
-        if (pat) {
-            const u32 op = g.p_ro[r0 + i];
-            s_pro[i] = op;
-            if (op < base_p || u64(op - base_p) > g.p_nnz) s_bad = 1;
-        }
-    }
+    tile_offsets_load<kTileRows>(g.a_ro, r0, nr, base_a, g.a_nnz, s_aro, &s_bad);
+    if (pat) tile_offsets_load<kTileRows>(g.p_ro, r0, nr, base_p, g.p_nnz, s_pro, &s_bad);
     __syncthreads();
-    if (t < nr && (s_aro[t] > s_aro[t + 1] || (pat && s_pro[t] > s_pro[t + 1]))) s_bad = 1;
+    if (tile_offsets_descend(s_aro, nr) || (pat && tile_offsets_descend(s_pro, nr))) s_bad = 1;
     __syncthreads();
     if (s_bad) {  // (nothing of col_ids is addressed through such offsets)
         if (t == 0) g.st->invalid = 1;
         return;
     }
     if (t == 0 && r0 + nr == g.rows) g.st->entries = s_aro[nr] - base_a;
-    // the tile's pattern entries: below cols, above their predecessor unless they start a row
-    if (pat) {
-        bool unsorted = false;
-        const u64 lo = s_pro[0], hi = s_pro[nr];
-#pragma unroll 4
-        for (u64 i = lo + t; i < hi; i += kTileRows) {
-            const u32 c = g.p_col[i];
-            unsorted |= c >= g.cols;
-            if (i > lo && g.p_col[i - 1] >= c) unsorted |= i > s_pro[first_end_beyond(s_pro + 1, nr, i)];  // (not the first entry of its row)
-        }
-        if (unsorted) g.st->unsorted = 1;
-    }
+    if (pat && !rows_ascending_below<kTileRows>(g.p_col, s_pro, nr, g.cols)) g.st->unsorted = 1;
     // the tile's entries of A, a batch of kMarkUnroll per thread (every thread makes the same trips: the waves stay whole
-    // for the ballot below)
+    // for count_entry_in_row)
     bool bad_a = false;
-    const u32 lane = lane_id();
     const u64 lo = s_aro[0], hi = s_aro[nr];
     for (u64 b = lo; b < hi; b += u64(kTileRows) * kMarkUnroll) {
         u32 c[kMarkUnroll];
@@ -146,22 +127,12 @@ __global__ __launch_bounds__(kTileRows) void select_mark_kernel(const SelectArgs
             if (mag) keep &= !(fabs((double)v[k]) <= g.threshold) != not_mag;
             if (pat && keep) {
                 // (offsets relative to p_col as they stand: absolute, checked above)
-                u32 plo = s_pro[r], phi = s_pro[r + 1];
-                const u32 pend = phi;
-                while (plo < phi) {
-                    const u32 mid = plo + ((phi - plo) >> 1);
-                    if (g.p_col[mid] < c[k]) plo = mid + 1; else phi = mid;
-                }
-                const bool in = plo < pend && g.p_col[plo] == c[k];
+                const u32 pend = s_pro[r + 1], at = lower_bound_in_row(g.p_col, s_pro[r], pend, c[k]);
+                const bool in = at < pend && g.p_col[at] == c[k];
                 keep = in != not_pat;
             }
             if (valid) g.keep[i - base_a] = keep ? 1 : 0;
-            // a wave's entries are consecutive: where they lie in one row, one LDS atomic counts them
-            const u32 r_first = (u32)__builtin_amdgcn_readfirstlane((int)r), r_last = (u32)__builtin_amdgcn_readlane((int)r, 63);
-            if (r_first == r_last) {
-                const u64 m = __ballot(keep);
-                if (lane == 0 && m) atomicAdd(&s_cnt[r_first], (u32)__popcll(m));
-            } else if (keep) atomicAdd(&s_cnt[r], 1u);
+            count_entry_in_row(s_cnt, r, keep);
         }
     }
     if (bad_a) g.st->invalid = 1;
@@ -173,15 +144,12 @@ __global__ __launch_bounds__(kTileRows) void select_mark_kernel(const SelectArgs
         g.row_cnt[r0 + t] = cnt;
         same = cnt == s_aro[t + 1] - s_aro[t];
     }
-    const u64 m = __ballot(same);
-    cnt = wave_reduce_add(cnt);
-    if (lane == 0) {
-        if (cnt) atomicAdd(&s_kept, (unsigned long long)cnt);
-        if (m) atomicAdd(&s_unchanged, (u32)__popcll(m));
-    }
+    const u64 m = __ballot(same);  // (a flag per row: counted from the ballot, not summed)
+    if (lane_id() == 0 && m) atomicAdd(&s_unchanged, (u32)__popcll(m));
+    wave_counter_to_lds(&s_kept, cnt);
     __syncthreads();
-    if (t == 0 && s_kept) atomicAdd(&g.st->kept, s_kept);
-    if (t == 64 && s_unchanged) atomicAdd(&g.st->unchanged, s_unchanged);
+    lds_counter_to_status(&g.st->kept, &s_kept, 0u);
+    lds_counter_to_status(&g.st->unchanged, &s_unchanged, 64u);  // (another wave's thread: the two atomics leave side by side)
 }
 
 // ------------------------------------------------------------------------------------------------ host
@@ -192,26 +160,13 @@ int select_run(SelectScratch* sc, hipStream_t s, const speck_dcsr* A, const spec
     const u32 rows = (u32)A->rows;
     const u64 nnz = A->nnz;
     const bool pat = p->flags & SPECK_SELECT_PATTERN;
-    if (rows == 0) {
-        int rc = prepare_c(C, 0, 0, sizeof(T), out);
-        if (rc != SPECK_OK) return rc;
-        HIP_TRY(hipMemsetAsync(out->ro, 0, sizeof(u32), s));
-        HIP_TRY(hipStreamSynchronize(s));
-        publish_c(C, 0, A->cols, 0, out);
-        return SPECK_OK;
-    }
+    if (rows == 0) return publish_empty_c(C, A->cols, sizeof(T), s, out);
 
     // status | kept per row | new row offsets | workgroup sums of the scan
-    const u32 nblk = (rows + 1023) / 1024;
-    const size_t row_bytes = up256((size_t(rows) + 1) * 4), sum_bytes = up256(size_t(nblk) * 4);
-    int rc = sc->fixed.ensure(256 + 2 * row_bytes + sum_bytes);
+    RowScratch<SelectStatus> f;
+    int rc = carve_row_scratch(&sc->fixed, rows, 0, &f);
     if (rc != SPECK_OK) return rc;
-    unsigned char* fb = static_cast<unsigned char*>(sc->fixed.p);
-    SelectStatus* st = reinterpret_cast<SelectStatus*>(fb);
-    u32* row_cnt = reinterpret_cast<u32*>(fb + 256);
-    u32* new_ro = reinterpret_cast<u32*>(fb + 256 + row_bytes);
-    u32* block_sums = reinterpret_cast<u32*>(fb + 256 + 2 * row_bytes);
-    static_assert(sizeof(SelectStatus) <= 256, "status block");
+    SelectStatus* st = f.st;
     // keep bytes | kept entries per tile of the compaction
     const size_t keep_bytes = up256(std::max<u64>(nnz, 1));
     const size_t tile_bytes = up256(size_t(std::max<u64>((nnz + kCompactTile - 1) / kCompactTile, 1)) * 4);
@@ -227,18 +182,17 @@ int select_run(SelectScratch* sc, hipStream_t s, const speck_dcsr* A, const spec
     const SelectArgs<T> g{A->row_offsets, A->col_ids, static_cast<const T*>(A->data), nnz,
                           P ? P->row_offsets : nullptr, P ? P->col_ids : nullptr, P ? P->nnz : 0, rows, (u32)A->cols,
                           p->flags, (long long)p->band_lo, (long long)p->band_hi, p->row_base, p->abs_threshold, keep,
-                          row_cnt, st};
+                          f.row_cnt, st};
     if ((nnz + (P ? P->nnz : 0)) / rows >= SPECK_SELECT_LONG_ROW_AVG)
         SPECK_LAUNCH((select_mark_kernel<T, kTileLong>), dim3((rows + kTileLong - 1) / kTileLong), dim3(kTileLong), 0, s, g);
     else
         SPECK_LAUNCH((select_mark_kernel<T, kTileShort>), dim3((rows + kTileShort - 1) / kTileShort), dim3(kTileShort), 0, s, g);
     // (on a refused input the counts of a tile may be missing: the scan adds up whatever the words hold and addresses
     //  nothing through them)
-    launch_exclusive_scan(s, CountArray{row_cnt}, rows, block_sums, new_ro, &st->nnz_out);
+    launch_exclusive_scan(s, CountArray{f.row_cnt}, rows, f.block_sums, f.new_ro, &st->nnz_out);
     SelectStatus h{};
-    HIP_TRY(hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (take_launch_error()) return SPECK_ERR_HIP;
+    rc = read_status(s, st, &h);
+    if (rc != SPECK_OK) return rc;
     if (h.invalid) return SPECK_ERR_INVALID;
     if (h.unsorted) return SPECK_ERR_UNSORTED;
 
@@ -246,18 +200,11 @@ int select_run(SelectScratch* sc, hipStream_t s, const speck_dcsr* A, const spec
     const u64 nnz_out = h.nnz_out;
     rc = prepare_c(C, rows, nnz_out, sizeof(T), out);
     if (rc != SPECK_OK) return rc;
-    if (nnz_out) {
-        // (h.entries <= nnz, checked by the pass: entries of the buffers behind the last row have no keep byte)
-        const u64 entries = h.entries;
-        const KeepWord words{reinterpret_cast<const u32*>(keep), entries};
-        launch_exclusive_scan(s, words, (u32)((entries + 3) / 4), tile_sums, nullptr, nullptr);
-        SPECK_LAUNCH((compact_entries_kernel<T, T>), dim3((u32)((entries + kCompactTile - 1) / kCompactTile)), dim3(1024), 0, s, words, tile_sums, A->col_ids + h.base_a,
-                     static_cast<const T*>(A->data) + h.base_a, out->col, static_cast<T*>(out->val));
-    }
-    HIP_TRY(hipMemcpyAsync(out->ro, new_ro, (size_t(rows) + 1) * 4, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (take_launch_error()) return SPECK_ERR_HIP;
-    publish_c(C, rows, A->cols, nnz_out, out);
+    // (h.entries <= nnz, checked by the pass: entries of the buffers behind the last row have no keep byte)
+    const KeepWord words{reinterpret_cast<const u32*>(keep), h.entries};
+    rc = finish_subset<T, T>(s, words, tile_sums, A->col_ids + h.base_a, static_cast<const T*>(A->data) + h.base_a, f.new_ro, rows,
+                             A->cols, nnz_out, C, out);
+    if (rc != SPECK_OK) return rc;
     if (info) {
         info->kept = h.kept;
         info->dropped = h.entries - h.kept;
@@ -267,13 +214,7 @@ int select_run(SelectScratch* sc, hipStream_t s, const speck_dcsr* A, const spec
     return SPECK_OK;
 }
 
-// debug option guard_bytes: the canary zones of the temporaries and of C's buffers after the call
-int check_select_guards(const SelectScratch* sc, hipStream_t s, const speck_dcsr* C, int rc)
-{
-    const void* whole[] = {sc->fixed.p, sc->var.p, C->data, C->col_ids, C->row_offsets};
-    static const char* names[] = {"select row counts", "select keep bytes", "C.data", "C.col_ids", "C.row_offsets"};
-    return guard_check_buffers(whole, names, 5, s, " by the select", rc);
-}
+const char* const kGuardNames[5] = {"select row counts", "select keep bytes", "C.data", "C.col_ids", "C.row_offsets"};
 
 template <typename T>
 int select_impl(speck_config* cfg, const speck_dcsr* A, const speck_select_params* p, speck_dcsr* C, speck_select_info* info)
@@ -292,23 +233,8 @@ int select_impl(speck_config* cfg, const speck_dcsr* A, const speck_select_param
     if (shares_buffer(C, A) || (P && shares_buffer(C, P))) return SPECK_ERR_INVALID;
     if (info) *info = speck_select_info{};
     if (!cfg && !device_present()) return SPECK_ERR_NO_DEVICE;
-    SelectScratch own;
-    SelectScratch* sc = cfg ? select_scratch(cfg) : &own;
-    const hipStream_t s = cfg ? call_stream(cfg) : nullptr;
-    (void)take_launch_error();
-    COut out;
-    int rc = select_run<T>(sc, s, A, p, C, info, &out);
-    if (rc != SPECK_OK) {
-        (void)hipStreamSynchronize(s);
-        out.discard();  // (what was allocated for C and never handed over)
-        if (info) *info = speck_select_info{};
-    }
-    rc = check_select_guards(sc, s, C, rc);
-    if (!cfg) {
-        (void)hipStreamSynchronize(s);
-        own.release();
-    }
-    return rc;
+    return run_side_call(cfg, select_scratch, C, info, kGuardNames, " by the select",
+                         [&](SelectScratch* sc, hipStream_t s, COut* out) { return select_run<T>(sc, s, A, p, C, info, out); });
 }
 
 }  // namespace

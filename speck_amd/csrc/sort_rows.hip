@@ -2,10 +2,10 @@
 // equal columns merged.  What makes a matrix that was produced ON the device acceptable to speck_multiply_* (whose input
 // check wants strictly ascending rows).  The reference has no counterpart: its host loader sorts (source/CSR.cpp:173-212).
 //
-//   sort_classify_kernel   one streaming pass over row_offsets and col_ids: the input check (offsets monotone and inside
-//                          the matrix, columns < cols -- every address clamped before it is used) and, per row, "strictly
-//                          ascending?".  Rows that are pass no further; the others go to one of six lists by length
-//                          (wave-aggregated atomic cursors: the order inside a list does not matter).
+//   sort_classify_kernel   one streaming pass over row_offsets and col_ids: the input check (the offset check:
+//                          row_tiles.hpp; columns < cols -- no offset is used as an address before it was checked) and,
+//                          per row, "strictly ascending?".  Rows that are pass no further; the others go to one of six
+//                          lists by length (wave-aggregated atomic cursors: the order inside a list does not matter).
 //   sort_reg_kernel<L>     rows of <= 4 L entries, L = 8 / 16 / 32 / 64 lanes per row: the sorting networks of esc.hpp /
 //                          esc_wide.hpp on keys (column - smallest column of the row) << 8 | position.  The position makes
 //                          the sort stable and gathers the value (staged in LDS by position).  A row whose column range
@@ -16,7 +16,8 @@
 //                          transpose's radix_scatter_kernel, tiles taken in order) between the row and a temporary.
 //   compaction             (SUM_DUPLICATES, when a row shrank) row lengths minus duplicates -> the shared scan
 //                          (scan.hpp) -> the runs summed in double while the rows move to a temporary -> copied back.
-// The host side stands on host_common.hpp (scratch buffers, stream, error macro) and guards.hpp (the check after the call).
+// The host side stands on host_common.hpp and side_call.hpp (the status read-back, the guard check after the call); the
+// frame of the call is its own: M is sorted in place, no C is handed over, and a refused call keeps what it told `info`.
 // Every kernel that writes M starts after the host has read the verdict of the classifying pass.
 #include <hip/hip_runtime.h>
 
@@ -25,7 +26,9 @@
 #include "esc.hpp"
 #include "esc_wide.hpp"
 #include "launch.hpp"
+#include "row_tiles.hpp"
 #include "scan.hpp"
+#include "side_call.hpp"
 #include "sort_rows.hpp"
 
 using namespace speck;
@@ -75,13 +78,9 @@ __global__ __launch_bounds__(kClassifyThreads) void sort_classify_kernel(const u
     if (t == 0 && blockIdx.x == 0) st->base = base;
     if (t < kTileRows) s_flag[t] = 0;
     __syncthreads();
-    for (u32 i = t; i <= nr; i += kClassifyThreads) {
-        const u32 o = ro[r0 + i];
-        s_ro[i] = o;
-        if (o < base || u64(o - base) > nnz) s_bad = 1;
-    }
+    tile_offsets_load<kClassifyThreads>(ro, r0, nr, base, nnz, s_ro, &s_bad);
     __syncthreads();
-    if (t < nr && s_ro[t] > s_ro[t + 1]) s_bad = 1;
+    if (tile_offsets_descend(s_ro, nr)) s_bad = 1;
     __syncthreads();
     if (s_bad) {  // (nothing of col_ids is addressed through such offsets)
         if (t == 0) st->invalid = 1;
@@ -491,16 +490,15 @@ int sort_rows_run(SortScratch* sc, hipStream_t s, speck_dcsr* M, int flags, spec
     static_assert(sizeof(SortStatus) <= 256, "status block");
 
     HIP_TRY(hipMemsetAsync(st, 0, sizeof(SortStatus), s));
-    if (nnz / rows >= 64 || rows < (1u << 19))  // (measured: the scircuit stand-in's 171 k short rows want the small tile too)
-        SPECK_LAUNCH(sort_classify_kernel<128>, dim3((rows + 127) / 128), dim3(kClassifyThreads), 0, s, ro, col, rows, cols, nnz,
-                     sc->reg_max, sc->lds_max, lists, st);
+    if (nnz / rows >= kSortTileLongAvg || rows < kSortTileLongRows)  // (measured: the scircuit stand-in's 171 k short rows want the small tile too)
+        SPECK_LAUNCH(sort_classify_kernel<kSortTileRows>, dim3((rows + kSortTileRows - 1) / kSortTileRows), dim3(kClassifyThreads), 0, s,
+                     ro, col, rows, cols, nnz, sc->reg_max, sc->lds_max, lists, st);
     else
-        SPECK_LAUNCH(sort_classify_kernel<512>, dim3((rows + 511) / 512), dim3(kClassifyThreads), 0, s, ro, col, rows, cols, nnz,
-                     sc->reg_max, sc->lds_max, lists, st);
+        SPECK_LAUNCH(sort_classify_kernel<kSortTileRowsLong>, dim3((rows + kSortTileRowsLong - 1) / kSortTileRowsLong),
+                     dim3(kClassifyThreads), 0, s, ro, col, rows, cols, nnz, sc->reg_max, sc->lds_max, lists, st);
     SortStatus h{};
-    HIP_TRY(hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (take_launch_error()) return SPECK_ERR_HIP;
+    rc = read_status(s, st, &h);
+    if (rc != SPECK_OK) return rc;
     if (h.invalid) return SPECK_ERR_INVALID;
 
     u64 to_sort = 0;
@@ -553,9 +551,8 @@ int sort_rows_run(SortScratch* sc, hipStream_t s, speck_dcsr* M, int flags, spec
                      rd, reinterpret_cast<u32*>(vb), reinterpret_cast<u32*>(vb + g4), reinterpret_cast<u32*>(vb + 2 * g4),
                      reinterpret_cast<T*>(vb + 3 * g4), ge, (u32)end_bit);
     }
-    HIP_TRY(hipMemcpyAsync(&h, st, sizeof h, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (take_launch_error()) return SPECK_ERR_HIP;
+    rc = read_status(s, st, &h);
+    if (rc != SPECK_OK) return rc;
     if (info) {
         info->rows_sorted[0] = reg_rows - h.deferred;
         info->rows_sorted[1] = h.cnt[LIST_LDS];
@@ -594,13 +591,7 @@ int sort_rows_run(SortScratch* sc, hipStream_t s, speck_dcsr* M, int flags, spec
     return SPECK_OK;
 }
 
-// debug option guard_bytes: the canary zones of M's buffers and of the temporaries after the call
-int check_sort_guards(const SortScratch* sc, hipStream_t s, const speck_dcsr* M, int rc)
-{
-    const void* whole[] = {sc->fixed.p, sc->var.p, M->data, M->col_ids, M->row_offsets};
-    static const char* names[] = {"sort lists", "sort temporaries", "M.data", "M.col_ids", "M.row_offsets"};
-    return guard_check_buffers(whole, names, 5, s, " by the row sort", rc);
-}
+const char* const kGuardNames[5] = {"sort lists", "sort temporaries", "M.data", "M.col_ids", "M.row_offsets"};
 
 template <typename T>
 int sort_rows_impl(speck_config* cfg, speck_dcsr* M, int flags, speck_sort_info* info)
@@ -620,7 +611,7 @@ int sort_rows_impl(speck_config* cfg, speck_dcsr* M, int flags, speck_sort_info*
     const hipStream_t s = cfg ? call_stream(cfg) : nullptr;
     (void)take_launch_error();
     int rc = sort_rows_run<T>(sc, s, M, flags, info);
-    rc = check_sort_guards(sc, s, M, rc);
+    rc = check_side_guards(sc, s, M, kGuardNames, " by the row sort", rc);
     if (!cfg) {
         (void)hipStreamSynchronize(s);
         own.release();

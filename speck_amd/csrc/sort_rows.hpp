@@ -16,5 +16,7 @@ struct SortScratch {
 };
 
 SortScratch* sort_scratch(speck_config* c);
+// rows per tile of the classifying pass: the long tile for kSortTileLongRows rows or more of fewer than kSortTileLongAvg entries
+constexpr u32 kSortTileRows = 128, kSortTileRowsLong = 512, kSortTileLongRows = 1u << 19, kSortTileLongAvg = 64;
 
 }  // namespace speck
