@@ -175,6 +175,11 @@ int speck_dcsr_free(speck_dcsr *m);
 int speck_dcsr_upload(speck_dcsr *dst, uint64_t rows, uint64_t cols, uint64_t nnz,
                       const uint32_t *h_row_offsets, const uint32_t *h_col_ids, const void *h_data,
                       size_t value_size);
+/* convert(CSR&, const dCSR&) -- source/dCSR.cpp:67-76; any of the host arrays may be NULL.  `src` may be a row-range
+ * view with absolute offsets (first offset not 0, last offset = first + nnz): the host receives exactly what a
+ * download of its speck_dcsr_copy gives -- the nnz entries from the first offset on, offsets rebased to start at 0.
+ * Every other matrix (an owner: first offset 0; offsets that do not span nnz entries) is downloaded as it lies in
+ * memory: offsets unchanged, the first nnz entries of col_ids / data. */
 int speck_dcsr_download(const speck_dcsr *src, uint32_t *h_row_offsets, uint32_t *h_col_ids,
                         void *h_data, size_t value_size);
 /* convert(dCSR&, const CSR&, padding) -- source/dCSR.cpp:51-66: buffers for rows + padding rows and nnz + 8 * padding
@@ -198,7 +203,7 @@ int speck_dcsr_update(speck_dcsr *dst, const uint32_t *h_row_offsets, const uint
  * or both are finite and within the bound -- equal infinities match, an infinity never matches a
  * finite value or the opposite infinity, NaN matches NaN only (the reference passes NaN against any
  * value, source/GPU/Compare.cu:50).
- * *h_mismatches = number of differing rows (0 = equal). */
+ * *h_mismatches = number of differing rows (0 = equal); a row that differs in its pattern AND in a value is one row. */
 int speck_compare_f64(speck_config *cfg, const speck_dcsr *ref, const speck_dcsr *cmp,
                       int compare_data, double rel_tol, uint64_t *h_mismatches);
 /* ... and its float instantiation (source/GPU/Compare.cu:84) */
@@ -207,7 +212,8 @@ int speck_compare_f32(speck_config *cfg, const speck_dcsr *ref, const speck_dcsr
 /* The value check a SpGEMM result admits whatever its summation order: |ref - cmp| <= tol * S per
  * entry, S = sum |a*b| of the entry, handed over as `abs_products` = |A|*|B| (same pattern as ref).
  * Role of the reference's compare against cuSPARSE (source/Executor.cpp:29-40), made to FAIL on
- * values: *h_structure_rows / *h_value_rows = rows that differ in pattern / beyond the bound. */
+ * values: *h_structure_rows / *h_value_rows = rows that differ in pattern / rows of equal pattern with a value beyond
+ * the bound (no row is in both counts). */
 int speck_compare_bounded_f64(speck_config *cfg, const speck_dcsr *ref, const speck_dcsr *cmp,
                               const speck_dcsr *abs_products, double tol, uint64_t *h_structure_rows,
                               uint64_t *h_value_rows);

@@ -8,6 +8,7 @@ from .api import (  # noqa: F401
     SpeckError, Timings, dCSR, spECKConfig, HostCSR, MultiplyspECK, BoundMultiply, analysis, symbolic,
     partition_rows, compare, compare_bounded, transpose, gen_matrix, load_matrix, load_mtx, store_mtx, load_hicsr,
     store_hicsr, lib_path, sort_rows, SortInfo, SORT_REG_MAX, SORT_LDS_MAX,
+    TRANSPOSE_TILE, TRANSPOSE_BLOCKS, TRANSPOSE_WAVE_SHARE, COMPARE_MAX_WAVES, COPY_MAX_THREADS,
     multiply_masked, MaskedInfo, MASK_GROUP_MAX, MASK_LDS_MAX,
     select, tril, triu, SelectInfo, SELECT_TILE_ROWS, SELECT_LONG_ROW_AVG,
     SELECT_BAND, SELECT_ABS, SELECT_PATTERN, SELECT_NOT_BAND, SELECT_NOT_ABS, SELECT_NOT_PATTERN,

@@ -400,7 +400,7 @@ def compare(ref, cmp, config, compare_data=False, rel_tol=1e-12):
 
 
 def compare_bounded(ref, cmp, abs_products, config, tol=1e-12):
-    """(rows differing in structure, rows with |ref - cmp| > tol * sum|a*b|); abs_products = |A|*|B|."""
+    """(rows differing in structure, rows of equal structure with |ref - cmp| > tol * sum|a*b|); abs_products = |A|*|B|."""
     ns, nv = C.c_uint64(), C.c_uint64()
     _check(_lib.load().speck_compare_bounded_f64(config._h, C.byref(ref._c), C.byref(cmp._c),
                                                  C.byref(abs_products._c), float(tol), C.byref(ns), C.byref(nv)),
@@ -419,6 +419,15 @@ def transpose(A, config):
 # include/speck_c_api.h: SPECK_SORT_REG_MAX / SPECK_SORT_LDS_MAX (rows up to this many entries are sorted in registers / in LDS)
 SORT_REG_MAX = 256
 SORT_LDS_MAX = 4096
+# speck_amd/csrc/extras.hip: the radix sort behind transpose walks tiles of TRANSPOSE_TILE entries (kRadixThreads x
+# kRadixItems; a wave's share of a tile is TRANSPOSE_WAVE_SHARE = 64 x kRadixItems) in TRANSPOSE_BLOCKS workgroups
+# (kRadixBlocks); compare runs at most COMPARE_MAX_WAVES waves (8192 workgroups of 4), one row per wave and trip;
+# speck_amd/csrc/dcsr.hip: the device copy runs at most COPY_MAX_THREADS threads (8192 workgroups of 256), a word per trip
+TRANSPOSE_TILE = 2048
+TRANSPOSE_BLOCKS = 1024
+TRANSPOSE_WAVE_SHARE = 512
+COMPARE_MAX_WAVES = 32768
+COPY_MAX_THREADS = 2097152
 
 
 class SortInfo:

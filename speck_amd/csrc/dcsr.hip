@@ -122,12 +122,31 @@ int speck_dcsr_download(const speck_dcsr* src, uint32_t* h_row_offsets, uint32_t
                         void* h_data, size_t value_size)
 {
     if (!src) return SPECK_ERR_INVALID;
-    if (src->nnz) {
-        if (h_data) HIP_TRY(hipMemcpy(h_data, src->data, src->nnz * value_size, hipMemcpyDeviceToHost));
-        if (h_col_ids) HIP_TRY(hipMemcpy(h_col_ids, src->col_ids, src->nnz * 4, hipMemcpyDeviceToHost));
+    // A row-range view keeps absolute offsets into buffers it shares: its entries start at its FIRST offset, and the
+    // host gets what speck_dcsr_copy makes of it (its own entries, offsets from 0).  A view is known by its offsets:
+    // the first is not 0 and the last is the first + nnz.  Anything else (an owner, whose first offset is 0; offsets
+    // that were never written or do not describe nnz entries) is downloaded as it lies in memory, from entry 0.
+    u32 base = 0;
+    if (src->row_offsets) {
+        u32 ends[2] = {0, 0};
+        if (h_row_offsets) {
+            HIP_TRY(hipMemcpy(h_row_offsets, src->row_offsets, (src->rows + 1) * 4, hipMemcpyDeviceToHost));
+            ends[0] = h_row_offsets[0];
+            ends[1] = h_row_offsets[src->rows];
+        } else if (h_col_ids || h_data) {
+            HIP_TRY(hipMemcpy(&ends[0], src->row_offsets, 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(&ends[1], src->row_offsets + src->rows, 4, hipMemcpyDeviceToHost));
+        }
+        if (ends[0] && uint64_t(ends[1]) == uint64_t(ends[0]) + src->nnz) base = ends[0];
+        if (base && h_row_offsets)
+            for (uint64_t i = 0; i <= src->rows; ++i) h_row_offsets[i] -= base;
     }
-    if (h_row_offsets && src->row_offsets)
-        HIP_TRY(hipMemcpy(h_row_offsets, src->row_offsets, (src->rows + 1) * 4, hipMemcpyDeviceToHost));
+    if (src->nnz) {
+        if (h_data)
+            HIP_TRY(hipMemcpy(h_data, static_cast<const char*>(src->data) + size_t(base) * value_size,
+                              src->nnz * value_size, hipMemcpyDeviceToHost));
+        if (h_col_ids) HIP_TRY(hipMemcpy(h_col_ids, src->col_ids + base, src->nnz * 4, hipMemcpyDeviceToHost));
+    }
     return SPECK_OK;
 }
 

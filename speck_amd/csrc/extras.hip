@@ -62,8 +62,9 @@ __global__ void compare_kernel(const u32* __restrict__ ro_a, const u32* __restri
                 }
             }
         }
-        if (__ballot(bad) != 0 && lane == 0) atomicAdd(&mismatches[0], 1ull);
-        if (__ballot(badv) != 0 && lane == 0) atomicAdd(&mismatches[1], 1ull);
+        // a row counts once: its values are only judged where its pattern is the same
+        const bool row_bad = __ballot(bad) != 0, row_badv = __ballot(badv) != 0;
+        if (lane == 0 && (row_bad || row_badv)) atomicAdd(&mismatches[row_bad ? 0 : 1], 1ull);
     }
 }
 
