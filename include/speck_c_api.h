@@ -414,6 +414,58 @@ int speck_add_f64(speck_config *cfg, double alpha, const speck_dcsr *A, double b
 int speck_add_f32(speck_config *cfg, double alpha, const speck_dcsr *A, double beta, const speck_dcsr *B, speck_dcsr *C,
                   int flags, speck_add_info *info);
 
+/* ---- reduction (new: the reference has no counterpart): per row and over all entries of a matrix that is already on the
+ *      device, a sum or an extremum -- the triangle count and the per-vertex counts behind symmetrize -> tril ->
+ *      multiply_masked, the max-abs or Frobenius norm of a residual A - B, the row sums, row norms and largest entries
+ *      that a row normalisation or a pruning threshold asks of a product.  The one map matrix -> vector / scalar.
+ *  d_row_out[i] (a DEVICE array of A->rows doubles, may be NULL) is the reduction of row i, *h_total (HOST, may be NULL)
+ *      that of all entries; both NULL: SPECK_ERR_INVALID.  Results are double for both value types: a float is widened
+ *      exactly and never rounded back.
+ *  SUM adds v, ABS_SUM |v|, SQ_SUM v v (each square rounded to double before it is added, no fused multiply-add: every code
+ *      path adds the same terms); MAX / MIN / ABS_MAX take the largest v, the smallest v, the largest |v|.  A row without
+ *      an entry (and the total of a matrix without one) is +0.0 for the three sums and ABS_MAX, -inf for MAX, +inf for MIN.
+ *      A NaN entry makes its row's result and the total NaN for EVERY op -- the extrema do not drop it as fmax does: a NaN
+ *      is not hidden -- and touches no other row.  Infinities follow IEEE (inf + -inf is NaN).  The sign of a zero result
+ *      is unspecified.
+ *  No floating-point atomic anywhere.  Every result comes from a combination tree that depends only on the ABSOLUTE
+ *      positions of the entries in data (counted from the buffer's start, not from row_offsets[0]): the same call gives
+ *      the same bits from run to run, and a row-range view gives bit for bit the rows r0..r1 of the whole matrix's result
+ *      -- a row-sharded reduction equals the unsharded one.  The total is reproducible from run to run; its tree is
+ *      otherwise unspecified.  Against the exact sum |got - exact| <= g_n sum|term|, g_n = n 2^-53 / (1 - n 2^-53), n the
+ *      number of terms of the row (of the matrix, for the total): the bound of any summation order.  The extrema are exact.
+ *  Only row_offsets and data are read: col_ids is never dereferenced and may be NULL or garbage, and rows need not be
+ *      sorted or free of duplicates.  Offsets descending, leaving [row_offsets[0], row_offsets[0] + nnz], or a last offset
+ *      that is not row_offsets[0] + nnz: SPECK_ERR_INVALID.  NULL A, NULL row_offsets, data == NULL with nnz > 0, an unknown
+ *      op, d_row_out equal to one of A's three pointers: SPECK_ERR_INVALID.  rows > 2^27: SPECK_ERR_DIM_LIMIT.  nnz >= 2^32:
+ *      SPECK_ERR_NNZ_OVERFLOW.  A may be a row-range view with absolute offsets; rows == 0 or nnz == 0 is valid (identities).
+ *  On any error d_row_out and *h_total are untouched (*info is zero once the arguments have passed).  No offset is used as
+ *      an address before it was checked, and there is NO read-back in the middle of the call: a checking pass raises the
+ *      verdict in a status block, the kernels that read data and write results are queued behind it and do nothing where it
+ *      is raised, and the host reads the status once, at the end -- the verdict, the counters, the total.
+ *  Runs on the config's stream (speck_config_set_stream is honoured) and returns with the results complete.  Temporaries
+ *      are grow-only buffers of the config's own (not the multiply's arena: a reduce between two identical multiplies does
+ *      not disturb the second one's reuse sequence), released with it; cfg == NULL is allowed as for speck_sort_rows_*.
+ *      With the debug option guard_bytes the canary zones of the temporaries are checked after the call.
+ *  The entries are walked in tiles of SPECK_REDUCE_TILE_ENTRIES, aligned to absolute positions; a thread holds
+ *      SPECK_REDUCE_THREAD_ENTRIES consecutive ones, a wave SPECK_REDUCE_WAVE_ENTRIES.  One path for every row length.
+ *  Not built: column reductions (transpose, then reduce); counts (a row's is the difference of two offsets); means;
+ *      user-defined monoids; a reduce fused into the product that made A. ---- */
+enum { SPECK_REDUCE_SUM = 0, SPECK_REDUCE_ABS_SUM = 1, SPECK_REDUCE_SQ_SUM = 2,
+       SPECK_REDUCE_MAX = 3, SPECK_REDUCE_MIN = 4, SPECK_REDUCE_ABS_MAX = 5 };
+#define SPECK_REDUCE_TILE_ENTRIES 4096
+#define SPECK_REDUCE_THREAD_ENTRIES 16
+#define SPECK_REDUCE_WAVE_ENTRIES 1024
+typedef struct speck_reduce_info {
+    uint64_t rows_empty;   /* rows without an entry: they receive the identity */
+    uint64_t rows_split;   /* rows whose entries lie in more than one tile */
+    uint64_t tiles;        /* tiles walked */
+    uint64_t entries;      /* entries reduced = nnz */
+} speck_reduce_info;
+int speck_reduce_f64(speck_config *cfg, const speck_dcsr *A, int op, double *d_row_out, double *h_total,
+                     speck_reduce_info *info /* may be NULL */);
+int speck_reduce_f32(speck_config *cfg, const speck_dcsr *A, int op, double *d_row_out, double *h_total,
+                     speck_reduce_info *info);
+
 /* ---- row-sharded multi-GPU (new: the reference is single-GPU, source/Executor.cpp:25).  One process per GPU;
  *      rank p multiplies the row range [b_p, b_{p+1}) of A (a view with absolute offsets, boundaries from
  *      speck_partition_rows) with a replicated B, then ONE exchange concatenates the shards on a root rank:

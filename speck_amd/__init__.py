@@ -13,4 +13,6 @@ from .api import (  # noqa: F401
     select, tril, triu, SelectInfo, SELECT_TILE_ROWS, SELECT_LONG_ROW_AVG,
     SELECT_BAND, SELECT_ABS, SELECT_PATTERN, SELECT_NOT_BAND, SELECT_NOT_ABS, SELECT_NOT_PATTERN,
     add, symmetrize, AddInfo, ADD_UNION, ADD_TILE_ROWS, ADD_LONG_ROW_AVG, ADD_TILE_ENTRIES,
+    reduce, ReduceInfo, REDUCE_SUM, REDUCE_ABS_SUM, REDUCE_SQ_SUM, REDUCE_MAX, REDUCE_MIN, REDUCE_ABS_MAX, REDUCE_OPS,
+    REDUCE_TILE_ENTRIES, REDUCE_THREAD_ENTRIES, REDUCE_WAVE_ENTRIES,
 )

@@ -70,6 +70,11 @@ class CAddInfo(C.Structure):
     _fields_ = [("only_a", C.c_uint64), ("only_b", C.c_uint64), ("both", C.c_uint64), ("nnz_out", C.c_uint64)]
 
 
+class CReduceInfo(C.Structure):
+    # include/speck_c_api.h: speck_reduce_info
+    _fields_ = [("rows_empty", C.c_uint64), ("rows_split", C.c_uint64), ("tiles", C.c_uint64), ("entries", C.c_uint64)]
+
+
 # every symbol include/speck_c_api.h declares, with its ctypes signature
 _P = C.POINTER
 _SIGS = {
@@ -107,6 +112,8 @@ _SIGS = {
     "speck_select_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(CSelectParams), _P(DCsr), _P(CSelectInfo)]),
     "speck_add_f64": (C.c_int, [C.c_void_p, C.c_double, _P(DCsr), C.c_double, _P(DCsr), _P(DCsr), C.c_int, _P(CAddInfo)]),
     "speck_add_f32": (C.c_int, [C.c_void_p, C.c_double, _P(DCsr), C.c_double, _P(DCsr), _P(DCsr), C.c_int, _P(CAddInfo)]),
+    "speck_reduce_f64": (C.c_int, [C.c_void_p, _P(DCsr), C.c_int, C.c_void_p, _P(C.c_double), _P(CReduceInfo)]),
+    "speck_reduce_f32": (C.c_int, [C.c_void_p, _P(DCsr), C.c_int, C.c_void_p, _P(C.c_double), _P(CReduceInfo)]),
     "speck_compare_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), C.c_int, C.c_double, _P(C.c_uint64)]),
     "speck_compare_bounded_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), _P(DCsr), C.c_double, _P(C.c_uint64),
                                             _P(C.c_uint64)]),

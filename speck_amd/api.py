@@ -620,3 +620,59 @@ def symmetrize(A, config):
     if A.rows != A.cols:
         raise ValueError("symmetrize: A must be square")
     return add(A, transpose(A, config), config)[0]
+
+
+# include/speck_c_api.h: SPECK_REDUCE_*; the entries of a tile, of a thread and of a wave of the pass that walks them
+REDUCE_SUM, REDUCE_ABS_SUM, REDUCE_SQ_SUM, REDUCE_MAX, REDUCE_MIN, REDUCE_ABS_MAX = range(6)
+REDUCE_OPS = {"sum": REDUCE_SUM, "abs_sum": REDUCE_ABS_SUM, "sq_sum": REDUCE_SQ_SUM, "max": REDUCE_MAX, "min": REDUCE_MIN,
+              "abs_max": REDUCE_ABS_MAX}
+REDUCE_TILE_ENTRIES = 4096
+REDUCE_THREAD_ENTRIES = 16
+REDUCE_WAVE_ENTRIES = 1024
+
+
+class ReduceInfo:
+    """speck_reduce_info: what the reduction walked."""
+
+    def __init__(self, c):
+        self.rows_empty = int(c.rows_empty)
+        self.rows_split = int(c.rows_split)
+        self.tiles = int(c.tiles)
+        self.entries = int(c.entries)
+
+    def __repr__(self):
+        return (f"ReduceInfo(rows_empty={self.rows_empty}, rows_split={self.rows_split}, tiles={self.tiles}, "
+                f"entries={self.entries})")
+
+
+def reduce(A, config, op="sum", rows=True, total=True, out_ptr=None):
+    """Per row and over all entries of a device matrix (speck_reduce_f64 / _f32): op is "sum", "abs_sum", "sq_sum", "max",
+    "min" or "abs_max" (or its REDUCE_* number); results are float64 for both value types.  A row without entries is 0.0,
+    -inf for "max", +inf for "min"; a NaN entry makes its row and the total NaN for every op.  Bit-reproducible, and a
+    row_view gives the rows of the whole matrix bit for bit.  Column quantities: reduce(transpose(A)).
+    Returns (row_values, total, ReduceInfo).  row_values is a numpy array downloaded from a buffer of the library's
+    allocator; None when rows=False, and None when out_ptr -- a device address of A.rows float64, e.g. a torch tensor's
+    data_ptr() -- keeps the result on the device.  total is None when total=False.  config may be None."""
+    if isinstance(op, str):
+        if op not in REDUCE_OPS:
+            raise ValueError(f"reduce: unknown op {op!r} (one of {', '.join(REDUCE_OPS)})")
+        op = REDUCE_OPS[op]
+    elif op not in REDUCE_OPS.values():
+        raise ValueError(f"reduce: unknown op {op!r}")
+    L = _lib.load()
+    fn = L.speck_reduce_f32 if A.dtype == np.float32 else L.speck_reduce_f64
+    buf = None
+    if out_ptr is None and rows:
+        buf = dCSR(np.float64)  # (its data array: A.rows doubles)
+        buf.alloc(0, 0, max(A.rows, 1), allocOffsets=False)
+        out_ptr = buf._c.data
+    t = C.c_double()
+    info = _lib.CReduceInfo()
+    _check(fn(config._h if config is not None else None, C.byref(A._c), int(op), out_ptr if rows else None,
+              C.byref(t) if total else None, C.byref(info)), "reduce")
+    row_values = None
+    if buf is not None:
+        row_values = np.zeros(max(A.rows, 1), dtype=np.float64)
+        _check(L.speck_dcsr_download(C.byref(buf._c), None, None, row_values.ctypes.data, 8), "reduce: download")
+        row_values = row_values[:A.rows]
+    return row_values, (float(t.value) if total else None), ReduceInfo(info)

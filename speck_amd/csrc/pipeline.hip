@@ -32,6 +32,7 @@
 #include "masked.hpp"
 #include "select.hpp"
 #include "add.hpp"
+#include "reduce.hpp"
 #include "sort_rows.hpp"
 
 using namespace speck;
@@ -235,6 +236,7 @@ struct speck_config {
     MaskedScratch masked;  // ... and of speck_multiply_masked_* (masked.hip)
     SelectScratch select;  // ... and of speck_select_* (select.hip)
     AddScratch add;  // ... and of speck_add_* (add.hip)
+    ReduceScratch reduce;  // ... and of speck_reduce_* (reduce.hip)
     const void* zones_arena = nullptr;
     u64 zones_m = 0, zones_nnz = 0, zones_gap = 0;
     bool gpool_zones_filled = false;
@@ -1922,6 +1924,7 @@ MaskedScratch* masked_scratch(speck_config* c) { return &c->masked; }
 
 SelectScratch* select_scratch(speck_config* c) { return &c->select; }
 AddScratch* add_scratch(speck_config* c) { return &c->add; }
+ReduceScratch* reduce_scratch(speck_config* c) { return &c->reduce; }
 }  // namespace speck
 
 extern "C" {
@@ -2038,6 +2041,7 @@ int speck_config_destroy(speck_config* c)
     c->masked.release();
     c->select.release();
     c->add.release();
+    c->reduce.release();
     if (c->pred.off) (void)guarded_free(c->pred.off);
     if (c->gpred.off) (void)guarded_free(c->gpred.off);
     if (c->d_stats) (void)hipFree(c->d_stats);
@@ -2122,6 +2126,7 @@ int speck_config_set_option(speck_config* c, const char* name, int64_t value)
         c->masked.release();
         c->select.release();
         c->add.release();
+        c->reduce.release();
     }
     else if (n == "sort_reg_max") c->sort.reg_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_REG_MAX);
     else if (n == "sort_lds_max") c->sort.lds_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_LDS_MAX);
