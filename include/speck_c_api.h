@@ -466,6 +466,73 @@ int speck_reduce_f64(speck_config *cfg, const speck_dcsr *A, int op, double *d_r
 int speck_reduce_f32(speck_config *cfg, const speck_dcsr *A, int op, double *d_row_out, double *h_total,
                      speck_reduce_info *info);
 
+/* ---- scaling (new: the reference has no counterpart): C(i,j) = ((alpha g(A(i,j))) (.) l[i]) (.) r[j] on the pattern of a
+ *      matrix that is already on the device -- the one map from a device vector back into a matrix, as speck_reduce_* is
+ *      the one out of it: the row normalisation of a product by its row sums (Markov matrices, the inflation v v and the
+ *      normalisation of an MCL step), D^-1/2 (S + S^T) D^-1/2 with one vector on both sides, D^-1 A of a Jacobi-smoothed
+ *      prolongator, the indicator matrix of a weighted graph before a triangle count.  g is p->map: IDENTITY, ABS |v|,
+ *      SQUARE v v, ONE (1.0 whatever the entry holds, a NaN included).  The vectors are optional; each multiplies
+ *      (SPECK_SCALE_MUL) or divides (SPECK_SCALE_DIV).  C == NULL works IN PLACE -- the structure does not change, so
+ *      this is the one side operation that can.
+ *  Values: every step in double for both value types, in this order: x = (double)a; x = g(x); x = alpha * x (always);
+ *      x = x * l[i] or x / l[i] where row_mode is set; x = x * r[j] or x / r[j] where col_mode is set; ONE rounding to T.
+ *      Each step is rounded to double on its own, the division is the correctly rounded IEEE division, nothing is fused:
+ *      every result that is not a NaN is bit for bit numpy's (((alpha * g(a.astype(f64))) (.) l[row]) (.) r[col]).astype(T),
+ *      signed zeros and subnormals included, and a NaN stands exactly where numpy has one.  Nothing is hidden: 0 * inf,
+ *      x / 0, a NaN in a vector land in the entry; info->nonfinite counts the results that are inf or NaN AFTER the
+ *      rounding to T, and they do not make the call fail.  Every entry is written once by one thread: the same bits from
+ *      run to run.  Structural: no entry is dropped, a result of 0.0 stays (as in speck_add_*).
+ *  d_row (DEVICE, A->rows doubles) is indexed by the row INSIDE A -- for a row-range view the caller offsets the pointer,
+ *      not the library; d_col (DEVICE, A->cols doubles) by the column id.  The two may be the same array.  A mode set with
+ *      a NULL vector, a vector given with mode NONE, a vector equal to one of A's or C's three pointers, an unknown map
+ *      or mode, alpha NaN: SPECK_ERR_INVALID.
+ *  In place (C == NULL): only A->data[row_offsets[0] .. row_offsets[0] + nnz) is written; row_offsets, col_ids, nnz and
+ *      the three pointers stay as they were.  On a row-range view with absolute offsets only the view's entries are
+ *      touched: the owner's entries in front of and behind them keep their bytes.
+ *  Out of place: C receives A's pattern -- the offsets rebased to 0, col_ids copied bit for bit -- under the ownership
+ *      rule of speck_select_*: rows(C) == rows(A) keeps C->row_offsets, nnz(C) == nnz(A) keeps data / col_ids, anything
+ *      else is freed and re-allocated; C sharing a buffer with A: SPECK_ERR_INVALID.
+ *  Rows need not be sorted or free of duplicates.  col_ids is read only where col_mode != NONE or C != NULL: in place
+ *      without a column vector it may be NULL or garbage.  Offsets descending, leaving [row_offsets[0], row_offsets[0] +
+ *      nnz], or a last offset that is not row_offsets[0] + nnz; a column id >= cols where col_ids is read; NULL A or p,
+ *      NULL row_offsets, data == NULL with nnz > 0: SPECK_ERR_INVALID.  rows or cols > 2^27: SPECK_ERR_DIM_LIMIT.
+ *      nnz >= 2^32: SPECK_ERR_NNZ_OVERFLOW.  rows == 0 or nnz == 0 is valid.
+ *  On any error NOTHING is written: not A->data, not C's buffers, not C's struct (*info is zero once the arguments have
+ *      passed).  As in speck_reduce_*: no offset or column id is used as an address before it was checked; a checking pass
+ *      raises its verdict in a status block, the kernels that write are queued behind it and do nothing where it is raised,
+ *      and the host reads the status ONCE, at the end -- the verdict, nonfinite.
+ *  Runs on the config's stream (speck_config_set_stream is honoured) and returns complete.  Temporaries are two grow-only
+ *      buffers of the config's own (not the multiply's arena: a scale between two identical multiplies does not disturb
+ *      the second one's reuse sequence), released with it; cfg == NULL is allowed as for speck_sort_rows_*.  With the debug
+ *      option guard_bytes the canary zones of the temporaries and of C (in place: of A's buffers) are checked after the call.
+ *  Without a row vector the call is a plain stream over the entries, 16 bytes per lane and step, and knows nothing of rows
+ *      beyond the check of the offsets (info->tiles is 0).  With one the entries are walked in tiles of
+ *      SPECK_SCALE_TILE_ENTRIES, aligned to absolute positions as the reduction's; one path for every row length; l[i]
+ *      is loaded once per row segment.  The 16-byte form needs data (and col_ids where read) on 16-byte boundaries and,
+ *      out of place, row_offsets[0] a multiple of 4; elsewhere the entries go one by one, with the same results.
+ *  Not built: pow and other libm maps (not bit-reproducible against numpy); sqrt modes (the vector is the caller's: a
+ *      torch rsqrt_ on it is plumbing); per-row thresholds in speck_select_*; a scale fused into the product that made A;
+ *      vectors in float. ---- */
+enum { SPECK_MAP_IDENTITY = 0, SPECK_MAP_ABS = 1, SPECK_MAP_SQUARE = 2, SPECK_MAP_ONE = 3 };
+enum { SPECK_SCALE_NONE = 0, SPECK_SCALE_MUL = 1, SPECK_SCALE_DIV = 2 };
+#define SPECK_SCALE_TILE_ENTRIES 4096
+typedef struct speck_scale_params {
+    uint32_t map;                 /* SPECK_MAP_*   */
+    uint32_t row_mode, col_mode;  /* SPECK_SCALE_* */
+    double alpha;
+    const double *d_row;          /* DEVICE, A->rows doubles, indexed by the row INSIDE A (a view offsets the pointer) */
+    const double *d_col;          /* DEVICE, A->cols doubles */
+} speck_scale_params;
+typedef struct speck_scale_info {
+    uint64_t entries;             /* entries written = nnz */
+    uint64_t nonfinite;           /* ... of which the result, after rounding to T, is inf or NaN */
+    uint64_t tiles;               /* entry tiles walked (0 for a call without a row vector: it has no tiles) */
+} speck_scale_info;
+int speck_scale_f64(speck_config *cfg, const speck_dcsr *A, const speck_scale_params *p, speck_dcsr *C /* NULL: in place */,
+                    speck_scale_info *info /* may be NULL */);
+int speck_scale_f32(speck_config *cfg, const speck_dcsr *A, const speck_scale_params *p, speck_dcsr *C,
+                    speck_scale_info *info);
+
 /* ---- row-sharded multi-GPU (new: the reference is single-GPU, source/Executor.cpp:25).  One process per GPU;
  *      rank p multiplies the row range [b_p, b_{p+1}) of A (a view with absolute offsets, boundaries from
  *      speck_partition_rows) with a replicated B, then ONE exchange concatenates the shards on a root rank:

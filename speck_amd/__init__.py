@@ -15,4 +15,6 @@ from .api import (  # noqa: F401
     add, symmetrize, AddInfo, ADD_UNION, ADD_TILE_ROWS, ADD_LONG_ROW_AVG, ADD_TILE_ENTRIES,
     reduce, ReduceInfo, REDUCE_SUM, REDUCE_ABS_SUM, REDUCE_SQ_SUM, REDUCE_MAX, REDUCE_MIN, REDUCE_ABS_MAX, REDUCE_OPS,
     REDUCE_TILE_ENTRIES, REDUCE_THREAD_ENTRIES, REDUCE_WAVE_ENTRIES,
+    scale, normalize_rows, pattern_ones, ScaleInfo, MAP_IDENTITY, MAP_ABS, MAP_SQUARE, MAP_ONE, SCALE_MAPS,
+    SCALE_NONE, SCALE_MUL, SCALE_DIV, SCALE_TILE_ENTRIES,
 )

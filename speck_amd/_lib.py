@@ -75,6 +75,17 @@ class CReduceInfo(C.Structure):
     _fields_ = [("rows_empty", C.c_uint64), ("rows_split", C.c_uint64), ("tiles", C.c_uint64), ("entries", C.c_uint64)]
 
 
+class CScaleParams(C.Structure):
+    # include/speck_c_api.h: speck_scale_params
+    _fields_ = [("map", C.c_uint32), ("row_mode", C.c_uint32), ("col_mode", C.c_uint32), ("alpha", C.c_double),
+                ("d_row", C.c_void_p), ("d_col", C.c_void_p)]
+
+
+class CScaleInfo(C.Structure):
+    # include/speck_c_api.h: speck_scale_info
+    _fields_ = [("entries", C.c_uint64), ("nonfinite", C.c_uint64), ("tiles", C.c_uint64)]
+
+
 # every symbol include/speck_c_api.h declares, with its ctypes signature
 _P = C.POINTER
 _SIGS = {
@@ -114,6 +125,8 @@ _SIGS = {
     "speck_add_f32": (C.c_int, [C.c_void_p, C.c_double, _P(DCsr), C.c_double, _P(DCsr), _P(DCsr), C.c_int, _P(CAddInfo)]),
     "speck_reduce_f64": (C.c_int, [C.c_void_p, _P(DCsr), C.c_int, C.c_void_p, _P(C.c_double), _P(CReduceInfo)]),
     "speck_reduce_f32": (C.c_int, [C.c_void_p, _P(DCsr), C.c_int, C.c_void_p, _P(C.c_double), _P(CReduceInfo)]),
+    "speck_scale_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(CScaleParams), _P(DCsr), _P(CScaleInfo)]),
+    "speck_scale_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(CScaleParams), _P(DCsr), _P(CScaleInfo)]),
     "speck_compare_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), C.c_int, C.c_double, _P(C.c_uint64)]),
     "speck_compare_bounded_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), _P(DCsr), C.c_double, _P(C.c_uint64),
                                             _P(C.c_uint64)]),

@@ -676,3 +676,103 @@ def reduce(A, config, op="sum", rows=True, total=True, out_ptr=None):
         _check(L.speck_dcsr_download(C.byref(buf._c), None, None, row_values.ctypes.data, 8), "reduce: download")
         row_values = row_values[:A.rows]
     return row_values, (float(t.value) if total else None), ReduceInfo(info)
+
+
+# include/speck_c_api.h: SPECK_MAP_*, SPECK_SCALE_*; the entries of a tile of the pass that walks them with a row vector
+MAP_IDENTITY, MAP_ABS, MAP_SQUARE, MAP_ONE = range(4)
+SCALE_MAPS = {"identity": MAP_IDENTITY, "abs": MAP_ABS, "square": MAP_SQUARE, "one": MAP_ONE}
+SCALE_NONE, SCALE_MUL, SCALE_DIV = range(3)
+SCALE_TILE_ENTRIES = 4096
+
+
+class ScaleInfo:
+    """speck_scale_info: what the scaling wrote."""
+
+    def __init__(self, c):
+        self.entries = int(c.entries)
+        self.nonfinite = int(c.nonfinite)
+        self.tiles = int(c.tiles)
+
+    def __repr__(self):
+        return f"ScaleInfo(entries={self.entries}, nonfinite={self.nonfinite}, tiles={self.tiles})"
+
+
+def _device_vector(v, n, what):
+    """The device address of a vector of n float64: an address as it is, a torch tensor (anything with data_ptr()) checked"""
+    if v is None:
+        return None
+    if not hasattr(v, "data_ptr"):
+        return int(v)
+    if hasattr(v, "dtype") and str(v.dtype) not in ("torch.float64", "float64"):
+        raise ValueError(f"scale: {what} must be float64, not {v.dtype}")
+    if hasattr(v, "is_contiguous") and not v.is_contiguous():
+        raise ValueError(f"scale: {what} must be contiguous")
+    if hasattr(v, "numel") and v.numel() != n:
+        raise ValueError(f"scale: {what} holds {v.numel()} values, the matrix asks for {n}")
+    return int(v.data_ptr())
+
+
+def scale(A, config, alpha=1.0, map="identity", row=None, col=None, row_div=False, col_div=False, matOut=None, inplace=False):
+    """C(i,j) = ((alpha g(A(i,j))) (.) row[i]) (.) col[j] on A's pattern (speck_scale_f64 / _f32).  map is g: "identity",
+    "abs", "square" or "one" (1.0 whatever the entry holds, a NaN included), or its MAP_* number.  row (A.rows float64) and
+    col (A.cols float64) are optional device vectors -- a device address or an object with data_ptr(), e.g. a torch tensor;
+    they may be one array; row is indexed by the row inside A, so for a row_view pass the slice.  Each multiplies, or divides
+    with row_div / col_div.  Every step is computed in double and rounded once to A's value type: bit for bit numpy's
+    (((alpha * g(a.astype(f64))) (.) row[i]) (.) col[j]).astype(dtype), NaN where numpy has NaN.  Nothing is hidden or
+    dropped: 0 * inf, x / 0 and a NaN of a vector land in the entry and are counted in info.nonfinite; a result of 0.0 stays.
+    inplace=True overwrites A's values (on a row_view: the view's entries only) and leaves its structure alone; otherwise
+    the result goes to matOut (a new matrix when None) with A's pattern, offsets rebased to 0.  Rows need not be sorted;
+    col_ids is read only for col or a new matrix.  config may be None.  Returns (matOut or A, ScaleInfo)."""
+    if isinstance(map, str):
+        if map not in SCALE_MAPS:
+            raise ValueError(f"scale: unknown map {map!r} (one of {', '.join(SCALE_MAPS)})")
+        map = SCALE_MAPS[map]
+    elif map not in SCALE_MAPS.values():
+        raise ValueError(f"scale: unknown map {map!r}")
+    if inplace and matOut is not None:
+        raise ValueError("scale: inplace=True and matOut exclude each other")
+    p = _lib.CScaleParams()
+    p.map = int(map)
+    p.alpha = float(alpha)
+    p.d_row = _device_vector(row, A.rows, "row")
+    p.d_col = _device_vector(col, A.cols, "col")
+    p.row_mode = SCALE_NONE if row is None else SCALE_DIV if row_div else SCALE_MUL
+    p.col_mode = SCALE_NONE if col is None else SCALE_DIV if col_div else SCALE_MUL
+    L = _lib.load()
+    fn = L.speck_scale_f32 if A.dtype == np.float32 else L.speck_scale_f64
+    info = _lib.CScaleInfo()
+    h = config._h if config is not None else None
+    if inplace:
+        _check(fn(h, C.byref(A._c), C.byref(p), None, C.byref(info)), "scale")
+        return A, ScaleInfo(info)
+    if matOut is None:
+        matOut = dCSR(A.dtype)
+    if matOut.dtype != A.dtype:
+        matOut.reset()
+        matOut.dtype = A.dtype
+    _check(fn(h, C.byref(A._c), C.byref(p), C.byref(matOut._c), C.byref(info)), "scale")
+    ro = A._host_row_offsets   # (C's offsets are A's, from 0: the host copy is shared where A's start there)
+    matOut._host_row_offsets = ro if ro is None or ro[0] == 0 else (ro - ro[0]).astype(np.uint32)
+    return matOut, ScaleInfo(info)
+
+
+_ROW_NORMS = ("abs_sum", "sum", "abs_max")
+
+
+def normalize_rows(A, config, norm="abs_sum", inplace=False):
+    """Every row of A divided by its norm -- "abs_sum" (row-stochastic where the entries are not negative), "sum" or
+    "abs_max" -- without leaving the device: reduce(A, norm) into a device buffer, then scale(A, row=that, row_div=True).
+    A row whose norm is 0 (explicit zeros only, or values that cancel under "sum") becomes NaN (0 / 0) or inf (x / 0): such
+    entries are not hidden and show up in info.nonfinite.  Rows without entries stay empty.  Returns (matrix, ScaleInfo)."""
+    if norm not in _ROW_NORMS:
+        raise ValueError(f"normalize_rows: unknown norm {norm!r} (one of {', '.join(_ROW_NORMS)})")
+    buf = dCSR(np.float64)  # (its data array: A.rows doubles of the library's allocator)
+    buf.alloc(0, 0, max(A.rows, 1), allocOffsets=False)
+    reduce(A, config, norm, total=False, out_ptr=buf._c.data)
+    return scale(A, config, row=buf._c.data, row_div=True, inplace=inplace)
+
+
+def pattern_ones(A, config):
+    """The indicator matrix of A: its pattern with every value 1.0 (scale with map "one"), made on the device -- what a
+    triangle count L o (L L) needs of a weighted graph."""
+    return scale(A, config, map="one")[0]

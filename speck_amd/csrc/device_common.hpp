@@ -408,7 +408,8 @@ __device__ __forceinline__ u64 wave_reduce_add(u64 v)
     const u64 s_lo16 = wave_reduce_add(lo & 0xFFFFu), s_hi16 = wave_reduce_add(lo >> 16);
     return (u64(wave_reduce_add(hi)) << 32) + (s_hi16 << 16) + s_lo16;
 }
-__device__ __forceinline__ u32 wave_reduce_max(u32 v)
+// the largest value of the lanes up to mine
+__device__ __forceinline__ u32 wave_inclusive_max(u32 v)
 {
     v = max(v, dpp_move<kDppRowShr + 1>(0, v));
     v = max(v, dpp_move<kDppRowShr + 2>(0, v));
@@ -416,7 +417,11 @@ __device__ __forceinline__ u32 wave_reduce_max(u32 v)
     v = max(v, dpp_move<kDppRowShr + 8>(0, v));
     v = max(v, dpp_move<kDppRowBcast15, 0xA>(0, v));
     v = max(v, dpp_move<kDppRowBcast31, 0xC>(0, v));
-    return (u32)__builtin_amdgcn_readlane((int)v, 63);
+    return v;
+}
+__device__ __forceinline__ u32 wave_reduce_max(u32 v)
+{
+    return (u32)__builtin_amdgcn_readlane((int)wave_inclusive_max(v), 63);
 }
 __device__ __forceinline__ u32 wave_reduce_min(u32 v)
 {

@@ -33,6 +33,7 @@
 #include "select.hpp"
 #include "add.hpp"
 #include "reduce.hpp"
+#include "scale.hpp"
 #include "sort_rows.hpp"
 
 using namespace speck;
@@ -237,6 +238,7 @@ struct speck_config {
     SelectScratch select;  // ... and of speck_select_* (select.hip)
     AddScratch add;  // ... and of speck_add_* (add.hip)
     ReduceScratch reduce;  // ... and of speck_reduce_* (reduce.hip)
+    ScaleScratch scale;  // ... and of speck_scale_* (scale.hip)
     const void* zones_arena = nullptr;
     u64 zones_m = 0, zones_nnz = 0, zones_gap = 0;
     bool gpool_zones_filled = false;
@@ -1925,6 +1927,7 @@ MaskedScratch* masked_scratch(speck_config* c) { return &c->masked; }
 SelectScratch* select_scratch(speck_config* c) { return &c->select; }
 AddScratch* add_scratch(speck_config* c) { return &c->add; }
 ReduceScratch* reduce_scratch(speck_config* c) { return &c->reduce; }
+ScaleScratch* scale_scratch(speck_config* c) { return &c->scale; }
 }  // namespace speck
 
 extern "C" {
@@ -2042,6 +2045,7 @@ int speck_config_destroy(speck_config* c)
     c->select.release();
     c->add.release();
     c->reduce.release();
+    c->scale.release();
     if (c->pred.off) (void)guarded_free(c->pred.off);
     if (c->gpred.off) (void)guarded_free(c->gpred.off);
     if (c->d_stats) (void)hipFree(c->d_stats);
@@ -2127,6 +2131,7 @@ int speck_config_set_option(speck_config* c, const char* name, int64_t value)
         c->select.release();
         c->add.release();
         c->reduce.release();
+        c->scale.release();
     }
     else if (n == "sort_reg_max") c->sort.reg_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_REG_MAX);
     else if (n == "sort_lds_max") c->sort.lds_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_LDS_MAX);

@@ -4,7 +4,8 @@
 //   reduce_check_kernel    a thread per row: the offsets ascend, stay inside [row_offsets[0], row_offsets[0] + nnz] and the
 //                          last one spans nnz; counts the rows without an entry.  Raises the verdict in the status block.
 //                          A row that holds the first or the last entry of a tile says so in the tile's two words: the
-//                          tile pass searches nothing (a search was four dependent loads in front of every tile).
+//                          tile pass searches nothing (a search was four dependent loads in front of every tile).  The
+//                          check of a row is entry_tiles.hpp's: the scaling walks the same tiles.
 //   reduce_tile_kernel     queued behind it, looks at the verdict first (and does nothing where it is raised: no offset is
 //                          used as an address before it was checked, and there is no read-back in between).  A workgroup
 //                          per ENTRY TILE: the absolute entries [4096 t, 4096 (t + 1)) of `data`, clipped to the matrix.
@@ -27,6 +28,7 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "entry_tiles.hpp"
 #include "launch.hpp"
 #include "reduce.hpp"
 #include "row_tiles.hpp"
@@ -134,24 +136,9 @@ __global__ __launch_bounds__(kThreads) void reduce_check_kernel(const u32* __res
     if (threadIdx.x == 0) s_empty = 0;
     if (r == 0) st->base = base;
     __syncthreads();
-    u32 empty = 0;
-    if (r < rows) {
-        const u32 a = ro[r], b = ro[r + 1];
-        bool bad = a > b || a < base || u64(b) - base > nnz;  // (b < base wraps to more than any nnz)
-        if (r == rows - 1u) bad |= u64(b) - base != nnz;
-        if (bad) st->invalid = 1;
-        empty = a == b;
-        if (!bad && a < b) {  // (its own offsets are sound: at most as many trips as the matrix has tiles)
-            const u64 end = u64(base) + nnz, t_first = base / kTile;
-            for (u64 k = a / kTile; k <= (u64(b) - 1) / kTile; ++k) {
-                const u64 i = k - t_first, lo = std::max<u64>(k * kTile, base), hi = std::min<u64>((k + 1) * kTile, end);
-                if (i >= max_tiles) break;  // (cannot happen: the entries of the row lie inside the matrix)
-                if (a <= lo) tile_rows[2 * i] = r;
-                if (hi <= b) tile_rows[2 * i + 1] = r;
-            }
-        }
-    }
-    block_counter_to(&st->rows_empty, empty, &s_empty);
+    bool empty = false;
+    if (r < rows && !row_offsets_sound<kTile>(ro, r, rows, base, nnz, max_tiles, tile_rows, &empty)) st->invalid = 1;
+    block_counter_to(&st->rows_empty, (u32)empty, &s_empty);
 }
 
 // ------------------------------------------------------------------------------------------------ tiles
@@ -342,8 +329,7 @@ double identity_of(int op)
 template <typename T>
 int reduce_run(ReduceScratch* sc, hipStream_t s, const speck_dcsr* A, int op, double* d_row_out, ReduceStatus* h)
 {
-    // a range of nnz entries touches one tile more than it fills at most: its place is known on the device only
-    const u32 max_tiles = A->nnz ? (u32)((A->nnz + kTile - 1) / kTile + 1) : 0u;
+    const u32 max_tiles = entry_tiles_at_most(A->nnz, kTile);
     int rc = sc->fixed.ensure(256);
     if (rc != SPECK_OK) return rc;
     const size_t rec_bytes = up256(size_t(std::max(max_tiles, 1u)) * sizeof(TileRec));
