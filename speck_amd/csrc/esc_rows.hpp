@@ -69,21 +69,35 @@ __device__ __forceinline__ u32 num_esc_row(const SubWave<L>& g, unsigned char* m
         ends = (u64(esc_row_or((u32)(bit >> 32))) << 32) | esc_row_or((u32)bit);
     }
     wave_lds_fence();
-    u32 key[PER];
+    // (the loads of all PER products first, their uses behind them: with load and use under one `if` the compiler waits
+    //  for product u before it requests product u + 1 -- PER round trips per row where one does)
+    u32 key[PER], c[PER];
+    T bv[PER];
+    Acc<T> a[PER];
 #pragma unroll
     for (u32 u = 0; u < PER; ++u) {
         const u32 p = u * L + gl;
-        key[u] = kEscInvalid;
+        c[u] = 0;
+        bv[u] = T(0);
+        a[u] = 0;
         if (p < total) {
             u32 j;
             if constexpr (L <= 8) j = (u32)__popc(ends & ((2u << p) - 1u));
             else j = (u32)__popcll(ends & ((2ull << p) - 1ull));
             const u32 ib = s_off[j] + p;
-            const u32 c = src.b_col[ib];
-            const T bv = src.b_val[ib];
-            const T prod = (T)s_av[j] * bv;  // rounded product, added later (no FMA across the add)
+            c[u] = src.b_col[ib];
+            bv[u] = src.b_val[ib];
+            a[u] = s_av[j];
+        }
+    }
+#pragma unroll
+    for (u32 u = 0; u < PER; ++u) {
+        const u32 p = u * L + gl;
+        key[u] = kEscInvalid;
+        if (p < total) {
+            const T prod = (T)a[u] * bv[u];  // rounded product, added later (no FMA across the add)
             s_vals[p] = (Acc<T>)prod;
-            key[u] = (c << TAG) | p;
+            key[u] = (c[u] << TAG) | p;
         }
     }
     wave_lds_fence();

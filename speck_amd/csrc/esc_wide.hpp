@@ -207,19 +207,32 @@ __device__ __forceinline__ u32 num_escw_row(const SubWave<L>& g, unsigned char* 
         s_av[before] = av;
     }
     ends.build(g, nonempty, incl);  // (fences inside: the staging above is visible as well)
-    u32 key[PER];
+    // (the loads of all PER products first, their uses behind them: esc_rows.hpp)
+    u32 key[PER], c[PER];
+    T bv[PER];
+    Acc<T> a[PER];
+#pragma unroll
+    for (u32 u = 0; u < PER; ++u) {
+        const u32 p = u * L + gl;
+        c[u] = 0;
+        bv[u] = T(0);
+        a[u] = 0;
+        if (p < total) {
+            const u32 j = ends.owner(p);
+            const u32 ib = s_off[j] + p;
+            c[u] = src.b_col[ib];
+            bv[u] = src.b_val[ib];
+            a[u] = s_av[j];
+        }
+    }
 #pragma unroll
     for (u32 u = 0; u < PER; ++u) {
         const u32 p = u * L + gl;
         key[u] = kEscInvalid;
         if (p < total) {
-            const u32 j = ends.owner(p);
-            const u32 ib = s_off[j] + p;
-            const u32 c = src.b_col[ib];
-            const T bv = src.b_val[ib];
-            const T prod = (T)s_av[j] * bv;  // rounded product, added later (no FMA across the add)
+            const T prod = (T)a[u] * bv[u];  // rounded product, added later (no FMA across the add)
             s_vals[p] = (Acc<T>)prod;
-            key[u] = ((c - cmin) << TAG) | p;
+            key[u] = ((c[u] - cmin) << TAG) | p;
         }
     }
     wave_lds_fence();
