@@ -24,7 +24,7 @@ KEYS = [
     (r"analysis_kernel<\d+, \d+u, true>", "analysis_verify_reuse"), (r"verify_inputs_kernel", "verify_inputs_reuse"),
     (r"snapshot_inputs_kernel", "snapshot_inputs_reuse"),
     (r"sym_light_fused_kernel", "sym_light_fused_reuse"), (r"sym_light_kernel", "sym_light"),
-    (r"num_hash_kernel<Block<512>", "num_block8k"), (r"num_hash_kernel<Block<256>", "num_block2k"),
+    (r"num_hash_kernel<Block<512>", "num_block8k"),
     (r"num_dense_kernel<\w+, 16384u", "num_dense16k"),
     (r"num_spill_scatter_kernel", "num_global_scatter"), (r"num_spill_count_kernel", "num_global_count"),
     (r"num_spill_reduce_kernel<\w+, 2048u", "num_global_reduce"), (r"num_spill_reduce_kernel<\w+, 8192u", "num_global_reduce_big"),

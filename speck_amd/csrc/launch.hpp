@@ -189,6 +189,74 @@ __device__ __forceinline__ void store_row_count(const RowWork& w, u32* __restric
 }
 #endif
 
+// ---- the classes of a phase: declared HERE, once -----------------------------------------------------------
+// A class is LIGHT (256 threads, <= ~40 KiB of LDS: a slot of the phase's one merged launch) or HEAVY (launches of its
+// own, launch_symbolic / launch_numeric_first / launch_numeric).  The light table gives the slots of the merged launch in
+// launch order, heaviest first, with the rows a workgroup of the class takes at a time; the order gives the items
+// run_classes (pipeline.hip) schedules, heaviest first, the merged launch last.  Masks, block ranges, LDS sizes and the
+// device-side branches are derived from these tables or asserted against them; a class in neither table of its phase does
+// not compile (below).
+struct ClassSlot {
+    int cls;
+    u32 rows;  // rows per workgroup = groups of lanes per 256 threads
+};
+constexpr int kLight = -1;  // pseudo class of an order: the merged launch of the phase's light table
+constexpr ClassSlot kSymLight[] = {{SYM_BM1, 1}, {SYM_B4K, 1}, {SYM_W1K, 4},   {SYM_W256, 8}, {SYM_R64, 4},
+                                   {SYM_R32, 8}, {SYM_W128, 16}, {SYM_G16, 16}, {SYM_G8, 32}};
+constexpr int kSymOrder[] = {SYM_GH, SYM_BM2, SYM_B32K, SYM_B16K, SYM_NF, kLight};
+constexpr ClassSlot kNumLight[] = {{NUM_D1, 1},  {NUM_B2K, 1},  {NUM_W512, 4}, {NUM_W256, 8}, {NUM_R64, 4},
+                                   {NUM_R32, 8}, {NUM_W128, 8}, {NUM_G16, 16}, {NUM_G8, 32},  {NUM_DIRECT, 256}};
+constexpr int kNumOrder[] = {NUM_G, NUM_D2, NUM_B8K, NUM_NFCOPY, kLight};
+// num_tiny_kernel carries the slots from this one on: the launch of a call without rows in the slots before it
+constexpr u32 kNumTinyFirst = 4;
+
+template <size_t N>
+constexpr u32 class_mask(const ClassSlot (&t)[N], size_t from = 0, size_t to = N)
+{
+    u32 m = 0;
+    for (size_t k = from; k < to; ++k) m |= 1u << t[k].cls;
+    return m;
+}
+template <size_t N>
+constexpr u32 class_mask(const int (&order)[N])  // (without kLight)
+{
+    u32 m = 0;
+    for (int c : order) m |= c < 0 ? 0u : 1u << c;
+    return m;
+}
+template <size_t N>
+constexpr u32 class_rows(const ClassSlot (&t)[N], int cls)  // 0: not a light class
+{
+    for (const ClassSlot& s : t)
+        if (s.cls == cls) return s.rows;
+    return 0;
+}
+// slot k of `t`, from slot FROM on, holds class cls[k - FROM]: written in front of every device-side chain of branches
+template <size_t FROM = 0, size_t N, typename... C>
+constexpr bool slots_are(const ClassSlot (&t)[N], C... cls)
+{
+    const int want[] = {int(cls)...};
+    if (FROM + sizeof...(C) != N) return false;
+    for (size_t k = FROM; k < N; ++k)
+        if (t[k].cls != want[k - FROM]) return false;
+    return true;
+}
+constexpr size_t popcount32(u32 x) { return x ? 1 + popcount32(x & (x - 1u)) : 0; }
+
+constexpr u32 kSymLightMask = class_mask(kSymLight), kSymHeavyMask = class_mask(kSymOrder);
+constexpr u32 kNumLightMask = class_mask(kNumLight), kNumHeavyMask = class_mask(kNumOrder);
+constexpr u32 kNumBigLightMask = class_mask(kNumLight, 0, kNumTinyFirst);  // what num_tiny_kernel does NOT carry
+constexpr size_t kSymLightSlots = sizeof(kSymLight) / sizeof(kSymLight[0]);
+constexpr size_t kNumLightSlots = sizeof(kNumLight) / sizeof(kNumLight[0]);
+static_assert(popcount32(kSymLightMask) == kSymLightSlots && popcount32(kNumLightMask) == kNumLightSlots,
+              "a class has two slots");
+static_assert(popcount32(kSymHeavyMask) + 1 == sizeof(kSymOrder) / sizeof(int) &&
+                  popcount32(kNumHeavyMask) + 1 == sizeof(kNumOrder) / sizeof(int),
+              "a class is launched twice (or the merged launch is missing from an order)");
+static_assert((kSymLightMask & kSymHeavyMask) == 0 && (kNumLightMask & kNumHeavyMask) == 0, "a class is light AND heavy");
+static_assert((kSymLightMask | kSymHeavyMask) == (1u << SYM_CLASSES) - 1u, "a symbolic class that nothing launches");
+static_assert((kNumLightMask | kNumHeavyMask) == (1u << NUM_CLASSES) - 1u, "a numeric class that nothing launches");
+
 // Block ranges of the classes inside a merged ("light") launch: class slot k owns the blocks [first[k], first[k+1]);
 // cnt[k] = the rows the host expects in the slot's class (exact when the structure is what it was at the last read-back /
 // in the previous call; ~0: unknown): a workgroup requests its first list entries by it BEFORE the device-side class
@@ -197,14 +265,19 @@ struct ClassGrid {
     u32 first[13];
     u32 cnt[12];
 };
+// (one range more than slots: the workgroups of the numeric launch that move the staged row offsets; plan_light)
+static_assert(kNumLightSlots + 2 <= sizeof(ClassGrid::first) / sizeof(u32) && kSymLightSlots + 2 <= sizeof(ClassGrid::first) / sizeof(u32) &&
+                  kNumLightSlots <= sizeof(ClassGrid::cnt) / sizeof(u32) && kSymLightSlots <= sizeof(ClassGrid::cnt) / sizeof(u32),
+              "ClassGrid is too small for a light table");
 constexpr u32 kNoCount = 0xFFFFFFFFu;
-constexpr u32 kSymLightMask = (1u << SYM_BM1) | (1u << SYM_B4K) | (1u << SYM_W1K) | (1u << SYM_W256) | (1u << SYM_G16) |
-                              (1u << SYM_G8) | (1u << SYM_W128) | (1u << SYM_R32) | (1u << SYM_R64);
-constexpr u32 kNumLightMask = (1u << NUM_D1) | (1u << NUM_B2K) | (1u << NUM_W512) | (1u << NUM_W256) | (1u << NUM_W128) |
-                              (1u << NUM_G16) | (1u << NUM_G8) | (1u << NUM_DIRECT) | (1u << NUM_R32) | (1u << NUM_R64);
 // the register classes (esc.hpp, esc_wide.hpp): their rows are finished in the symbolic phase of a fused replay
 constexpr u32 kNumEscMask = (1u << NUM_G8) | (1u << NUM_G16) | (1u << NUM_R32) | (1u << NUM_R64);
 constexpr u32 kSymEscMask = (1u << SYM_G8) | (1u << SYM_G16) | (1u << SYM_R32) | (1u << SYM_R64);
+// ... by the numeric body of the class with the same group of lanes (so the same rows per workgroup): the LDS is that class'
+constexpr int fused_num_class(int sym_cls)
+{
+    return sym_cls == SYM_G8 ? NUM_G8 : sym_cls == SYM_G16 ? NUM_G16 : sym_cls == SYM_R32 ? NUM_R32 : sym_cls == SYM_R64 ? NUM_R64 : -1;
+}
 
 // One launch for all 256-thread classes in `mask`.  counts_hint[cls] sizes each class' block range
 // (the kernels read the real counts on the device and stride, so a stale hint only costs speed).
@@ -219,9 +292,9 @@ void launch_numeric_light(hipStream_t s, const u32* counts_hint, u32 mask, const
                           const CsrView<T>& B, const RowWork& w, u32* c_col, T* c_val, int cu_count,
                           bool exact = false, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 
-// Launch the symbolic kernel of class `cls`.  `count` is an UPPER BOUND of the class' row count
-// (the rows of A): the grid depends only on it, the kernels read the real count from the
-// device-side stats block, so the launch sequence is static.
+// Launch the symbolic kernel of the HEAVY class `cls` (kSymOrder; SYM_NF: launch_numeric_first).  `count` is an UPPER
+// BOUND of the class' row count (the rows of A): the grid depends only on it, the kernels read the real count from the
+// device-side stats block, so the launch sequence is static.  Any other class: the launch error is latched.
 void launch_symbolic(hipStream_t s, int cls, u32 count, const u32* a_ro, const uint2* b_sl,
                      const u32* b_col, const RowWork& w, u32* counts, int cu_count);
 
@@ -253,7 +326,7 @@ int take_launch_error();  // the first failure since the last call (0: none); cl
         ::speck::note_launch_status(hipGetLastError(), #kernel_);                                          \
     } while (0)
 
-// Launch the numeric kernel of class `cls` (same convention for `count`).
+// Launch the numeric kernel(s) of the HEAVY class `cls` (kNumOrder; same convention for `count`, same answer to any other class).
 template <typename T>
 void launch_numeric(hipStream_t s, int cls, u32 count, const CsrView<T>& A, const CsrView<T>& B,
                     const RowWork& w, u32* c_col, T* c_val, int cu_count);
@@ -263,6 +336,39 @@ void launch_walk(hipStream_t s, const WalkArgs& args, const ProductSrc<T>& src, 
                  hipEvent_t e1 = nullptr);
 
 u32 grid_for(u32 count, u32 lds, int threads, int cu_count, u32 rows_per_block);
+
+// kernels above 64 KiB of LDS need the opt-in (a workgroup may own all 160 KiB on gfx950)
+template <typename K>
+void set_dyn_lds(K kernel, u32 bytes)
+{
+    if (bytes > 48 * 1024)
+        note_launch_status(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes),
+                           "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+}
+
+// The block ranges and the LDS bytes of a merged launch: every class of `mask` sizes the LDS (class_lds(cls)), every one
+// with rows by its hint gets blocks; `extra` blocks follow the last slot (range N).  false: no block at all -- nothing is
+// launched, and a caller that times the launch has got an empty interval.
+template <size_t N, typename LdsFn>
+bool plan_light(const ClassSlot (&tab)[N], u32 mask, const u32* counts_hint, bool exact, int cu_count, LdsFn&& class_lds,
+                u32 extra, hipStream_t s, hipEvent_t e0, hipEvent_t e1, ClassGrid* cg, u32* lds)
+{
+    *lds = 0;
+    for (const ClassSlot& t : tab)
+        if (mask >> t.cls & 1u) *lds = *lds > class_lds(t.cls) ? *lds : class_lds(t.cls);
+    *cg = ClassGrid{};
+    for (size_t k = 0; k < N; ++k) {
+        const u32 hint = counts_hint[tab[k].cls];
+        const bool on = (mask >> tab[k].cls & 1u) && hint;
+        cg->first[k + 1] = cg->first[k] + (on ? grid_for(hint, *lds, 256, cu_count, tab[k].rows) : 0u);
+        cg->cnt[k] = exact ? hint : kNoCount;
+    }
+    cg->first[N + 1] = cg->first[N] + extra;
+    if (cg->first[N + 1] != 0) return true;
+    if (e0) (void)hipEventRecord(e0, s), (void)hipEventRecord(e1, s);
+    return false;
+}
 // resident-set multiples a class grid may reach before its workgroups start striding over rows
 void set_grid_rounds(u32 block_classes, u32 subwave_classes);
 void set_b8k_full_first(u32 mask);  // NUM_B8K: the full-table launch in front of the half-table one (bit 0 complete calls, bit 1 reuse)

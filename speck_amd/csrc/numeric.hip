@@ -1060,22 +1060,11 @@ __global__ __launch_bounds__(256) void nf_copy_kernel(RowWork w, u32* __restrict
 }
 
 // ------------------------------------------------------------------ kernels
-// Stand-alone kernels (one class per launch) and the merged "light" kernel: all classes whose
-// workgroups are 256 threads wide and need <= ~40 KiB of LDS share ONE launch -- block ranges map
+// The kernels of the heavy classes (one class per launch, kNumOrder) and the merged "light" kernel: all classes whose
+// workgroups are 256 threads wide and need <= ~40 KiB of LDS (kNumLight) share ONE launch -- block ranges map
 // to classes (ClassGrid), heaviest class first.  One launch instead of up to six removes the
 // cross-queue fork/join hand-offs (~15 us each on MI355X) and lets the dispatcher interleave
 // workgroups of different classes on a CU.
-template <typename T, int THREADS>
-__global__ __launch_bounds__(THREADS) void num_direct_kernel(ProductSrc<T> src, const u32* a_ro, RowWork w,
-                                                             u32* __restrict__ c_col,
-                                                             T* __restrict__ c_val)
-{
-    SPECK_POISON();
-    src.rebase(a_ro);
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    num_direct_body<T, THREADS>(smem, src, w, c_col, c_val, blockIdx.x, gridDim.x);
-}
-
 template <class G, typename T, u32 CAP, u32 W1, u32 NMAX, int MODE, int THREADS, u32 NLO = 0, bool VERIFY = false>
 __global__ __launch_bounds__(THREADS) void num_hash_kernel(ProductSrc<T> src, const u32* a_ro, RowWork w,
                                                            u32* __restrict__ c_col,
@@ -1109,27 +1098,6 @@ __global__ __launch_bounds__(THREADS) void num_dense_kernel(ProductSrc<T> src, c
     num_dense_body<T, WCOLS, THREADS, VERIFY>(smem, src, w, c_col, c_val, cls, blockIdx.x, gridDim.x);
 }
 
-template <typename T, u32 L>
-__global__ __launch_bounds__(256) void num_esc_kernel(ProductSrc<T> src, const u32* a_ro, RowWork w,
-                                                      u32* __restrict__ c_col, T* __restrict__ c_val, int cls)
-{
-    SPECK_POISON();
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    src.rebase(a_ro);
-    num_esc_body<T, L, 256>(smem, src, w, c_col, c_val, cls, blockIdx.x, gridDim.x);
-}
-
-template <typename T, u32 L>
-__global__ __launch_bounds__(256) void num_escw_kernel(ProductSrc<T> src, const u32* a_ro, RowWork w,
-                                                       u32* __restrict__ c_col, T* __restrict__ c_val, int cls)
-{
-    SPECK_POISON();
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    src.rebase(a_ro);
-    num_escw_body<T, L, 256>(smem, src, w, c_col, c_val, cls, blockIdx.x, gridDim.x);
-}
-
-
 // WITH_ESC = false: the launch of a sequence whose register-class rows are finished in its symbolic phase (fused
 // replay) -- those bodies are not even compiled in, and the kernel carries another NAME than the launch of an eager
 // call, so that a kernel trace tells the two apart (profiles/: per-kernel averages of the replayed sequence alone).
@@ -1144,7 +1112,8 @@ __global__ __launch_bounds__(256) void num_light_kernel(ProductSrc<T> src, const
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     src.rebase(a_ro);
     const u32 b = blockIdx.x;
-    // launch order (ClassGrid slots): D1, B2K, W512, W256, R64, R32, W128, G16, G8, DIRECT
+    // branch k below = slot k of the launch (ClassGrid); the range behind the last slot moves the row offsets
+    static_assert(slots_are(kNumLight, NUM_D1, NUM_B2K, NUM_W512, NUM_W256, NUM_R64, NUM_R32, NUM_W128, NUM_G16, NUM_G8, NUM_DIRECT));
     // (every body starts with open_list: its first row ids are requested by the host-known count while the
     //  device-side table and the capacity_miss flag are still on their way)
     if (b < cg.first[1])
@@ -1362,6 +1331,8 @@ __global__ __launch_bounds__(256) void num_tiny_kernel(ProductSrc<T> src, const 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     src.rebase(a_ro);
     const u32 b = blockIdx.x;
+    // (the slots in front of kNumTinyFirst are empty -- launch_numeric_light --, the others keep their numbers)
+    static_assert(kNumTinyFirst == 4 && slots_are<kNumTinyFirst>(kNumLight, NUM_R64, NUM_R32, NUM_W128, NUM_G16, NUM_G8, NUM_DIRECT));
     if (b < cg.first[5])
         num_escw_body<T, 64, 256>(smem, src, w, c_col, c_val, NUM_R64, b - cg.first[4], cg.first[5] - cg.first[4], cg.cnt[4]);
     else if (b < cg.first[6])
@@ -1821,15 +1792,21 @@ __global__ __launch_bounds__(256) void num_spill_copy_kernel(RowWork w, u32* __r
 template <typename T>
 u32 numeric_lds_bytes_t(int cls)
 {
+    const u32 groups = class_rows(kNumLight, cls);  // of the sub-wave classes: a group of lanes per row
+    static_assert(class_rows(kNumLight, NUM_G8) == 256 / 8 && class_rows(kNumLight, NUM_G16) == 256 / 16 &&
+                      class_rows(kNumLight, NUM_R32) == 256 / 32 && class_rows(kNumLight, NUM_R64) == 256 / 64 &&
+                      class_rows(kNumLight, NUM_W128) == 256 / 32 && class_rows(kNumLight, NUM_W256) == 256 / 32 &&
+                      class_rows(kNumLight, NUM_W512) == 256 / 64 && class_rows(kNumLight, NUM_DIRECT) == 256,
+                  "rows per workgroup = 256 threads / the lanes of the class' group (the bodies in num_light_kernel)");
     switch (cls) {
         case NUM_DIRECT: return num_direct_lds<T, 256>();
-        case NUM_G8: return 32 * num_esc_group_lds<T, 8>();
-        case NUM_G16: return 16 * num_esc_group_lds<T, 16>();
-        case NUM_R32: return 8 * num_escw_group_lds<T, 32>();
-        case NUM_R64: return 4 * num_escw_group_lds<T, 64>();
-        case NUM_W128: return 8 * num_group_lds<SubWave<32>, T, kNumW128Cap, 256>();
-        case NUM_W512: return 4 * num_group_lds<SubWave<64>, T, kNumW512Cap, 256>();
-        case NUM_W256: return 8 * num_group_lds<SubWave<32>, T, kNumW256Cap, 256>();
+        case NUM_G8: return groups * num_esc_group_lds<T, 8>();
+        case NUM_G16: return groups * num_esc_group_lds<T, 16>();
+        case NUM_R32: return groups * num_escw_group_lds<T, 32>();
+        case NUM_R64: return groups * num_escw_group_lds<T, 64>();
+        case NUM_W128: return groups * num_group_lds<SubWave<32>, T, kNumW128Cap, 256>();
+        case NUM_W512: return groups * num_group_lds<SubWave<64>, T, kNumW512Cap, 256>();
+        case NUM_W256: return groups * num_group_lds<SubWave<32>, T, kNumW256Cap, 256>();
         case NUM_B2K: return num_group_lds<Block<256>, T, kNumB2KCap, 256>();
         case NUM_B8K: return num_group_lds<Block<512>, T, kNumB8KCap, 512>();
         case NUM_D1: return num_dense_lds<T, kNumD1Win, 256>();
@@ -1843,15 +1820,6 @@ u32 numeric_lds_bytes_t(int cls)
 u32 numeric_lds_bytes(int cls, u32 vsize)
 {
     return vsize == 8 ? numeric_lds_bytes_t<double>(cls) : numeric_lds_bytes_t<float>(cls);
-}
-
-template <typename K>
-static void set_dyn_lds(K kernel, u32 bytes)
-{
-    if (bytes > 48 * 1024)
-        note_launch_status(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes),
-                           "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
 }
 
 template <class G, typename T, u32 CAP, u32 W1, u32 NMAX, int MODE, int THREADS, u32 NLO = 0, bool VERIFY = false>
@@ -1870,38 +1838,64 @@ void set_b8k_full_first(u32 mask) { g_b8k_full_first = mask; }
 static u32 g_spill_big_grid = 256;
 void set_spill_big_grid(u32 blocks) { g_spill_big_grid = blocks ? blocks : 256u; }
 
+// NUM_B8K.  Two launches over the class: the rows of the lower half fit a half-size table, whose workgroups run two per CU
+// (the full table owns 106 of a CU's 160 KiB).  A handful of rows cannot fill the CUs anyway: one launch, one row's
+// latency less.
+// The full table first: a workgroup of 106 KiB finds room on a CU only while the light launch beside it has not filled the
+// chip -- webbase stand-in 1.176 -> 1.158 ms complete, three alternating pairs; the verifying launches of a reuse sequence
+// keep the half table first: 0.788 against 0.868 ms.  Option b8k_full_first.
+template <typename T, bool VERIFY>
+static void launch_b8k(hipStream_t s, u32 count, const ProductSrc<T>& A, const u32* B, const RowWork& w, u32* c_col,
+                       T* c_val, int cu_count)
+{
+    constexpr int cls = NUM_B8K;
+    if (w.sliced) {  // in column slices of the 2 Ki table (num_sliced_body)
+        const u32 sl = num_sliced_lds(num_group_lds<Block<256>, T, kNumB2KCap, 256>());
+        SPECK_LAUNCH((num_sliced_kernel<T, VERIFY>), dim3(grid_for(count, sl, 256, cu_count, 1)), dim3(256), sl, s, A, B, w,
+                     c_col, c_val, cls);
+        return;
+    }
+    // the full table for every row of the class / for the rows beyond the half table; the half table for the others
+    const auto all = launch_num_hash<Block<512>, T, kNumB8KCap, kB8KW1, kNumB8KMaxNnz, SORT_BITMAP, 512, 0, VERIFY>;
+    const auto upper = launch_num_hash<Block<512>, T, kNumB8KCap, kB8KW1, kNumB8KMaxNnz, SORT_BITMAP, 512, kNumB8KHalfMaxNnz, VERIFY>;
+    const auto lower = launch_num_hash<Block<512>, T, kNumB8KCap / 2, kB8KW1, kNumB8KHalfMaxNnz, SORT_BITMAP, 512, 0, VERIFY>;
+    if (count * 2 < (u32)cu_count) {
+        all(s, cls, count, A, B, w, c_col, c_val, cu_count);
+        return;
+    }
+    const bool full_first = (g_b8k_full_first & (VERIFY ? 2u : 1u)) != 0;
+    if (full_first) upper(s, cls, count, A, B, w, c_col, c_val, cu_count);
+    lower(s, cls, count, A, B, w, c_col, c_val, cu_count);
+    if (!full_first) upper(s, cls, count, A, B, w, c_col, c_val, cu_count);
+}
+
+template <typename T, bool VERIFY>
+static void launch_d2(hipStream_t s, u32 count, const ProductSrc<T>& A, const u32* B, const RowWork& w, u32* c_col,
+                      T* c_val, int cu_count)
+{
+    auto k = num_dense_kernel<T, kNumD2Cols, 1024, VERIFY>;
+    const u32 lds = numeric_lds_bytes_t<T>(NUM_D2);
+    set_dyn_lds(k, lds);
+    SPECK_LAUNCH(k, dim3(grid_for(count, lds, 1024, cu_count, 1)), dim3(1024), lds, s, A, B, w, c_col, c_val, (int)NUM_D2);
+}
+
 template <typename T>
 void launch_numeric_light(hipStream_t s, const u32* counts_hint, u32 mask, const CsrView<T>& Av,
                           const CsrView<T>& Bv, const RowWork& w, u32* c_col, T* c_val, int cu_count, bool exact,
                           hipEvent_t e0, hipEvent_t e1)
 {
-    constexpr int NS = 10;
-    static const int slots[NS] = {NUM_D1, NUM_B2K, NUM_W512, NUM_W256, NUM_R64, NUM_R32, NUM_W128, NUM_G16, NUM_G8, NUM_DIRECT};
-    static const u32 rows_per_block[NS] = {1, 1, 4, 8, 4, 8, 8, 16, 32, 256};
-    bool tiny_only = true;
-    for (int k = 0; k < 4; ++k)
-        if ((mask >> slots[k] & 1u) && counts_hint[slots[k]]) tiny_only = false;
-    if (w.verify_numeric || w.off_n) tiny_only = false;  // (only the big kernel has verifying bodies / moves the offsets)
-    u32 lds = 0;
-    for (int k = 0; k < NS; ++k)
-        if (mask >> slots[k] & 1u) lds = std::max(lds, numeric_lds_bytes_t<T>(slots[k]));
-    ClassGrid cg{};
-    for (int k = 0; k < NS; ++k) {
-        const bool on = (mask >> slots[k] & 1u) && counts_hint[slots[k]];
-        cg.first[k + 1] = cg.first[k] + (on ? grid_for(counts_hint[slots[k]], lds, 256, cu_count, rows_per_block[k]) : 0u);
-        cg.cnt[k] = exact ? counts_hint[slots[k]] : kNoCount;
-    }
-    // ... + the workgroups that move the staged row offsets (only the big kernel carries them)
-    cg.first[NS + 1] = cg.first[NS];
-    if (!tiny_only && w.off_n) cg.first[NS + 1] += std::min<u32>((w.off_n + 2047u) / 2048u, 512u);
-    if (cg.first[NS + 1] == 0) {
-        if (e0) (void)hipEventRecord(e0, s), (void)hipEventRecord(e1, s);  // (nothing to time: an empty interval)
-        return;
-    }
+    constexpr size_t NS = kNumLightSlots;
+    // ... + the workgroups that move the staged row offsets
+    const u32 off_blocks = w.off_n ? std::min<u32>((w.off_n + 2047u) / 2048u, 512u) : 0u;
+    ClassGrid cg;
+    u32 lds;
+    if (!plan_light(kNumLight, mask, counts_hint, exact, cu_count, numeric_lds_bytes_t<T>, off_blocks, s, e0, e1, &cg, &lds)) return;
+    // (only the big kernel has verifying bodies / moves the offsets)
+    const bool tiny_only = cg.first[kNumTinyFirst] == 0 && !w.verify_numeric && !w.off_n;
     const ProductSrc<T> src{w.b_sl, Av.data, Bv.col_ids, Bv.data, w.w_sl};
     bool with_esc = false;  // (a class of the mask without rows has no blocks: its body is never entered)
-    for (int k = 0; k < NS; ++k)
-        if ((kNumEscMask >> slots[k] & 1u) && cg.first[k + 1] != cg.first[k]) with_esc = true;
+    for (size_t k = 0; k < NS; ++k)
+        if ((kNumEscMask >> kNumLight[k].cls & 1u) && cg.first[k + 1] != cg.first[k]) with_esc = true;
     if (w.verify_numeric)  // (pipeline.hip plans such a sequence only when this launch has workgroup / wave classes and no
                            //  register-class rows of its own)
         SPECK_LAUNCH_TIMED((num_light_kernel<T, false, true>), dim3(cg.first[NS + 1]), dim3(256), lds, s, e0, e1, src,
@@ -1948,114 +1942,19 @@ void launch_numeric(hipStream_t s, int cls, u32 count, const CsrView<T>& Av, con
     // (A, B) below = (product source, A.row_offsets): the kernels rebase the per-entry arrays
     const ProductSrc<T> A{w.b_sl, Av.data, Bv.col_ids, Bv.data, w.w_sl};
     const u32* B = Av.row_offsets;
-    const u32 lds = numeric_lds_bytes_t<T>(cls);
     switch (cls) {
-        case NUM_DIRECT: {
-            constexpr int TH = 256;
-            SPECK_LAUNCH((num_direct_kernel<T, TH>), dim3(grid_for(count, lds, TH, cu_count, TH)),
-                               dim3(TH), lds, s, A, B, w, c_col, c_val);
-            break;
-        }
-        case NUM_G8:
-            SPECK_LAUNCH((num_esc_kernel<T, 8>), dim3(grid_for(count, lds, 256, cu_count, 32)), dim3(256), lds, s, A, B,
-                               w, c_col, c_val, cls);
-            break;
-        case NUM_G16:
-            SPECK_LAUNCH((num_esc_kernel<T, 16>), dim3(grid_for(count, lds, 256, cu_count, 16)), dim3(256), lds, s, A, B,
-                               w, c_col, c_val, cls);
-            break;
-        case NUM_R32:
-            SPECK_LAUNCH((num_escw_kernel<T, 32>), dim3(grid_for(count, lds, 256, cu_count, 8)), dim3(256), lds, s, A, B,
-                               w, c_col, c_val, cls);
-            break;
-        case NUM_R64:
-            SPECK_LAUNCH((num_escw_kernel<T, 64>), dim3(grid_for(count, lds, 256, cu_count, 4)), dim3(256), lds, s, A, B,
-                               w, c_col, c_val, cls);
-            break;
-        case NUM_W128:
-            launch_num_hash<SubWave<32>, T, kNumW128Cap, 0, kNumW128MaxNnz, SORT_RANK, 256>(
-                s, cls, count, A, B, w, c_col, c_val, cu_count);
-            break;
-        case NUM_W512:
-            launch_num_hash<SubWave<64>, T, kNumW512Cap, kW512W1, kNumW512MaxNnz, SORT_BITMAP, 256>(
-                s, cls, count, A, B, w, c_col, c_val, cu_count);
-            break;
-        case NUM_W256:
-            launch_num_hash<SubWave<32>, T, kNumW256Cap, kW256W1, kNumW256MaxNnz, SORT_BITMAP, 256>(
-                s, cls, count, A, B, w, c_col, c_val, cu_count);
-            break;
-        case NUM_B2K:
-            launch_num_hash<Block<256>, T, kNumB2KCap, kB2KW1, kNumB2KMaxNnz, SORT_BITMAP, 256>(
-                s, cls, count, A, B, w, c_col, c_val, cu_count);
-            break;
         case NUM_B8K:
-            // two launches over the class: the rows of the lower half fit a half-size table, whose
-            // workgroups run two per CU (the full table owns 106 of a CU's 160 KiB); the full table goes first
-            // (a handful of rows cannot fill the CUs anyway: one launch, one row's latency less)
-            if (w.sliced) {  // in column slices of the 2 Ki table (num_sliced_body)
-                const u32 sl = num_sliced_lds(num_group_lds<Block<256>, T, kNumB2KCap, 256>());
-                if (w.verify_numeric)
-                    SPECK_LAUNCH((num_sliced_kernel<T, true>), dim3(grid_for(count, sl, 256, cu_count, 1)), dim3(256), sl, s, A, B, w,
-                                 c_col, c_val, cls);
-                else
-                    SPECK_LAUNCH((num_sliced_kernel<T, false>), dim3(grid_for(count, sl, 256, cu_count, 1)), dim3(256), sl, s, A, B, w,
-                                 c_col, c_val, cls);
-                break;
-            }
-            if (w.verify_numeric) {  // (a sequence without a symbolic pass: the verifying forms of the same launches)
-                if (count * 2 < (u32)cu_count) {
-                    launch_num_hash<Block<512>, T, kNumB8KCap, kB8KW1, kNumB8KMaxNnz, SORT_BITMAP, 512, 0, true>(
-                        s, cls, count, A, B, w, c_col, c_val, cu_count);
-                    break;
-                }
-                if (g_b8k_full_first & 2u)
-                    launch_num_hash<Block<512>, T, kNumB8KCap, kB8KW1, kNumB8KMaxNnz, SORT_BITMAP, 512, kNumB8KHalfMaxNnz, true>(
-                        s, cls, count, A, B, w, c_col, c_val, cu_count);
-                launch_num_hash<Block<512>, T, kNumB8KCap / 2, kB8KW1, kNumB8KHalfMaxNnz, SORT_BITMAP, 512, 0, true>(
-                    s, cls, count, A, B, w, c_col, c_val, cu_count);
-                if (!(g_b8k_full_first & 2u))
-                    launch_num_hash<Block<512>, T, kNumB8KCap, kB8KW1, kNumB8KMaxNnz, SORT_BITMAP, 512, kNumB8KHalfMaxNnz, true>(
-                        s, cls, count, A, B, w, c_col, c_val, cu_count);
-                break;
-            }
-            if (count * 2 < (u32)cu_count) {
-                launch_num_hash<Block<512>, T, kNumB8KCap, kB8KW1, kNumB8KMaxNnz, SORT_BITMAP, 512>(
-                    s, cls, count, A, B, w, c_col, c_val, cu_count);
-                break;
-            }
-            // (the full table first: a workgroup of 106 KiB finds room on a CU only while the light launch beside it has
-            //  not filled the chip -- webbase stand-in 1.176 -> 1.158 ms complete, three alternating pairs; the verifying
-            //  launches of a reuse sequence keep the half table first: 0.788 against 0.868 ms.  Option b8k_full_first)
-            if (g_b8k_full_first & 1u)
-                launch_num_hash<Block<512>, T, kNumB8KCap, kB8KW1, kNumB8KMaxNnz, SORT_BITMAP, 512, kNumB8KHalfMaxNnz>(
-                    s, cls, count, A, B, w, c_col, c_val, cu_count);
-            launch_num_hash<Block<512>, T, kNumB8KCap / 2, kB8KW1, kNumB8KHalfMaxNnz, SORT_BITMAP, 512>(
-                s, cls, count, A, B, w, c_col, c_val, cu_count);
-            if (!(g_b8k_full_first & 1u))
-                launch_num_hash<Block<512>, T, kNumB8KCap, kB8KW1, kNumB8KMaxNnz, SORT_BITMAP, 512, kNumB8KHalfMaxNnz>(
-                    s, cls, count, A, B, w, c_col, c_val, cu_count);
+            if (w.verify_numeric)  // (a sequence without a symbolic pass: the verifying forms of the same launches)
+                launch_b8k<T, true>(s, count, A, B, w, c_col, c_val, cu_count);
+            else
+                launch_b8k<T, false>(s, count, A, B, w, c_col, c_val, cu_count);
             break;
-        case NUM_D1: {
-            auto k = num_dense_kernel<T, kNumD1Win, 256>;
-            set_dyn_lds(k, lds);
-            SPECK_LAUNCH(k, dim3(grid_for(count, lds, 256, cu_count, 1)), dim3(256), lds, s, A, B, w,
-                               c_col, c_val, cls);
+        case NUM_D2:
+            if (w.verify_numeric)
+                launch_d2<T, true>(s, count, A, B, w, c_col, c_val, cu_count);
+            else
+                launch_d2<T, false>(s, count, A, B, w, c_col, c_val, cu_count);
             break;
-        }
-        case NUM_D2: {
-            if (w.verify_numeric) {
-                auto kv = num_dense_kernel<T, kNumD2Cols, 1024, true>;
-                set_dyn_lds(kv, lds);
-                SPECK_LAUNCH(kv, dim3(grid_for(count, lds, 1024, cu_count, 1)), dim3(1024), lds, s, A, B,
-                                   w, c_col, c_val, cls);
-                break;
-            }
-            auto k = num_dense_kernel<T, kNumD2Cols, 1024>;
-            set_dyn_lds(k, lds);
-            SPECK_LAUNCH(k, dim3(grid_for(count, lds, 1024, cu_count, 1)), dim3(1024), lds, s, A, B,
-                               w, c_col, c_val, cls);
-            break;
-        }
         case NUM_NFCOPY: {
             u32 blocks = (count + 3) / 4;  // four waves per workgroup, a row per wave
             const u32 cap = (u32)cu_count * 8u * 4u;
@@ -2082,6 +1981,7 @@ void launch_numeric(hipStream_t s, int cls, u32 count, const CsrView<T>& Av, con
             // (the big table takes a bucket up to a load of 0.85: beyond it only the dense windows are left, and a bucket
             //  that misses the 2/3 mark by a few entries would pay dozens of them over its column span)
             auto kr_big = num_spill_reduce_kernel<T, kNumB8KCap, kB8KW1, 512, kNumB2KMaxNnz, kNumB8KCap * 85 / 100, true>;
+            const u32 lds = numeric_lds_bytes_t<T>(NUM_G);
             set_dyn_lds(kr_big, lds);
             // (its workgroups stride over the list of oversized buckets, which only the device knows -- usually a handful.
             //  Each needs 106 KiB of LDS just to find that out: a grid of 2048 queued behind the NUM_B8K launches of the
@@ -2090,6 +1990,8 @@ void launch_numeric(hipStream_t s, int cls, u32 count, const CsrView<T>& Av, con
             SPECK_LAUNCH((num_spill_copy_kernel<T>), dim3(rows, 32), dim3(256), 0, s, w, c_col, c_val, cls);
             break;
         }
+        default:  // a light class (kNumLight: launch_numeric_light) or no class at all
+            note_launch_status(hipErrorInvalidValue, "launch_numeric: not a heavy class");
     }
 }
 

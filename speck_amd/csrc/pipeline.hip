@@ -569,21 +569,31 @@ hipEvent_t kernel_event(speck_config* c, size_t i)
     return c->kev[i];
 }
 
-// Launch one kernel per class in `mask`.  The classes are independent (disjoint rows), so each
-// runs on its own stream between a fork and a join event on the pipeline stream: the
-// latency-bound heavy-row kernels (few workgroups) overlap the throughput-bound small-row ones
-// (the reference does the same with its 6 streams, source/GPU/Multiply.cu:494-553, but relies on
-// legacy default-stream ordering; here the dependencies are explicit events).
+// The call's value type for code that is a template of it: f(T{}) with T = double / float by the size of a value
+template <typename F>
+auto with_value_type(u32 vsize, F&& f)
+{
+    return vsize == 8 ? f(double{}) : f(float{});
+}
+template <typename T>
+CsrView<T> view_of(const speck_dcsr* M)
+{
+    return {M->row_offsets, M->col_ids, static_cast<const T*>(M->data), (u32)M->rows, (u32)M->cols};
+}
+
 struct ClassTiming {
     int cls;
     size_t ev;
 };
 
-// pseudo class: the merged launch of the 256-thread classes of a phase
-constexpr int kLight = -1;
-
-template <typename LaunchFn>
-int run_classes(speck_config* c, hipStream_t s, const int* order, int n_order, u32 mask, u32 light_mask,
+// Launch the items of `order` (kSymOrder / kNumOrder, launch.hpp) that have rows by `mask`: the heavy classes, each with
+// launches of its own, and kLight, the ONE launch of the classes in `light_mask`.  The items are independent (disjoint
+// rows), so each may run on its own stream between a fork and a join event on the pipeline stream: the
+// latency-bound heavy-row kernels (few workgroups) overlap the throughput-bound small-row ones
+// (the reference does the same with its 6 streams, source/GPU/Multiply.cu:494-553, but relies on
+// legacy default-stream ordering; here the dependencies are explicit events).
+template <int n_order, typename LaunchFn>
+int run_classes(speck_config* c, hipStream_t s, const int (&order)[n_order], u32 mask, u32 light_mask,
                 const u32* counts, const float* ns_per_row, size_t* ev_idx, std::vector<ClassTiming>* timing,
                 int exact_cls, LaunchFn&& launch)
 {
@@ -672,7 +682,8 @@ int run_classes(speck_config* c, hipStream_t s, const int* order, int n_order, u
     return SPECK_OK;
 }
 
-// isolated cost per row of every class (ns, MI355X, scripts/class_times.py on the four stand-ins)
+// isolated cost per row of every class (ns, MI355X, scripts/class_times.py on the four stand-ins), in the order of
+// SymClass / NumClass (device_common.hpp)
 constexpr float kSymNsPerRow[kMaxClasses] = {0.15f, 0.6f, 3.f, 5.f, 30.f, 1000.f, 8.5f, 1000.f, 12.f, 50000.f, 0.1f, 0.4f,
                                              0.4f, 0.8f, 0.f, 0.f};
 constexpr float kNumNsPerRow[kMaxClasses] = {0.1f, 0.3f, 2.f, 4.f, 12.f, 75.f, 12.f, 300.f, 1500.f, 2.5f, 1.5f, 0.2f,
@@ -759,8 +770,7 @@ int enqueue_front(speck_config* c, hipStream_t s, const speck_dcsr* A_in, const 
     u32 all_m[kMaxClasses];
     for (auto& x : all_m) x = m;  // no host-known counts: size every class for rows(A)
     const u32* hint = sym_hint ? sym_hint : all_m;
-    static const int order[6] = {SYM_GH, SYM_BM2, SYM_B32K, SYM_B16K, SYM_NF, kLight};
-    int rc = run_classes(c, s, order, 6, sym_mask, kSymLightMask, sym_hint, kSymNsPerRow, tm ? &tm->ev : nullptr,
+    int rc = run_classes(c, s, kSymOrder, sym_mask, kSymLightMask, sym_hint, kSymNsPerRow, tm ? &tm->ev : nullptr,
                          tm ? &tm->sym : nullptr, (int)SYM_NF,
                          [&](hipStream_t ks, int cls, hipEvent_t e0, hipEvent_t e1) {
                              if (cls == kLight) {
@@ -769,15 +779,11 @@ int enqueue_front(speck_config* c, hipStream_t s, const speck_dcsr* A_in, const 
                                                        c->capture_fused ? vsize : 0u, A->data, B->data, e0, e1);
                              } else if (cls == SYM_NF) {
                                  // the numeric dense-window kernel, in the symbolic phase (numeric.hip)
-                                 if (vsize == 8) {
-                                     CsrView<double> Av{A->row_offsets, A->col_ids, static_cast<const double*>(A->data), m, (u32)A->cols};
-                                     CsrView<double> Bv{B->row_offsets, B->col_ids, static_cast<const double*>(B->data), (u32)B->rows, (u32)B->cols};
-                                     launch_numeric_first<double>(ks, hint[cls], Av, Bv, w, c_ro, c->sm, c->nf_wcols, e0, e1);
-                                 } else {
-                                     CsrView<float> Av{A->row_offsets, A->col_ids, static_cast<const float*>(A->data), m, (u32)A->cols};
-                                     CsrView<float> Bv{B->row_offsets, B->col_ids, static_cast<const float*>(B->data), (u32)B->rows, (u32)B->cols};
-                                     launch_numeric_first<float>(ks, hint[cls], Av, Bv, w, c_ro, c->sm, c->nf_wcols, e0, e1);
-                                 }
+                                 with_value_type(vsize, [&](auto t) {
+                                     using T = decltype(t);
+                                     launch_numeric_first<T>(ks, hint[cls], view_of<T>(A), view_of<T>(B), w, c_ro, c->sm,
+                                                             c->nf_wcols, e0, e1);
+                                 });
                              } else
                                  launch_symbolic(ks, cls, hint[cls], A->row_offsets, sc.b_sl,
                                                  B->col_ids, w, c_ro, c->sm);
@@ -817,13 +823,11 @@ int enqueue_front(speck_config* c, hipStream_t s, const speck_dcsr* A_in, const 
         wa.expect_g = expect_g;
         wa.expect_g_rows = expect_g_rows;
         wa.bytes_acc = bytes;
-        if (vsize == 8) {
-            const ProductSrc<double> src{sc.b_sl, static_cast<const double*>(A->data), B->col_ids, static_cast<const double*>(B->data), sc.w_sl};
-            launch_walk<double>(s, wa, src, chain, e0, e1);
-        } else {
-            const ProductSrc<float> src{sc.b_sl, static_cast<const float*>(A->data), B->col_ids, static_cast<const float*>(B->data), sc.w_sl};
-            launch_walk<float>(s, wa, src, chain, e0, e1);
-        }
+        with_value_type(vsize, [&](auto t) {
+            using T = decltype(t);
+            const ProductSrc<T> src{sc.b_sl, static_cast<const T*>(A->data), B->col_ids, static_cast<const T*>(B->data), sc.w_sl};
+            launch_walk<T>(s, wa, src, chain, e0, e1);
+        });
         LAUNCHES_OK();
         return SPECK_OK;
     }
@@ -861,9 +865,9 @@ int enqueue_back(speck_config* c, hipStream_t s, const speck_dcsr* A, const spec
                  const u32* counts /*host-known, or nullptr*/, Timing* tm)
 {
     const u32 m = (u32)A->rows;
-    CsrView<T> Av{c->capture_overlap ? sc.a_ro_copy : A->row_offsets, A->col_ids, static_cast<const T*>(A->data), m, (u32)A->cols};
-    CsrView<T> Bv{B->row_offsets, B->col_ids, static_cast<const T*>(B->data), (u32)B->rows,
-                  (u32)B->cols};
+    CsrView<T> Av = view_of<T>(A);
+    const CsrView<T> Bv = view_of<T>(B);
+    if (c->capture_overlap) Av.row_offsets = sc.a_ro_copy;  // (as enqueue_front: the structure the sequence was built on)
     RowWork w = make_work(c, sc, c->spill, m);
     w.sliced = (c->cp.slice_ops && u64(B->cols) <= kSliceMaxCols) ? 1u : 0u;  // (as enqueue_front classifies)
     // the staged offsets -> C.row_offsets: by extra workgroups of the numeric light launch when there is one, else by a
@@ -875,8 +879,7 @@ int enqueue_back(speck_config* c, hipStream_t s, const speck_dcsr* A, const spec
     u32 all_m[kMaxClasses];
     for (auto& x : all_m) x = m;
     const u32* hint = counts ? counts : all_m;
-    static const int order[5] = {NUM_G, NUM_D2, NUM_B8K, NUM_NFCOPY, kLight};
-    return run_classes(c, s, order, 5, num_mask, kNumLightMask, counts, kNumNsPerRow, tm ? &tm->ev : nullptr,
+    return run_classes(c, s, kNumOrder, num_mask, kNumLightMask, counts, kNumNsPerRow, tm ? &tm->ev : nullptr,
                        tm ? &tm->num : nullptr, -100,
                        [&](hipStream_t ks, int cls, hipEvent_t e0, hipEvent_t e1) {
                            if (cls == kLight)
@@ -1024,7 +1027,6 @@ ReplayPlan plan_replay(const speck_config* c, bool arena_mine, bool arena_replay
     // offsets, classes, records and lists it would produce are a function of the rows' nnz and of the analysis' quantities
     // -- all verified where they are produced.  C.row_offsets is still rewritten in every call (from the sequence's copy
     // of the offsets, by extra workgroups of the numeric light launch: needs that launch).
-    constexpr u32 kBigLight = (1u << NUM_D1) | (1u << NUM_B2K) | (1u << NUM_W512) | (1u << NUM_W256);
     // (... or has no rows that are finished early at all: every row then goes through the numeric light launch)
     const bool early_ok = (p.fused && p.direct) || (p.num_mask & (kEscNum | (1u << NUM_NFCOPY))) == 0;
     // In such a sequence the symbolic pass of a hash / dense row has ONE reader left: the comparison of its count with the
@@ -1038,7 +1040,7 @@ ReplayPlan plan_replay(const speck_config* c, bool arena_mine, bool arena_replay
                              (c->num_verify >= 2 || us_hash > us_esc);
     const u32 eff_sym = want_verify ? (p.sym_mask & kSymEscMask) : p.sym_mask;
     p.skip_scan = c->skip_scan && arena_replay_ok && p.overlap && early_ok &&
-                  (p.launch_mask & kBigLight) != 0 && (eff_sym & ~kSymLightMask) == 0;
+                  (p.launch_mask & kNumBigLightMask) != 0 && (eff_sym & ~kSymLightMask) == 0;
     p.num_verify = want_verify && p.skip_scan;
     p.safe_numeric = (p.launch_mask & kEscNum) == 0;
     return p;

@@ -271,8 +271,8 @@ __global__ __launch_bounds__(kGhThreads) void sym_global_hash_kernel(ProductSrc<
 }
 
 // ------------------------------------------------------------------ kernels
-// Stand-alone kernels (one class per launch) and the merged "light" kernel (see numeric.hip):
-// every 256-thread class shares one launch, block ranges map to classes, heaviest first.
+// The kernels of the heavy classes (one class per launch, kSymOrder) and the merged "light" kernel (see numeric.hip):
+// the classes of kSymLight share one launch, block ranges map to classes, heaviest first.
 template <class G, u32 CAP, int THREADS>
 __global__ __launch_bounds__(THREADS) void sym_hash_kernel(ProductSrc<float> src, const u32* a_ro,
                                                            RowWork w, u32* __restrict__ counts,
@@ -295,26 +295,6 @@ __global__ __launch_bounds__(THREADS) void sym_bitmap_kernel(ProductSrc<float> s
     sym_bitmap_body<WORDS, THREADS>(smem, src, w, counts, cls, blockIdx.x, gridDim.x);
 }
 
-template <u32 L>
-__global__ __launch_bounds__(256) void sym_escw_kernel(ProductSrc<float> src, const u32* a_ro, RowWork w,
-                                                       u32* __restrict__ counts, int cls)
-{
-    SPECK_POISON();
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    src.rebase(a_ro);
-    sym_escw_body<L, 256>(smem, src, w, counts, cls, blockIdx.x, gridDim.x);
-}
-
-template <u32 L>
-__global__ __launch_bounds__(256) void sym_esc_kernel(ProductSrc<float> src, const u32* a_ro, RowWork w,
-                                                      u32* __restrict__ counts, int cls)
-{
-    SPECK_POISON();
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    src.rebase(a_ro);
-    sym_esc_body<L, 256>(smem, src, w, counts, cls, blockIdx.x, gridDim.x);
-}
-
 __global__ __launch_bounds__(256) void sym_light_kernel(ProductSrc<float> src, const u32* a_ro, RowWork w,
                                                         u32* __restrict__ counts, ClassGrid cg)
 {
@@ -322,7 +302,8 @@ __global__ __launch_bounds__(256) void sym_light_kernel(ProductSrc<float> src, c
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     src.rebase(a_ro);
     const u32 b = blockIdx.x;
-    // launch order (ClassGrid slots): BM1, B4K, W1K, W256, R64, R32, W128, G16, G8
+    // branch k below = slot k of the launch (ClassGrid)
+    static_assert(slots_are(kSymLight, SYM_BM1, SYM_B4K, SYM_W1K, SYM_W256, SYM_R64, SYM_R32, SYM_W128, SYM_G16, SYM_G8));
     if (b < cg.first[1])
         sym_bitmap_body<kSymBm1Words, 256>(smem, src, w, counts, SYM_BM1, b - cg.first[0], cg.first[1] - cg.first[0], cg.cnt[0]);
     else if (b < cg.first[2])
@@ -356,6 +337,7 @@ __global__ __launch_bounds__(256) void sym_light_fused_kernel(ProductSrc<T> nsrc
     nsrc.rebase(a_ro);
     const ProductSrc<float> src{nsrc.b_sl, nullptr, nsrc.b_col, nullptr, nsrc.w_sl};
     const u32 b = blockIdx.x;
+    static_assert(slots_are(kSymLight, SYM_BM1, SYM_B4K, SYM_W1K, SYM_W256, SYM_R64, SYM_R32, SYM_W128, SYM_G16, SYM_G8));
     if (b < cg.first[1])
         sym_bitmap_body<kSymBm1Words, 256>(smem, src, w, counts, SYM_BM1, b - cg.first[0], cg.first[1] - cg.first[0], cg.cnt[0]);
     else if (b < cg.first[2])
@@ -382,14 +364,20 @@ __global__ __launch_bounds__(256) void sym_light_fused_kernel(ProductSrc<T> nsrc
 
 u32 symbolic_lds_bytes(int cls)
 {
+    const u32 groups = class_rows(kSymLight, cls);  // of the sub-wave classes: a group of lanes per row
+    static_assert(class_rows(kSymLight, SYM_G8) == 256 / 8 && class_rows(kSymLight, SYM_G16) == 256 / 16 &&
+                      class_rows(kSymLight, SYM_R32) == 256 / 32 && class_rows(kSymLight, SYM_R64) == 256 / 64 &&
+                      class_rows(kSymLight, SYM_W128) == 256 / 16 && class_rows(kSymLight, SYM_W256) == 256 / 32 &&
+                      class_rows(kSymLight, SYM_W1K) == 256 / 64,
+                  "rows per workgroup = 256 threads / the lanes of the class' group (the bodies in sym_light_kernel)");
     switch (cls) {
-        case SYM_G8: return 32 * sym_esc_group_lds<8>();
-        case SYM_G16: return 16 * sym_esc_group_lds<16>();
-        case SYM_R32: return 8 * sym_escw_group_lds<32>();
-        case SYM_R64: return 4 * sym_escw_group_lds<64>();
-        case SYM_W128: return 16 * sym_group_lds<SubWave<16>, kSymW128Cap, 256>();
-        case SYM_W256: return 8 * sym_group_lds<SubWave<32>, kSymW256Cap, 256>();
-        case SYM_W1K: return 4 * sym_group_lds<SubWave<64>, kSymW1KCap, 256>();
+        case SYM_G8: return groups * sym_esc_group_lds<8>();
+        case SYM_G16: return groups * sym_esc_group_lds<16>();
+        case SYM_R32: return groups * sym_escw_group_lds<32>();
+        case SYM_R64: return groups * sym_escw_group_lds<64>();
+        case SYM_W128: return groups * sym_group_lds<SubWave<16>, kSymW128Cap, 256>();
+        case SYM_W256: return groups * sym_group_lds<SubWave<32>, kSymW256Cap, 256>();
+        case SYM_W1K: return groups * sym_group_lds<SubWave<64>, kSymW1KCap, 256>();
         case SYM_B4K: return sym_group_lds<Block<256>, kSymB4KCap, 256>();
         case SYM_B16K: return sym_group_lds<Block<512>, kSymB16KCap, 512>();
         case SYM_B32K: return sym_group_lds<Block<1024>, kSymB32KCap, 1024>();
@@ -398,16 +386,6 @@ u32 symbolic_lds_bytes(int cls)
         case SYM_GH: return (2 * kGhThreads + kGhThreads / 64 + 8 + win_words<Block<kGhThreads>>()) * 4;
     }
     return 0;
-}
-
-template <typename K>
-static void set_dyn_lds(K kernel, u32 bytes)
-{
-    // kernels above 64 KiB of LDS need the opt-in (a workgroup may own all 160 KiB on gfx950)
-    if (bytes > 48 * 1024)
-        note_launch_status(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes),
-                           "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
 }
 
 static u32 g_grid_rounds_block = 1, g_grid_rounds_sub = 4;
@@ -447,37 +425,21 @@ static void launch_sym_hash(hipStream_t s, int cls, u32 count, const ProductSrc<
                        dim3(THREADS), lds, s, A, B, w, counts, cls);
 }
 
-// `fused_vsize` (8 / 4, replayed sequence with direct placement only; 0 = off): the rows of SYM_G8 / SYM_G16 are
+// `fused_vsize` (8 / 4, replayed sequence with direct placement only; 0 = off): the rows of the register classes are
 // finished by this launch (sym_light_fused_kernel); a_val / b_val are then the values of A and B.
 void launch_symbolic_light(hipStream_t s, const u32* counts_hint, u32 mask, const u32* a_ro,
                            const uint2* b_sl, const u32* b_col, const RowWork& w,
                            u32* counts, int cu_count, bool exact, u32 fused_vsize, const void* a_val,
                            const void* b_val, hipEvent_t e0, hipEvent_t e1)
 {
-    constexpr int NS = 9;
-    static const int slots[NS] = {SYM_BM1, SYM_B4K, SYM_W1K, SYM_W256, SYM_R64, SYM_R32, SYM_W128, SYM_G16, SYM_G8};
-    static const u32 rows_per_block[NS] = {1, 1, 4, 8, 4, 8, 16, 16, 32};
+    constexpr size_t NS = kSymLightSlots;
     const bool fused = fused_vsize != 0 && (mask & kSymEscMask) != 0;
-    auto class_lds = [&](int cls) -> u32 {
-        if (fused && cls == SYM_G8) return 32 * (fused_vsize == 8 ? num_esc_group_lds<double, 8>() : num_esc_group_lds<float, 8>());
-        if (fused && cls == SYM_G16) return 16 * (fused_vsize == 8 ? num_esc_group_lds<double, 16>() : num_esc_group_lds<float, 16>());
-        if (fused && cls == SYM_R32) return 8 * (fused_vsize == 8 ? num_escw_group_lds<double, 32>() : num_escw_group_lds<float, 32>());
-        if (fused && cls == SYM_R64) return 4 * (fused_vsize == 8 ? num_escw_group_lds<double, 64>() : num_escw_group_lds<float, 64>());
-        return symbolic_lds_bytes(cls);
+    auto class_lds = [&](int cls) -> u32 {  // (a register class finished here runs the numeric body of its rows)
+        return fused && fused_num_class(cls) >= 0 ? numeric_lds_bytes(fused_num_class(cls), fused_vsize) : symbolic_lds_bytes(cls);
     };
-    u32 lds = 0;
-    for (int k = 0; k < NS; ++k)
-        if (mask >> slots[k] & 1u) lds = lds > class_lds(slots[k]) ? lds : class_lds(slots[k]);
-    ClassGrid cg{};
-    for (int k = 0; k < NS; ++k) {
-        const bool on = (mask >> slots[k] & 1u) && counts_hint[slots[k]];
-        cg.first[k + 1] = cg.first[k] + (on ? grid_for(counts_hint[slots[k]], lds, 256, cu_count, rows_per_block[k]) : 0u);
-        cg.cnt[k] = exact ? counts_hint[slots[k]] : kNoCount;
-    }
-    if (cg.first[NS] == 0) {
-        if (e0) (void)hipEventRecord(e0, s), (void)hipEventRecord(e1, s);  // (nothing to time: an empty interval)
-        return;
-    }
+    ClassGrid cg;
+    u32 lds;
+    if (!plan_light(kSymLight, mask, counts_hint, exact, cu_count, class_lds, 0u, s, e0, e1, &cg, &lds)) return;
     if (fused && fused_vsize == 8) {
         const ProductSrc<double> nsrc{b_sl, static_cast<const double*>(a_val), b_col, static_cast<const double*>(b_val), w.w_sl};
         SPECK_LAUNCH_TIMED((sym_light_fused_kernel<double>), dim3(cg.first[NS]), dim3(256), lds, s, e0, e1, nsrc, a_ro, w, counts, cg);
@@ -501,34 +463,8 @@ void launch_symbolic(hipStream_t s, int cls, u32 count, const u32* a_ro, const u
     const u32* B = a_ro;
     const u32 lds = symbolic_lds_bytes(cls);
     switch (cls) {
-        case SYM_G8:
-            SPECK_LAUNCH(sym_esc_kernel<8>, dim3(grid_for(count, lds, 256, cu_count, 32)), dim3(256), lds, s, A, B, w,
-                               counts, cls);
-            break;
-        case SYM_G16:
-            SPECK_LAUNCH(sym_esc_kernel<16>, dim3(grid_for(count, lds, 256, cu_count, 16)), dim3(256), lds, s, A, B, w,
-                               counts, cls);
-            break;
-        case SYM_R32:
-            SPECK_LAUNCH(sym_escw_kernel<32>, dim3(grid_for(count, lds, 256, cu_count, 8)), dim3(256), lds, s, A, B, w,
-                               counts, cls);
-            break;
-        case SYM_R64:
-            SPECK_LAUNCH(sym_escw_kernel<64>, dim3(grid_for(count, lds, 256, cu_count, 4)), dim3(256), lds, s, A, B, w,
-                               counts, cls);
-            break;
-        case SYM_W128: launch_sym_hash<SubWave<16>, kSymW128Cap, 256>(s, cls, count, A, B, w, counts, cu_count); break;
-        case SYM_W256: launch_sym_hash<SubWave<32>, kSymW256Cap, 256>(s, cls, count, A, B, w, counts, cu_count); break;
-        case SYM_W1K: launch_sym_hash<SubWave<64>, kSymW1KCap, 256>(s, cls, count, A, B, w, counts, cu_count); break;
-        case SYM_B4K: launch_sym_hash<Block<256>, kSymB4KCap, 256>(s, cls, count, A, B, w, counts, cu_count); break;
         case SYM_B16K: launch_sym_hash<Block<512>, kSymB16KCap, 512>(s, cls, count, A, B, w, counts, cu_count); break;
         case SYM_B32K: launch_sym_hash<Block<1024>, kSymB32KCap, 1024>(s, cls, count, A, B, w, counts, cu_count); break;
-        case SYM_BM1: {
-            auto k = sym_bitmap_kernel<kSymBm1Words, 256>;
-            SPECK_LAUNCH(k, dim3(grid_for(count, lds, 256, cu_count, 1)), dim3(256), lds, s, A, B,
-                               w, counts, cls);
-            break;
-        }
         case SYM_BM2: {
             auto k = sym_bitmap_kernel<kSymBm2Words, 1024>;
             set_dyn_lds(k, lds);
@@ -540,6 +476,8 @@ void launch_symbolic(hipStream_t s, int cls, u32 count, const u32* a_ro, const u
             SPECK_LAUNCH(sym_global_hash_kernel, dim3(grid_for(count, lds, kGhThreads, cu_count, 1)),
                                dim3(kGhThreads), lds, s, A, B, w, counts);
             break;
+        default:  // a light class (kSymLight: launch_symbolic_light), SYM_NF (launch_numeric_first) or no class at all
+            note_launch_status(hipErrorInvalidValue, "launch_symbolic: not a heavy class");
     }
 }
 
