@@ -29,6 +29,7 @@
 #include "compact.hpp"
 #include "launch.hpp"
 #include "masked.hpp"
+#include "masked_rules.hpp"
 #include "row_tiles.hpp"
 #include "scan.hpp"
 #include "side_call.hpp"
@@ -51,11 +52,9 @@ void MaskedScratch::release()
 
 namespace {
 
-constexpr u32 kGroupMax = SPECK_MASK_GROUP_MAX, kLdsMax = SPECK_MASK_LDS_MAX;
-constexpr u32 kLdsSmall = 1024;      // LDS class: rows up to this many entries take the 256-thread launch
+// (the lists, the class limits and every rule that picks a list, a table size or a walk: masked_rules.hpp)
+constexpr u32 kLdsSmall = kMaskLdsSmall, kLdsMax = kMaskLdsMax;
 constexpr u32 kHitBit = 0x80000000u, kColMask = 0x7FFFFFFFu;
-enum { LIST_G8 = 0, LIST_G16, LIST_G32, LIST_G64, LIST_LDS_S, LIST_LDS_L, LIST_GLOBAL, MASK_LISTS };
-static_assert(kGroupMax == 256 && kLdsMax <= 4096, "group widths / 16-bit table positions");
 
 struct MaskedStatus {
     u32 invalid;            // offsets of A / M, an id of A
@@ -143,7 +142,7 @@ __global__ __launch_bounds__(kTileRows) void masked_classify_kernel(const u32* _
             const u32 r = first_end_beyond(s_aro + 1, nr, i);  // the row of entry i
             if (s_mro[r + 1] > s_mro[r]) {
                 products += len;
-                if (s_ops[r] < (1u << 20)) atomicAdd(&s_ops[r], (u32)min(len, u64(1u << 20)));
+                if (s_ops[r] < kMaskOpsCeiling) atomicAdd(&s_ops[r], (u32)min(len, u64(kMaskOpsAddCap)));
             }
         }
     }
@@ -156,13 +155,7 @@ __global__ __launch_bounds__(kTileRows) void masked_classify_kernel(const u32* _
     if (t < nr) {
         const u32 len = s_mro[t + 1] - s_mro[t];
         if (len == 0 || s_aro[t + 1] == s_aro[t]) cls = MASK_LISTS;
-        else if (len <= group_max && len <= kGroupMax) {
-            // four mask entries per lane at most -- and not more than ~32 products per lane where a wider group can help
-            const u32 want = max((len + 3u) / 4u, s_ops[t] / 32u);
-            cls = want <= 8 ? LIST_G8 : want <= 16 ? LIST_G16 : want <= 32 ? LIST_G32 : LIST_G64;
-        }
-        else if (len <= lds_max && len <= kLdsMax) cls = len <= kLdsSmall ? LIST_LDS_S : LIST_LDS_L;
-        else cls = LIST_GLOBAL;
+        else cls = (int)mask_list_of(len, s_ops[t], group_max, lds_max);
     }
     u32 rank = 0;  // of my row among the tile's rows of its list
 #pragma unroll
@@ -282,7 +275,7 @@ __global__ __launch_bounds__(256) void masked_group_kernel(const MaskedArgs<T> g
                 ++hits;
             };
             // (four loads of B's columns in flight per lane in either walk: a walk is a chain of such loads otherwise)
-            if (total >= 16u * nb) {
+            if (mask_team_walk(total, nb)) {
                 // long rows of B (16 entries on average): teams of eight lanes take the batch's entries in turn and walk
                 // "their" row eight entries at a time -- no search for the entry of A
                 constexpr u32 NT = L / 8u;
@@ -326,8 +319,7 @@ __global__ __launch_bounds__(256) void masked_group_kernel(const MaskedArgs<T> g
 // power of two >= twice its length (load <= 1/2): clearing and building cost what the row is long, not what the class
 // admits.  The columns of a row are distinct, so building the table races only for empty slots: one compare-and-swap on
 // the word that holds the slot, repeated when the OTHER half of the word changed meanwhile.  Probes read.
-__device__ __forceinline__ u32 table_slot(u32 c, u32 bits) { return (c * 0x9E3779B1u) >> (32u - bits); }
-
+// (the table's size and a column's home slot: mask_table_bits, table_slot -- masked_rules.hpp)
 template <typename T, u32 THREADS>
 __global__ __launch_bounds__(THREADS) void masked_lds_kernel(const MaskedArgs<T> g, u32 list, u32 cap)
 {
@@ -348,8 +340,7 @@ __global__ __launch_bounds__(THREADS) void masked_lds_kernel(const MaskedArgs<T>
         const u32 row = *two_sided_at(g.lists, g.rows, list, e);
         const u32 m0 = g.m_ro[row], n = min(g.m_ro[row + 1] - m0, cap);
         const u32 a0 = g.a_ro[row], a1 = g.a_ro[row + 1];
-        u32 bits = 4;
-        while ((1u << bits) < 2u * n) ++bits;
+        const u32 bits = mask_table_bits(n);
         const u32 slots = 1u << bits;
         for (u32 p = t; p < n; p += THREADS) {
             col[p] = g.m_col[m0 + p];
