@@ -533,6 +533,57 @@ int speck_scale_f64(speck_config *cfg, const speck_dcsr *A, const speck_scale_pa
 int speck_scale_f32(speck_config *cfg, const speck_dcsr *A, const speck_scale_params *p, speck_dcsr *C,
                     speck_scale_info *info);
 
+/* ---- matrix-vector product (new: the reference has no counterpart): y = alpha A x + beta y on a matrix that is already
+ *      on the device -- the one map (matrix, vector) -> vector beside speck_reduce_* (matrix -> vector) and speck_scale_*
+ *      (vector -> matrix): a PageRank or power iteration on the row-normalised matrix, the residual b - A x or a Jacobi
+ *      sweep beside the Galerkin product, the check || A x - P (Q x) || of a product that never downloads it.
+ *  d_x is a DEVICE array of A->cols doubles, indexed by the column id; d_y a DEVICE array of A->rows doubles, indexed by
+ *      the row INSIDE A -- for a row-range view the caller offsets the pointer, as for speck_scale_*.  The vectors are
+ *      double for both value types.
+ *  Values: every step in double, each rounded on its own, nothing fused.  The term of an entry is t = (double)a * x[j],
+ *      rounded once; s_i is the combination of the row's terms in the SAME TREE speck_reduce_* uses for SPECK_REDUCE_SUM,
+ *      a function of the absolute positions of the entries in data alone; a row without entries has s_i = +0.0.  Then
+ *      y_i = alpha * s_i + beta * y_i: two products, each rounded, and one sum.  beta == 0.0 means y is NOT READ:
+ *      y_i = alpha * s_i, and a NaN or garbage in y does not survive (the BLAS convention -- unlike speck_add_*, where a
+ *      zero coefficient shields nothing and 0 * NaN stays NaN).  alpha is always applied (alpha == 0 with an infinite s_i
+ *      is NaN).  Nothing else is hidden: 0 * inf, a NaN in x or in A land in exactly the rows that reference them and in
+ *      no other row.  The sign of a zero s_i is unspecified, as in the reduction.
+ *  What follows: the same bits from run to run; a row-range view gives bit for bit the rows of the whole matrix's result
+ *      -- a row-sharded product equals the unsharded one; for fp64 with alpha = 1, beta = 0, y equals bit for bit the row
+ *      results of speck_reduce_f64(SUM) on speck_scale_f64(A, col = x, MUL), NaN where that has a NaN; and
+ *      |s_i - exact| <= g_n sum|t| with the reduction's g_n.  No floating-point atomic anywhere.
+ *  Rows need not be sorted or free of duplicates: duplicates simply add.  Offsets descending, leaving [row_offsets[0],
+ *      row_offsets[0] + nnz], or a last offset that is not row_offsets[0] + nnz; a column id >= cols; NULL A, NULL
+ *      row_offsets or NULL d_y with rows > 0; NULL d_x, data or col_ids with nnz > 0; alpha or beta NaN; d_x or d_y equal
+ *      to one of A's three pointers; the ranges [d_x, d_x + cols) and [d_y, d_y + rows) overlapping: SPECK_ERR_INVALID.
+ *      rows or cols > 2^27: SPECK_ERR_DIM_LIMIT.  nnz >= 2^32: SPECK_ERR_NNZ_OVERFLOW.  rows == 0 is valid and writes
+ *      nothing; nnz == 0 is valid and gives y_i = alpha * (+0.0) + beta * y_i.
+ *  On any error NOTHING of y is written (*info is zero once the arguments have passed).  No offset or column id is used as
+ *      an address before it was checked: the kernels that read the entries are queued behind the verdict on the offsets,
+ *      an id >= cols raises the verdict and is not followed, and the row sums wait in a temporary of rows doubles until the
+ *      kernel queued last has seen the verdict of EVERY tile -- only it writes y, each row once by one thread.  There is NO
+ *      read-back in the middle of the call: the host reads the status block once, at the end.
+ *  Runs on the config's stream (speck_config_set_stream is honoured) and returns complete.  Temporaries are grow-only
+ *      buffers of the config's own (not the multiply's arena: a spmv between two identical multiplies does not disturb the
+ *      second one's reuse sequence), released with it; cfg == NULL is allowed as for speck_reduce_*.  With the debug
+ *      option guard_bytes their canary zones are checked after the call.
+ *  The entries are walked in tiles of SPECK_SPMV_TILE_ENTRIES, the reduction's, aligned to absolute positions; one path for
+ *      every row length.  The 16-byte loads need data and col_ids on 16-byte boundaries; elsewhere the entries are loaded
+ *      one by one, with the same results.
+ *  Not built: A^T x (transpose, then spmv); several right-hand sides; vectors in float; a semiring other than (+, x); a
+ *      spmv fused into the product that made A. ---- */
+#define SPECK_SPMV_TILE_ENTRIES 4096
+typedef struct speck_spmv_info {
+    uint64_t rows_empty;   /* rows without an entry: s_i = +0.0 */
+    uint64_t rows_split;   /* rows whose entries lie in more than one tile */
+    uint64_t tiles;        /* tiles walked */
+    uint64_t entries;      /* entries multiplied = nnz */
+} speck_spmv_info;
+int speck_spmv_f64(speck_config *cfg, double alpha, const speck_dcsr *A, const double *d_x, double beta, double *d_y,
+                   speck_spmv_info *info /* may be NULL */);
+int speck_spmv_f32(speck_config *cfg, double alpha, const speck_dcsr *A, const double *d_x, double beta, double *d_y,
+                   speck_spmv_info *info);
+
 /* ---- row-sharded multi-GPU (new: the reference is single-GPU, source/Executor.cpp:25).  One process per GPU;
  *      rank p multiplies the row range [b_p, b_{p+1}) of A (a view with absolute offsets, boundaries from
  *      speck_partition_rows) with a replicated B, then ONE exchange concatenates the shards on a root rank:

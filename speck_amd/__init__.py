@@ -17,4 +17,5 @@ from .api import (  # noqa: F401
     REDUCE_TILE_ENTRIES, REDUCE_THREAD_ENTRIES, REDUCE_WAVE_ENTRIES,
     scale, normalize_rows, pattern_ones, ScaleInfo, MAP_IDENTITY, MAP_ABS, MAP_SQUARE, MAP_ONE, SCALE_MAPS,
     SCALE_NONE, SCALE_MUL, SCALE_DIV, SCALE_TILE_ENTRIES,
+    spmv, SpmvInfo, SPMV_TILE_ENTRIES,
 )

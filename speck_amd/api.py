@@ -697,18 +697,18 @@ class ScaleInfo:
         return f"ScaleInfo(entries={self.entries}, nonfinite={self.nonfinite}, tiles={self.tiles})"
 
 
-def _device_vector(v, n, what):
+def _device_vector(v, n, what, who="scale"):
     """The device address of a vector of n float64: an address as it is, a torch tensor (anything with data_ptr()) checked"""
     if v is None:
         return None
     if not hasattr(v, "data_ptr"):
         return int(v)
     if hasattr(v, "dtype") and str(v.dtype) not in ("torch.float64", "float64"):
-        raise ValueError(f"scale: {what} must be float64, not {v.dtype}")
+        raise ValueError(f"{who}: {what} must be float64, not {v.dtype}")
     if hasattr(v, "is_contiguous") and not v.is_contiguous():
-        raise ValueError(f"scale: {what} must be contiguous")
+        raise ValueError(f"{who}: {what} must be contiguous")
     if hasattr(v, "numel") and v.numel() != n:
-        raise ValueError(f"scale: {what} holds {v.numel()} values, the matrix asks for {n}")
+        raise ValueError(f"{who}: {what} holds {v.numel()} values, the matrix asks for {n}")
     return int(v.data_ptr())
 
 
@@ -776,3 +776,53 @@ def pattern_ones(A, config):
     """The indicator matrix of A: its pattern with every value 1.0 (scale with map "one"), made on the device -- what a
     triangle count L o (L L) needs of a weighted graph."""
     return scale(A, config, map="one")[0]
+
+
+# include/speck_c_api.h: the entries of a tile of the pass that walks them (the reduction's)
+SPMV_TILE_ENTRIES = 4096
+
+
+class SpmvInfo:
+    """speck_spmv_info: what the matrix-vector product walked."""
+
+    def __init__(self, c):
+        self.rows_empty = int(c.rows_empty)
+        self.rows_split = int(c.rows_split)
+        self.tiles = int(c.tiles)
+        self.entries = int(c.entries)
+
+    def __repr__(self):
+        return (f"SpmvInfo(rows_empty={self.rows_empty}, rows_split={self.rows_split}, tiles={self.tiles}, "
+                f"entries={self.entries})")
+
+
+def spmv(A, x, config, alpha=1.0, beta=0.0, y=None):
+    """y = alpha A x + beta y on a device matrix (speck_spmv_f64 / _f32).  x (A.cols float64, indexed by the column id) and
+    y (A.rows float64, indexed by the row inside A: for a row_view pass the slice) are device vectors -- a device address
+    or an object with data_ptr(), e.g. a torch tensor -- float64 for both value types.  Every term a x[j] and every sum is
+    rounded on its own; the row sums come from the tree of reduce(A, "sum"): bit-reproducible, a row_view gives the rows
+    of the whole matrix bit for bit, and for float64 spmv(A, x) equals reduce(scale(A, col=x), "sum") bit for bit.
+    beta == 0 does not read y (a NaN in it does not survive); alpha is always applied; a NaN or 0 * inf lands in exactly the
+    rows that reference it.  Rows need not be sorted, duplicates add.  y=None is allowed only with beta == 0: the result is
+    then a numpy array downloaded from a buffer of the library's allocator.  config may be None.
+    Returns (that array, or None where y was given and holds the result on the device, SpmvInfo)."""
+    if y is None and float(beta) != 0.0:
+        raise ValueError("spmv: beta != 0 needs a y to read")
+    x_ptr = _device_vector(x, A.cols, "x", "spmv")
+    y_ptr = _device_vector(y, A.rows, "y", "spmv")
+    L = _lib.load()
+    fn = L.speck_spmv_f32 if A.dtype == np.float32 else L.speck_spmv_f64
+    buf = None
+    if y is None:
+        buf = dCSR(np.float64)  # (its data array: A.rows doubles)
+        buf.alloc(0, 0, max(A.rows, 1), allocOffsets=False)
+        y_ptr = buf._c.data
+    info = _lib.CSpmvInfo()
+    _check(fn(config._h if config is not None else None, float(alpha), C.byref(A._c), x_ptr, float(beta), y_ptr,
+              C.byref(info)), "spmv")
+    out = None
+    if buf is not None:
+        out = np.zeros(max(A.rows, 1), dtype=np.float64)
+        _check(L.speck_dcsr_download(C.byref(buf._c), None, None, out.ctypes.data, 8), "spmv: download")
+        out = out[:A.rows]
+    return out, SpmvInfo(info)

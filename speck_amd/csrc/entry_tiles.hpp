@@ -1,4 +1,4 @@
-// entry_tiles.hpp -- what the operations that walk a matrix in ENTRY TILES (reduce.hip, scale.hip) share: the check of one
+// entry_tiles.hpp -- what the operations that walk a matrix in ENTRY TILES (reduce.hip, scale.hip, spmv.hip) share: the check of one
 // row's offsets in their first pass, which also tells every tile the rows of its first and of its last entry.  A tile is
 // the entries [kTile t, kTile (t + 1)) of the buffers, counted from the buffers' start and clipped to the matrix; the
 // i-th tile the matrix touches is tile row_offsets[0] / kTile + i.

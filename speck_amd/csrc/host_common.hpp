@@ -19,7 +19,9 @@
         if (_e != hipSuccess) {                                                             \
             std::fprintf(stderr, "speck_amd: HIP error %s at %s:%d (%s)\n",                 \
                          hipGetErrorString(_e), __FILE__, __LINE__, #expr);                 \
-            return (_e == hipErrorOutOfMemory) ? SPECK_ERR_OOM : SPECK_ERR_HIP;             \
+            return (_e == hipErrorOutOfMemory) ? SPECK_ERR_OOM                              \
+                   : (_e == hipErrorNoDevice)  ? SPECK_ERR_NO_DEVICE                        \
+                                               : SPECK_ERR_HIP;                             \
         }                                                                                   \
     } while (0)
 

@@ -34,6 +34,7 @@
 #include "add.hpp"
 #include "reduce.hpp"
 #include "scale.hpp"
+#include "spmv.hpp"
 #include "sort_rows.hpp"
 
 using namespace speck;
@@ -239,6 +240,7 @@ struct speck_config {
     AddScratch add;  // ... and of speck_add_* (add.hip)
     ReduceScratch reduce;  // ... and of speck_reduce_* (reduce.hip)
     ScaleScratch scale;  // ... and of speck_scale_* (scale.hip)
+    SpmvScratch spmv;  // ... and of speck_spmv_* (spmv.hip)
     const void* zones_arena = nullptr;
     u64 zones_m = 0, zones_nnz = 0, zones_gap = 0;
     bool gpool_zones_filled = false;
@@ -1930,6 +1932,7 @@ SelectScratch* select_scratch(speck_config* c) { return &c->select; }
 AddScratch* add_scratch(speck_config* c) { return &c->add; }
 ReduceScratch* reduce_scratch(speck_config* c) { return &c->reduce; }
 ScaleScratch* scale_scratch(speck_config* c) { return &c->scale; }
+SpmvScratch* spmv_scratch(speck_config* c) { return &c->spmv; }
 }  // namespace speck
 
 extern "C" {
@@ -2048,6 +2051,7 @@ int speck_config_destroy(speck_config* c)
     c->add.release();
     c->reduce.release();
     c->scale.release();
+    c->spmv.release();
     if (c->pred.off) (void)guarded_free(c->pred.off);
     if (c->gpred.off) (void)guarded_free(c->gpred.off);
     if (c->d_stats) (void)hipFree(c->d_stats);
@@ -2134,6 +2138,7 @@ int speck_config_set_option(speck_config* c, const char* name, int64_t value)
         c->add.release();
         c->reduce.release();
         c->scale.release();
+        c->spmv.release();
     }
     else if (n == "sort_reg_max") c->sort.reg_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_REG_MAX);
     else if (n == "sort_lds_max") c->sort.lds_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_LDS_MAX);
