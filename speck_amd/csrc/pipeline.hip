@@ -20,7 +20,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <string>
 #include <vector>
 
@@ -153,15 +152,10 @@ struct speck_config {
     // would have (nnz(C) = what the buffers hold, the classes with rows, the spill pool, the verdict of the input check: its
     // stream is joined in front of the scan); on a miss nothing of C is written and the call re-runs with its read-back.
     bool eager_through = true;
-    const u32* through_gate = nullptr;  // (set around enqueue_front: the verdict word the scan looks at)
-    u32 through_ticket = 0;             // != 0: ... and the ticket the check stores when it is done (its stream is not joined)
     hipEvent_t vdone = nullptr;         // the input check's stream, joined in front of that scan
     u64 through_hits = 0, through_misses = 0;
     u64 spec_rows_a = 0, spec_rows_b = 0;
     int eager_spec_hits = 0, eager_spec_misses = 0;
-    const u32* stage_off_src = nullptr;  // call in flight: the staged row offsets ride to C in the numeric light
-    u32* stage_off_dst = nullptr;        //   launch (RowWork::off_src)
-    u32 stage_off_n = 0;
     bool validate_inputs = true;  // complete call: B's rows strictly ascending and in range
     bool concurrent_classes = true;
     u32 max_side_streams = 12;
@@ -193,18 +187,12 @@ struct speck_config {
     Prediction pred, gpred;
     DeviceStats last_eager_stats{};  // final statistics block of the last complete call (what `pred` goes with)
     bool pred_valid = false;         // pred.off holds the offsets of the last complete call
-    bool nf_direct = true;           // option nf_direct
-    bool capture_direct = false;     // set while a sequence with direct placement is being enqueued
+    bool nf_direct = true;           // option nf_direct: a reuse sequence places its numeric-first rows directly
     bool esc_fused = true;           // option esc_fused: such a sequence finishes the rows of the register classes in
                                      //   its symbolic phase
-    bool capture_fused = false;      // set while a sequence that does so is being enqueued
-    u32* capture_c_col = nullptr;
-    void* capture_c_val = nullptr;
     ReplayPlan plan{};
     bool skip_scan = true;           // option skip_scan: a reuse sequence that follows a replay of itself has no scan kernel
-    bool capture_skip_scan = false;  // set while such a sequence is being enqueued
     int num_verify = 1;              // option num_verify (0: never, 1: when it pays, 2: whenever possible): ... and no symbolic pass for its hash / dense rows (ReplayPlan::num_verify)
-    bool capture_num_verify = false;
     // The inputs the analysis depends on as the last WRITING analysis saw them (stages.hip, launch_snapshot_inputs): A's
     // column ids | B's row offsets | first and last column id of every row of B.  The verifier of a reuse sequence
     // compares the inputs with this copy instead of recomputing the analysis (option verify_inputs); grow-only, and like
@@ -214,11 +202,9 @@ struct speck_config {
     bool verify_inputs = true;
     bool snap_pending = false;       // the verifier of the call in flight recomputes the analysis AND takes the copy
     bool snap_for_arena = false;     // the copy holds the inputs the arena's metadata was derived from (and verified against)
-    std::function<int()> after_analysis;  // set by a complete call for the duration of its first batch (multiply_impl)
     bool arena_from_replay = false;  // the arena (numeric records, lists, class table, statistics) was last written by a completed
                                      //   REPLAY of arena_key's problem: the layout a sequence without a scan reads
     bool overlap_analysis = true;    // option overlap_analysis: a reuse sequence runs its analysis as a verifier beside it
-    bool capture_overlap = false;    // set while such a sequence is being enqueued
     hipStream_t vstream = nullptr;   // the verifier's stream
     u32* h_verify = nullptr;         // its verdict (word 0) and its completion ticket (word 16): pinned, mapped
     u32* h_verify_dev = nullptr;
@@ -250,8 +236,6 @@ struct speck_config {
     // allocated (the caller's matOut of the previous call) and the class counts of the previous complete call for grids.
     int one_walk = 0;                // option: 0 never (default: measured and lost on every stand-in but cant),
                                      //   1 when the previous call says the walk kernel takes a good share of the rows, 2 whenever possible
-    bool capture_one_walk = false;   // set while such a call is being enqueued
-    u64 ow_c_cap = 0;                // ... entries the caller's C buffers hold
     bool last_was_walk = false;      // the last complete call was one (its nf_entries count the register-class slots too)
     u64 last_nf_entries = 0;         // scratch-pool entries the last complete call's analysis counted
     int walks = 0, walk_misses = 0;
@@ -501,7 +485,45 @@ int ensure_nfpool(speck_config* c, u64 entries, size_t vsize)
     return SPECK_OK;
 }
 
-RowWork make_work(speck_config* c, const Scratch& sc, const SpillBuffers& spill, u32 m, bool symbolic_phase = false)
+int begin_validate(speck_config* c, const speck_dcsr* B, hipStream_t gate = nullptr);
+
+// The input check of a complete call, started once: behind the launch of the analysis, the head of the call's critical
+// path, and beside that latency-bound kernel rather than beside the symbolic launches
+struct InputCheck {
+    speck_config* c;
+    const speck_dcsr* B;
+    hipStream_t s;
+    bool started = false;
+    int start()
+    {
+        if (!c->validate_inputs || started) return SPECK_OK;
+        started = true;
+        return begin_validate(c, B, s);
+    }
+};
+
+// What kind of call is being enqueued.  Whoever enqueues builds one on the stack and hands it to make_work,
+// enqueue_front and enqueue_back: it is gone with the call.  Default: a plain complete call, nothing staged.
+struct CallForm {
+    // a reuse sequence (enqueue_replay maps its ReplayPlan onto these): rows placed where the previous identical call put
+    // them | register-class rows finished in the symbolic phase | no analysis IN the sequence, A's offsets are the arena's
+    // copy | no scan kernel | the numeric launches in their verifying forms
+    bool direct = false, fused = false, overlap = false, skip_scan = false, num_verify = false;
+    bool one_walk = false;  // the one-walk complete call (walk.hip)
+    u32* c_col = nullptr;   // C's buffers, for the rows placed early (direct, one_walk) ...
+    void* c_val = nullptr;
+    u64 c_cap = 0;          // ... and the entries they hold (one_walk)
+    const u32* off_src = nullptr;  // the staged row offsets ride to C in the numeric light launch (RowWork::off_src)
+    u32* off_dst = nullptr;
+    u32 off_n = 0;
+    const u32* through_gate = nullptr;     // through call: the verdict word of the input check, which the scan looks at
+    u32 through_ticket = 0;                // != 0: ... and the ticket the check stores when it is done (its stream is not joined)
+    InputCheck* after_analysis = nullptr;  // complete call: started behind the launch of the analysis
+    u32 nf_wcols = kNumD1Cols;             // LDS window of the numeric-first kernel: c->nf_wcols, or a plan's
+};
+
+RowWork make_work(speck_config* c, const Scratch& sc, const SpillBuffers& spill, u32 m, const CallForm& f,
+                  bool symbolic_phase = false)
 {
     RowWork w{};
     w.recs = symbolic_phase ? sc.sym_recs : sc.num_recs;
@@ -513,16 +535,16 @@ RowWork make_work(speck_config* c, const Scratch& sc, const SpillBuffers& spill,
     w.nf_col = static_cast<u32*>(c->nfpool);
     w.nf_val = c->nfpool ? static_cast<unsigned char*>(c->nfpool) + Carver::need(c->nf_cap_entries, 4) : nullptr;
     w.nf_cap = c->nfpool ? c->nf_cap_entries : 0;
-    w.nf_pred_off = (c->capture_direct || c->capture_skip_scan) ? c->gpred.off : nullptr;
-    w.nf_direct_col = c->capture_direct ? c->capture_c_col : nullptr;
-    w.nf_direct_val = c->capture_direct ? c->capture_c_val : nullptr;
+    w.nf_pred_off = (f.direct || f.skip_scan) ? c->gpred.off : nullptr;
+    w.nf_direct_col = f.direct ? f.c_col : nullptr;
+    w.nf_direct_val = f.direct ? f.c_val : nullptr;
     w.w_sl = sc.w_sl;
     w.xcd_aware = c->xcd_aware;
-    w.off_src = symbolic_phase ? nullptr : c->stage_off_src;
-    w.off_dst = symbolic_phase ? nullptr : c->stage_off_dst;
-    w.off_n = symbolic_phase ? 0u : c->stage_off_n;
-    w.verify_counts = c->capture_skip_scan ? 1u : 0u;
-    w.verify_numeric = c->capture_num_verify ? 1u : 0u;
+    w.off_src = symbolic_phase ? nullptr : f.off_src;
+    w.off_dst = symbolic_phase ? nullptr : f.off_dst;
+    w.off_n = symbolic_phase ? 0u : f.off_n;
+    w.verify_counts = f.skip_scan ? 1u : 0u;
+    w.verify_numeric = f.num_verify ? 1u : 0u;
     return w;
 }
 
@@ -706,58 +728,68 @@ struct Timing {
     std::vector<ClassTiming> sym, num;
 };
 
+// What enqueue_front is given beside the form; the defaults are a plain complete call's.
+struct FrontArgs {
+    u64 exact_nnz = ~0ull;  // nnz(C) the scan insists on
+    u32 sym_mask = kAllSym, num_mask = kAllNum;
+    bool classify_numeric = true;
+    const u32* sym_hint = nullptr;  // rows per symbolic class: grids, fork decisions
+    bool hint_exact = true;         // ... and they are THIS call's counts
+    DeviceStats* host_mirror = nullptr;
+    u64 expect_g = ~0ull, expect_nf = ~0ull;
+    u32 expect_g_rows = ~0u;
+    u32 parts = 3;                // 1: analysis + binning, 2: symbolic launches + scan
+    u32* pred_off_out = nullptr;  // what this call leaves for a repeated one to place rows by
+};
+
 // analysis (+ symbolic binning) -> symbolic classes -> scan (+ numeric binning).  Nothing here needs a host
 // decision: `sym_mask` only prunes kernels of classes known to be empty (first call: all).
-int enqueue_front(speck_config* c, hipStream_t s, const speck_dcsr* A_in, const speck_dcsr* B,
-                  const Scratch& sc, u32 vsize, u64 exact_nnz, u32 sym_mask, u32 num_mask,
-                  bool classify_numeric, Timing* tm, const u32* sym_hint = nullptr,
-                  DeviceStats* host_mirror = nullptr, u64 expect_g = ~0ull, u32 expect_g_rows = ~0u,
-                  u32 parts = 3 /* 1: analysis + binning, 2: symbolic launches + scan */, u64 expect_nf = ~0ull,
-                  u32* pred_off_out = nullptr /* what this call leaves for a repeated one to place rows by */,
-                  bool hint_exact = true /* sym_hint holds THIS call's counts */)
+int enqueue_front(speck_config* c, hipStream_t s, const speck_dcsr* A_in, const speck_dcsr* B, const Scratch& sc,
+                  u32 vsize, const CallForm& f, const FrontArgs& a, Timing* tm)
 {
     const u32 m = (u32)A_in->rows;
-    // A sequence whose analysis only verifies (capture_overlap) reads A's row offsets where the previous identical call
+    const u32 sym_mask = a.sym_mask;
+    const u32* const sym_hint = a.sym_hint;
+    // A sequence whose analysis only verifies (CallForm::overlap) reads A's row offsets where the previous identical call
     // left them, like the rest of the structure-derived metadata: whatever the caller does to A.row_offsets while the
     // sequence runs, its kernels see ONE consistent structure, and the verifier says whether it is still A's.
     speck_dcsr a_stored = *A_in;
-    if (c->capture_overlap) a_stored.row_offsets = sc.a_ro_copy;
+    if (f.overlap) a_stored.row_offsets = sc.a_ro_copy;
     const speck_dcsr* const A = &a_stored;
     u32* const c_ro = sc.counts;  // the symbolic kernels count into scratch; the scan writes sc.offsets
     ClassifyParams cp = c->cp;
     cp.sym_allowed = sym_mask;
-    cp.num_allowed = num_mask;
+    cp.num_allowed = a.num_mask;
     cp.esc16 = (c->cp.esc16 && B->cols <= (1ull << 26)) ? 1u : 0u;  // (column << 6 | product number) fits 32 bits
-    cp.esc_fused = c->capture_fused ? 1u : 0u;
-    cp.one_walk = c->capture_one_walk ? 1u : 0u;
+    cp.esc_fused = f.fused ? 1u : 0u;
+    cp.one_walk = f.one_walk ? 1u : 0u;
     cp.slice_ops = (c->cp.slice_ops && u64(B->cols) <= kSliceMaxCols) ? c->cp.slice_ops : 0u;  // (as enqueue_back launches)
-    if (c->capture_one_walk) {  // (the walk kernel takes the register-class rows and moves the numeric-first ones itself)
+    if (f.one_walk) {  // (the walk kernel takes the register-class rows and moves the numeric-first ones itself)
         cp.sym_allowed |= kSymEscMask;
         cp.num_allowed |= kNumEscMask | (1u << NUM_NFCOPY);
     }
     u64* const bytes = c->cp.want_bytes ? c->d_bytes : nullptr;
     const bool timed = c->profile_kernels && tm;
-    if (parts & 1u) {
+    if (a.parts & 1u) {
         if (timed) {
             tm->ev_analysis = tm->ev;
             (void)hipEventRecord(kernel_event(c, tm->ev++), s);
         }
-        // (capture_overlap: no analysis IN the sequence -- launch_verifier puts it on a stream of its own)
-        if (!c->capture_overlap) {
+        // (overlap: no analysis IN the sequence -- launch_verifier puts it on a stream of its own)
+        if (!f.overlap) {
             if (bytes) HIP_TRY(hipMemsetAsync(bytes, 0, 2 * kMaxClasses * sizeof(u64), s));
             Chain chain;
             const int crc = next_chain(c, s, &chain);
             if (crc != SPECK_OK) return crc;
             launch_analysis(s, A->row_offsets, A->col_ids, B->row_offsets, B->col_ids, m, A->nnz, sc.row_ops,
                             sc.row_max_ops, sc.row_col_min, sc.row_col_max, sc.cls_sym, c_ro, sc.sym_recs,
-                            c->d_stats, cp, sc.b_sl, chain, sc.nf_off, expect_nf, (u32)B->rows, sc.a_ro_copy, nullptr, bytes,
+                            c->d_stats, cp, sc.b_sl, chain, sc.nf_off, a.expect_nf, (u32)B->rows, sc.a_ro_copy, nullptr, bytes,
                             B->nnz);
             c->snap_for_arena = false;  // (a writing analysis: the copy of the inputs is not its)
         }
-        // (complete call: the input check of B goes onto its stream HERE -- behind the launch of the analysis, the head of
-        //  the call's critical path, and beside that latency-bound kernel rather than beside the symbolic launches)
-        if (c->after_analysis) {
-            const int hrc = c->after_analysis();
+        // (complete call: the input check of B goes onto its stream HERE)
+        if (f.after_analysis) {
+            const int hrc = f.after_analysis->start();
             if (hrc != SPECK_OK) return hrc;
         }
         if (timed) {
@@ -766,8 +798,8 @@ int enqueue_front(speck_config* c, hipStream_t s, const speck_dcsr* A_in, const 
         }
         LAUNCHES_OK();
     }
-    if (!(parts & 2u)) return SPECK_OK;
-    const RowWork w = make_work(c, sc, SpillBuffers{}, m, true);
+    if (!(a.parts & 2u)) return SPECK_OK;
+    const RowWork w = make_work(c, sc, SpillBuffers{}, m, f, true);
     // heaviest classes first: they have the longest tails
     u32 all_m[kMaxClasses];
     for (auto& x : all_m) x = m;  // no host-known counts: size every class for rows(A)
@@ -777,21 +809,21 @@ int enqueue_front(speck_config* c, hipStream_t s, const speck_dcsr* A_in, const 
                          [&](hipStream_t ks, int cls, hipEvent_t e0, hipEvent_t e1) {
                              if (cls == kLight) {
                                  launch_symbolic_light(ks, hint, sym_mask & kSymLightMask, A->row_offsets, sc.b_sl, B->col_ids, w,
-                                                       c_ro, c->sm, sym_hint != nullptr && hint_exact,
-                                                       c->capture_fused ? vsize : 0u, A->data, B->data, e0, e1);
+                                                       c_ro, c->sm, sym_hint != nullptr && a.hint_exact,
+                                                       f.fused ? vsize : 0u, A->data, B->data, e0, e1);
                              } else if (cls == SYM_NF) {
                                  // the numeric dense-window kernel, in the symbolic phase (numeric.hip)
                                  with_value_type(vsize, [&](auto t) {
                                      using T = decltype(t);
                                      launch_numeric_first<T>(ks, hint[cls], view_of<T>(A), view_of<T>(B), w, c_ro, c->sm,
-                                                             c->nf_wcols, e0, e1);
+                                                             f.nf_wcols, e0, e1);
                                  });
                              } else
                                  launch_symbolic(ks, cls, hint[cls], A->row_offsets, sc.b_sl,
                                                  B->col_ids, w, c_ro, c->sm);
                          });
     if (rc != SPECK_OK) return rc;
-    if (c->capture_one_walk) {
+    if (f.one_walk) {
         // the walk kernel: scan + numeric binning + the numeric walk of the register-class rows (walk.hip); its events
         // carry the kernel's own begin and end
         hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -810,20 +842,20 @@ int enqueue_front(speck_config* c, hipStream_t s, const speck_dcsr* A_in, const 
         wa.counts = c_ro;
         wa.nf_off = sc.nf_off;
         wa.offsets_out = sc.offsets;
-        wa.pred_off_out = pred_off_out;
+        wa.pred_off_out = a.pred_off_out;
         wa.recs = sc.num_recs;
         wa.st = c->d_stats;
-        wa.c_col = c->capture_c_col;
-        wa.c_val = c->capture_c_val;
-        wa.c_cap = c->ow_c_cap;
+        wa.c_col = f.c_col;
+        wa.c_val = f.c_val;
+        wa.c_cap = f.c_cap;
         wa.pool_col = w.nf_col;
         wa.pool_val = w.nf_val;
         wa.pool_cap = w.nf_cap;
         wa.m = m;
         wa.vsize = vsize;
         wa.cp = cp;
-        wa.expect_g = expect_g;
-        wa.expect_g_rows = expect_g_rows;
+        wa.expect_g = a.expect_g;
+        wa.expect_g_rows = a.expect_g_rows;
         wa.bytes_acc = bytes;
         with_value_type(vsize, [&](auto t) {
             using T = decltype(t);
@@ -837,7 +869,7 @@ int enqueue_front(speck_config* c, hipStream_t s, const speck_dcsr* A_in, const 
         tm->ev_scan = tm->ev;
         (void)hipEventRecord(kernel_event(c, tm->ev++), s);
     }
-    if (c->capture_skip_scan) {
+    if (f.skip_scan) {
         // no scan: every row's nnz was compared with the previous call's where it was produced (store_row_count, the
         // fused register-class bodies, the numeric-first kernel); the numeric launches read what that call's scan left
     } else {
@@ -846,15 +878,15 @@ int enqueue_front(speck_config* c, hipStream_t s, const speck_dcsr* A_in, const 
         if (crc != SPECK_OK) return crc;
         // (through call: the input check finished long ago, or at least before this scan.  A LARGE B: its stream is joined;
         //  else the scan looks for the check's ticket -- a join costs ~6 us of this short call even on a finished branch)
-        if (c->through_gate && !c->through_ticket) {
+        if (f.through_gate && !f.through_ticket) {
             HIP_TRY(hipEventRecord(c->vdone, c->vstream));
             HIP_TRY(hipStreamWaitEvent(s, c->vdone, 0));
         }
         launch_scan(s, c_ro, sc.offsets, m, A->row_offsets, sc.row_ops, sc.row_col_min, sc.row_col_max,
-                    classify_numeric ? sc.num_recs : nullptr, c->d_stats, cp, vsize, exact_nnz, chain, host_mirror,
-                    expect_g, expect_g_rows, c->capture_direct ? c->gpred.off : nullptr, pred_off_out,
-                    host_mirror ? c->d_ticket : nullptr, host_mirror ? c->h_ticket_dev : nullptr, bytes, c->through_gate,
-                    c->through_ticket);
+                    a.classify_numeric ? sc.num_recs : nullptr, c->d_stats, cp, vsize, a.exact_nnz, chain, a.host_mirror,
+                    a.expect_g, a.expect_g_rows, f.direct ? c->gpred.off : nullptr, a.pred_off_out,
+                    a.host_mirror ? c->d_ticket : nullptr, a.host_mirror ? c->h_ticket_dev : nullptr, bytes,
+                    f.through_gate, f.through_ticket);
     }
     if (timed) (void)hipEventRecord(kernel_event(c, tm->ev++), s);
     LAUNCHES_OK();
@@ -863,14 +895,14 @@ int enqueue_front(speck_config* c, hipStream_t s, const speck_dcsr* A_in, const 
 
 template <typename T>
 int enqueue_back(speck_config* c, hipStream_t s, const speck_dcsr* A, const speck_dcsr* B,
-                 const Scratch& sc, u32* c_col, T* c_val, u32 num_mask,
+                 const Scratch& sc, const CallForm& f, u32* c_col, T* c_val, u32 num_mask,
                  const u32* counts /*host-known, or nullptr*/, Timing* tm)
 {
     const u32 m = (u32)A->rows;
     CsrView<T> Av = view_of<T>(A);
     const CsrView<T> Bv = view_of<T>(B);
-    if (c->capture_overlap) Av.row_offsets = sc.a_ro_copy;  // (as enqueue_front: the structure the sequence was built on)
-    RowWork w = make_work(c, sc, c->spill, m);
+    if (f.overlap) Av.row_offsets = sc.a_ro_copy;  // (as enqueue_front: the structure the sequence was built on)
+    RowWork w = make_work(c, sc, c->spill, m, f);
     w.sliced = (c->cp.slice_ops && u64(B->cols) <= kSliceMaxCols) ? 1u : 0u;  // (as enqueue_front classifies)
     // the staged offsets -> C.row_offsets: by extra workgroups of the numeric light launch when there is one, else by a
     // (guarded) copy of its own
@@ -1053,46 +1085,35 @@ template <typename T>
 int enqueue_replay(speck_config* c, hipStream_t s, const speck_dcsr* A, const speck_dcsr* B, const speck_dcsr* C,
                    const Scratch& sc, const ReplayPlan& p, Timing* tm, size_t* ev_num_end)
 {
-    c->capture_fused = p.fused;
-    c->capture_direct = p.direct;
-    c->capture_overlap = p.overlap;
-    c->capture_skip_scan = p.skip_scan;
-    c->capture_num_verify = p.num_verify || p.safe_numeric;
+    CallForm f;
+    f.fused = p.fused, f.direct = p.direct, f.overlap = p.overlap, f.skip_scan = p.skip_scan;
+    f.num_verify = p.num_verify || p.safe_numeric;
     // C.row_offsets <- the staged offsets of this call's scan, or (no scan) the sequence's own copy of the offsets
-    c->stage_off_src = p.skip_scan ? c->gpred.off : sc.offsets;
-    c->stage_off_dst = C->row_offsets;
-    c->stage_off_n = (u32)A->rows + 1u;
-    c->capture_c_col = C->col_ids;
-    c->capture_c_val = C->data;
-    struct Reset {
-        speck_config* c;
-        u32 wcols;
-        ~Reset()
-        {
-            c->capture_direct = c->capture_fused = c->capture_overlap = false;
-            c->stage_off_src = nullptr, c->stage_off_dst = nullptr, c->stage_off_n = 0;
-            c->capture_skip_scan = c->capture_num_verify = false;
-            c->nf_wcols = wcols;
-        }
-    } reset{c, c->nf_wcols};
-    c->nf_wcols = p.nf_wcols;
+    f.off_src = p.skip_scan ? c->gpred.off : sc.offsets;
+    f.off_dst = C->row_offsets;
+    f.off_n = (u32)A->rows + 1u;
+    f.c_col = C->col_ids, f.c_val = C->data;
+    f.nf_wcols = p.nf_wcols;  // (the plan's, not the config's: another problem may have been analysed since)
     // (num_verify: the symbolic phase is the register classes alone -- the plan keeps every class, for the form of the
     //  sequence that runs when the arena is not this problem's)
-    u32 sym_mask = p.sym_mask, sym_counts[kMaxClasses];
+    u32 sym_counts[kMaxClasses];
     std::memcpy(sym_counts, p.sym_counts, sizeof(sym_counts));
+    FrontArgs a;
+    a.exact_nnz = C->nnz;
+    a.sym_mask = p.sym_mask, a.num_mask = p.num_mask, a.sym_hint = sym_counts;
+    a.expect_g = p.g_products, a.expect_g_rows = p.num_counts[NUM_G], a.expect_nf = p.nf_cap_entries;
     if (p.num_verify) {
-        sym_mask &= kSymEscMask;
+        a.sym_mask &= kSymEscMask;
         for (int k = 0; k < kMaxClasses; ++k)
             if (!(kSymEscMask >> k & 1u)) sym_counts[k] = 0;
     }
-    int rc = enqueue_front(c, s, A, B, sc, (u32)sizeof(T), C->nnz, sym_mask, p.num_mask, true, tm, sym_counts, nullptr,
-                           p.g_products, p.num_counts[NUM_G], 3u, p.nf_cap_entries);
+    int rc = enqueue_front(c, s, A, B, sc, (u32)sizeof(T), f, a, tm);
     if (rc != SPECK_OK) return rc;
     if (tm) {
         tm->ev_num = tm->ev;
         (void)hipEventRecord(kernel_event(c, tm->ev++), s);
     }
-    rc = enqueue_back<T>(c, s, A, B, sc, C->col_ids, static_cast<T*>(C->data), p.launch_mask, p.num_counts, tm);
+    rc = enqueue_back<T>(c, s, A, B, sc, f, C->col_ids, static_cast<T*>(C->data), p.launch_mask, p.num_counts, tm);
     if (rc != SPECK_OK) return rc;
     if (tm) {
         *ev_num_end = tm->ev;
@@ -1204,7 +1225,7 @@ struct VerifierGuard {
 };
 
 // The input check of a complete call, beside it on the verifier's stream (stages.hip: validate_b_kernel).
-int begin_validate(speck_config* c, const speck_dcsr* B, hipStream_t gate = nullptr)
+int begin_validate(speck_config* c, const speck_dcsr* B, hipStream_t gate)
 {
     __atomic_store_n(c->h_verify, 0u, __ATOMIC_RELEASE);
     if (c->use_user_stream) {
@@ -1237,6 +1258,33 @@ int finish_validate(speck_config* c, bool* b_invalid)
     if (rc != SPECK_OK) return rc;
     *b_invalid = (__atomic_load_n(c->h_verify, __ATOMIC_ACQUIRE) & 4u) != 0;
     return SPECK_OK;
+}
+// What a complete call says of its inputs once the statistics of a batch are on the host: A (the analysis checks its
+// column ids), then B (the input check)
+int input_verdict(speck_config* c)
+{
+    if (c->h_stats->a_invalid) return SPECK_ERR_INVALID;
+    bool b_bad = false;
+    const int rc = finish_validate(c, &b_bad);
+    if (rc != SPECK_OK) return rc;
+    return b_bad ? SPECK_ERR_UNSORTED : SPECK_OK;
+}
+// A batch that wrote into the caller's buffers on the strength of the previous complete call: did that hold?
+bool speculation_held(const DeviceStats* h, u64 nnz_c)
+{
+    return !h->capacity_miss && !h->nnz_overflow && h->nnz_c == nnz_c && h->sum_products != 0;
+}
+// The sizing hints of such a batch: the rows per symbolic class of the previous complete call; returns the classes it
+// launches.  (The light launch is one kernel whatever it holds: every class of it may have rows.)
+u32 speculated_hints(const speck_config* c, u32 (&hints)[kMaxClasses])
+{
+    u32 mask = kSymLightMask;
+    for (int k = 0; k < kMaxClasses; ++k) {
+        hints[k] = c->last_sym_counts[k];
+        if (hints[k]) mask |= 1u << k;
+        if ((kSymLightMask >> k & 1u) && !hints[k]) hints[k] = 256;
+    }
+    return mask;
 }
 
 template <typename T>
@@ -1390,13 +1438,7 @@ int multiply_impl(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, spe
     const bool keep_pred = c->nf_direct && c->reuse && ensure_pred(c->pred, m);
     // (the scan mirrors the statistics and stores the ticket itself: await_scan_stats)
     const bool early_stats = c->spin_wait && !c->profile_kernels;
-    auto front = [&](u32 parts) {
-        // (the offsets go to scratch: C.row_offsets -- possibly the caller's reused buffer -- is written only once
-        //  nothing can fail any more)
-        return enqueue_front(c, s, A, B, sc, (u32)sizeof(T), ~0ull, kAllSym, kAllNum, true, &tm,
-                             parts == 2u ? sym_known : nullptr, early_stats ? c->h_stats_dev : nullptr, ~0ull, ~0u, parts, ~0ull,
-                             keep_pred ? c->pred.off : nullptr);
-    };
+    u32* const pred_out = keep_pred ? c->pred.off : nullptr;
     // ONE batch, sized from the previous complete call on this config (same shapes): the classes that call had rows in
     // (a row in any other class raises capacity_miss), grids from its counts, its scratch pool and numeric-first window
     // (checked by the analysis / numeric-first kernels).  Saves the first of the two read-backs.
@@ -1404,19 +1446,22 @@ int multiply_impl(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, spe
     // call on the verifier's stream; its verdict is looked at with the statistics of the scan, before anything of C is
     // written.  Until then the kernels stay inside their tables and windows whatever B holds (a requirement for every
     // kernel body: DESIGN.md 1).  A's column ids are checked -- and clamped -- by the analysis.
-    // (launched BEHIND the analysis of the call, not in front of it: enqueue_front calls it)
-    bool validate_started = false;
-    auto start_validate = [&]() -> int {
-        if (!c->validate_inputs || validate_started) return SPECK_OK;
-        validate_started = true;
-        return begin_validate(c, B, s);
+    // (launched BEHIND the analysis of the call, not in front of it: enqueue_front starts it)
+    InputCheck check{c, B, s};
+    // a form of this call: the config's numeric-first window as it is NOW, the input check behind the analysis
+    auto form = [&] {
+        CallForm f;
+        f.nf_wcols = c->nf_wcols, f.after_analysis = &check;
+        return f;
     };
-    struct HookGuard {
-        speck_config* c;
-        ~HookGuard() { c->after_analysis = nullptr; }
-    } hook_guard{c};
-    c->after_analysis = start_validate;
-    auto b_is_invalid = [&](bool* bad) { return finish_validate(c, bad); };
+    auto front = [&](u32 parts) {
+        // (the offsets go to scratch: C.row_offsets -- possibly the caller's reused buffer -- is written only once
+        //  nothing can fail any more)
+        FrontArgs a;
+        a.parts = parts, a.sym_hint = parts == 2u ? sym_known : nullptr;
+        a.host_mirror = early_stats ? c->h_stats_dev : nullptr, a.pred_off_out = pred_out;
+        return enqueue_front(c, s, A, B, sc, (u32)sizeof(T), form(), a, &tm);
+    };
     // ---- ONE-WALK call (walk.hip): when matOut is allocated and a complete call of the same shapes has run on the config,
     // the rows of the register classes are finished in ONE walk inside the kernel that places the rows -- no symbolic
     // pass for them, no scan kernel, no read-back before the numeric launches.  Everything the sequence assumes (classes
@@ -1439,8 +1484,9 @@ int multiply_impl(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, spe
             Chain3 ch3;
             rc = next_chain3(c, s, groups, &ch3);
             if (rc != SPECK_OK) return rc;
-            rc = enqueue_front(c, s, A, B, sc, (u32)sizeof(T), ~0ull, kAllSym, kAllNum, true, &tm, nullptr, nullptr, ~0ull, ~0u, 1u, ~0ull,
-                               nullptr);
+            FrontArgs fa;
+            fa.parts = 1u;
+            rc = enqueue_front(c, s, A, B, sc, (u32)sizeof(T), form(), fa, &tm);
             if (rc != SPECK_OK) return rc;
             hipEvent_t e0 = nullptr, e1 = nullptr;
             if (c->profile_kernels) {
@@ -1475,13 +1521,9 @@ int multiply_impl(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, spe
             LAUNCHES_OK();
             rc = read_stats(c, s);
             if (rc != SPECK_OK) return rc;
-            if (c->h_stats->a_invalid) return SPECK_ERR_INVALID;
-            bool b_bad = false;
-            rc = b_is_invalid(&b_bad);
+            rc = input_verdict(c);
             if (rc != SPECK_OK) return rc;
-            if (b_bad) return SPECK_ERR_UNSORTED;
-            const bool ok = !c->h_stats->capacity_miss && !c->h_stats->nnz_overflow && c->h_stats->nnz_c == C->nnz &&
-                            c->h_stats->sum_products != 0;
+            const bool ok = speculation_held(c->h_stats, C->nnz);
             ++(ok ? c->walks : c->walk_misses);
             if (ok) {
                 publish_counts(c, s);
@@ -1505,7 +1547,7 @@ int multiply_impl(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, spe
                 }
                 return SPECK_OK;
             }
-            validate_started = false;  // (the two-phase call checks B again)
+            check.started = false;  // (the two-phase call checks B again)
             tm = Timing{};
         }
     }
@@ -1518,51 +1560,32 @@ int multiply_impl(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, spe
         const bool pays = c->one_walk >= 2 || 8 * (esc_rows + sc_last[SYM_NF]) >= m;
         const u64 want = c->last_was_walk ? c->last_nf_entries + c->last_nf_entries / 32 + 4096 : c->last_nf_entries + esc_bound + 4096;
         if (pays && want < (1ull << 40) && ensure_nfpool(c, want, sizeof(T)) == SPECK_OK) {
-            u32 sym_mask = kSymLightMask, hints[kMaxClasses];
-            for (int k = 0; k < kMaxClasses; ++k) {
-                hints[k] = c->last_sym_counts[k];
-                if (hints[k]) sym_mask |= 1u << k;
-                if ((kSymLightMask >> k & 1u) && !hints[k]) hints[k] = 256;
-            }
-            sym_mask &= ~kSymEscMask;
+            u32 hints[kMaxClasses];
             const u32 launch_mask = c->last_num_mask & ~(kNumEscMask | (1u << NUM_NFCOPY));
-            struct WalkFlags {
-                speck_config* c;
-                ~WalkFlags()
-                {
-                    c->capture_one_walk = false;
-                    c->capture_c_col = nullptr, c->capture_c_val = nullptr;
-                    c->stage_off_src = nullptr, c->stage_off_dst = nullptr, c->stage_off_n = 0;
-                }
-            } walk_flags{c};
-            c->capture_one_walk = true;
-            c->capture_c_col = C->col_ids;
-            c->capture_c_val = C->data;
-            c->ow_c_cap = C->nnz;
-            c->stage_off_src = sc.offsets;
-            c->stage_off_dst = C->row_offsets;
-            c->stage_off_n = m + 1;
-            rc = enqueue_front(c, s, A, B, sc, (u32)sizeof(T), ~0ull, sym_mask, launch_mask, true, &tm, hints, nullptr,
-                               c->last_g_products, c->last_num_counts[NUM_G], 3u, c->nf_cap_entries,
-                               keep_pred ? c->pred.off : nullptr, false);
+            CallForm f = form();
+            f.one_walk = true;
+            f.c_col = C->col_ids, f.c_val = C->data, f.c_cap = C->nnz;
+            f.off_src = sc.offsets, f.off_dst = C->row_offsets, f.off_n = m + 1;
+            FrontArgs fa;
+            fa.sym_mask = speculated_hints(c, hints) & ~kSymEscMask, fa.num_mask = launch_mask;
+            fa.sym_hint = hints, fa.hint_exact = false;
+            fa.expect_g = c->last_g_products, fa.expect_g_rows = c->last_num_counts[NUM_G], fa.expect_nf = c->nf_cap_entries;
+            fa.pred_off_out = pred_out;
+            rc = enqueue_front(c, s, A, B, sc, (u32)sizeof(T), f, fa, &tm);
             if (rc != SPECK_OK) return rc;
             if (c->profile_kernels) {
                 tm.ev_num = tm.ev;
                 (void)hipEventRecord(kernel_event(c, tm.ev++), s);
             }
-            rc = enqueue_back<T>(c, s, A, B, sc, C->col_ids, static_cast<T*>(C->data), launch_mask, c->last_num_counts, &tm);
+            rc = enqueue_back<T>(c, s, A, B, sc, f, C->col_ids, static_cast<T*>(C->data), launch_mask, c->last_num_counts, &tm);
             if (rc != SPECK_OK) return rc;
             ev_num_end = tm.ev;
             if (c->profile_kernels) (void)hipEventRecord(kernel_event(c, tm.ev++), s);
             rc = read_stats(c, s);  // (done_kernel + ticket; the one wait of the call)
             if (rc != SPECK_OK) return rc;
-            if (c->h_stats->a_invalid) return SPECK_ERR_INVALID;
-            bool b_bad = false;
-            rc = b_is_invalid(&b_bad);
+            rc = input_verdict(c);
             if (rc != SPECK_OK) return rc;
-            if (b_bad) return SPECK_ERR_UNSORTED;
-            walked = !c->h_stats->capacity_miss && !c->h_stats->nnz_overflow && c->h_stats->nnz_c == C->nnz &&
-                     c->h_stats->sum_products != 0;
+            walked = speculation_held(c->h_stats, C->nnz);
             ++(walked ? c->walks : c->walk_misses);
             if (walked) {
                 publish_counts(c, s);
@@ -1571,7 +1594,7 @@ int multiply_impl(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, spe
                 t->spGEMMCounting = 0.f;
                 t->spGEMMNumeric = st.lap();
             } else {
-                validate_started = false;  // (the two-phase call checks B again: its verdict word was consumed)
+                check.started = false;  // (the two-phase call checks B again: its verdict word was consumed)
             }
         }
     }
@@ -1583,42 +1606,26 @@ int multiply_impl(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, spe
         c_ready && C->nnz <= 0xFFFFFFFFull && C->nnz == c->last_eager_stats.nnz_c && c->last_num_mask && !c->last_was_walk &&
         !c->profile_kernels && !t->measureAll && c->spin_wait && !c->cp.want_bytes &&
         (!(c->last_num_mask >> NUM_G & 1u) || c->spill.plan != nullptr)) {
-        u32 hints[kMaxClasses], mask = kSymLightMask;
-        for (int k = 0; k < kMaxClasses; ++k) {
-            hints[k] = c->last_sym_counts[k];
-            if (hints[k]) mask |= 1u << k;
-            if ((kSymLightMask >> k & 1u) && !hints[k]) hints[k] = 256;
-        }
-        struct ThroughFlags {
-            speck_config* c;
-            ~ThroughFlags()
-            {
-                c->through_gate = nullptr, c->through_ticket = 0;
-                c->stage_off_src = nullptr, c->stage_off_dst = nullptr, c->stage_off_n = 0;
-            }
-        } through_flags{c};
-        c->through_gate = c->validate_inputs ? c->h_verify_dev : nullptr;
+        u32 hints[kMaxClasses];
+        CallForm f = form();
+        f.through_gate = c->validate_inputs ? c->h_verify_dev : nullptr;
         // (the ticket the check of THIS call will store: wait_verifier counts them)
-        c->through_ticket = (c->validate_inputs && B->nnz < c->validate_after_nnz) ? c->vticket_expected + 1u : 0u;
-        c->stage_off_src = sc.offsets;
-        c->stage_off_dst = C->row_offsets;  // (c_ready: c_ro IS C's array)
-        c->stage_off_n = m + 1;
-        const bool has_g = (c->last_num_mask >> NUM_G & 1u) != 0;
-        rc = enqueue_front(c, s, A, B, sc, (u32)sizeof(T), C->nnz, mask, c->last_num_mask, true, &tm, hints, nullptr,
-                           has_g ? c->last_g_products : ~0ull, has_g ? c->last_num_counts[NUM_G] : ~0u, 3u, c->nf_cap_entries,
-                           keep_pred ? c->pred.off : nullptr, true);
+        f.through_ticket = (c->validate_inputs && B->nnz < c->validate_after_nnz) ? c->vticket_expected + 1u : 0u;
+        f.off_src = sc.offsets, f.off_dst = C->row_offsets, f.off_n = m + 1;  // (c_ready: c_ro IS C's array)
+        FrontArgs fa;
+        fa.exact_nnz = C->nnz;
+        fa.sym_mask = speculated_hints(c, hints), fa.num_mask = c->last_num_mask, fa.sym_hint = hints;
+        if (c->last_num_mask >> NUM_G & 1u) fa.expect_g = c->last_g_products, fa.expect_g_rows = c->last_num_counts[NUM_G];
+        fa.expect_nf = c->nf_cap_entries, fa.pred_off_out = pred_out;
+        rc = enqueue_front(c, s, A, B, sc, (u32)sizeof(T), f, fa, &tm);
         if (rc != SPECK_OK) return fail(rc);
-        rc = enqueue_back<T>(c, s, A, B, sc, C->col_ids, static_cast<T*>(C->data), c->last_num_mask, c->last_num_counts, &tm);
+        rc = enqueue_back<T>(c, s, A, B, sc, f, C->col_ids, static_cast<T*>(C->data), c->last_num_mask, c->last_num_counts, &tm);
         if (rc != SPECK_OK) return fail(rc);
         rc = read_stats(c, s);  // (done_kernel + ticket: the one wait of the call)
         if (rc != SPECK_OK) return fail(rc);
-        if (c->h_stats->a_invalid) return fail(SPECK_ERR_INVALID);
-        bool b_bad = false;
-        rc = b_is_invalid(&b_bad);
+        rc = input_verdict(c);  // (a B that fails the check: the scan saw the verdict, nothing of C was written)
         if (rc != SPECK_OK) return fail(rc);
-        if (b_bad) return fail(SPECK_ERR_UNSORTED);  // (the scan saw the verdict: nothing of C was written)
-        through_ok = !c->h_stats->capacity_miss && !c->h_stats->nnz_overflow && c->h_stats->nnz_c == C->nnz &&
-                     c->h_stats->sum_products != 0;
+        through_ok = speculation_held(c->h_stats, C->nnz);
         ++(through_ok ? c->through_hits : c->through_misses);
         if (through_ok) {
             publish_counts(c, s);
@@ -1637,7 +1644,7 @@ int multiply_impl(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, spe
             c->h_stats->capacity_miss = 0;
             through_missed = through_front = true;
         } else {
-            validate_started = false;  // (the call below checks B again: the verdict word was consumed)
+            check.started = false;  // (the call below checks B again: the verdict word was consumed)
             tm = Timing{};
             through_missed = true;
         }
@@ -1647,25 +1654,14 @@ int multiply_impl(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, spe
     if (through_front) c->last.eager_speculated = 1;
     u32 spec_counts[kMaxClasses];
     if (c->eager_speculate && !through_missed && c->spec_valid && c->spec_rows_a == A->rows && c->spec_rows_b == B->rows) {
-        u32 mask = 0;
-        for (int k = 0; k < kMaxClasses; ++k) {
-            spec_counts[k] = c->last_sym_counts[k];
-            if (spec_counts[k]) mask |= 1u << k;
-        }
-        // (the light launch is one kernel whatever it holds: every class of it may have rows)
-        for (int k = 0; k < kMaxClasses; ++k)
-            if ((kSymLightMask >> k & 1u) && !spec_counts[k]) spec_counts[k] = 256;
-        mask |= kSymLightMask;
-        rc = enqueue_front(c, s, A, B, sc, (u32)sizeof(T), ~0ull, mask, kAllNum, true, &tm, spec_counts,
-                           early_stats ? c->h_stats_dev : nullptr, ~0ull, ~0u, 3u, c->nf_cap_entries,
-                           keep_pred ? c->pred.off : nullptr, true);
+        FrontArgs fa;
+        fa.sym_mask = speculated_hints(c, spec_counts), fa.sym_hint = spec_counts;
+        fa.host_mirror = early_stats ? c->h_stats_dev : nullptr;
+        fa.expect_nf = c->nf_cap_entries, fa.pred_off_out = pred_out;
+        rc = enqueue_front(c, s, A, B, sc, (u32)sizeof(T), form(), fa, &tm);
         if (rc == SPECK_OK) rc = early_stats ? await_scan_stats(c, s) : read_stats(c, s);
+        if (rc == SPECK_OK) rc = input_verdict(c);
         if (rc != SPECK_OK) return fail(rc);
-        if (c->h_stats->a_invalid) return fail(SPECK_ERR_INVALID);
-        bool b_bad = false;
-        rc = b_is_invalid(&b_bad);
-        if (rc != SPECK_OK) return fail(rc);
-        if (b_bad) return fail(SPECK_ERR_UNSORTED);
         speculated = !c->h_stats->capacity_miss;
         ++(speculated ? c->eager_spec_hits : c->eager_spec_misses);
         c->last.eager_speculated = speculated ? 1 : -1;
@@ -1706,12 +1702,8 @@ int multiply_impl(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, spe
     rc = front(2u);
     if (rc != SPECK_OK) return fail(rc);
     rc = early_stats ? await_scan_stats(c, s) : read_stats(c, s);
+    if (rc == SPECK_OK) rc = input_verdict(c);
     if (rc != SPECK_OK) return fail(rc);
-    if (c->h_stats->a_invalid) return fail(SPECK_ERR_INVALID);
-    bool b_bad = false;
-    rc = b_is_invalid(&b_bad);
-    if (rc != SPECK_OK) return fail(rc);
-    if (b_bad) return fail(SPECK_ERR_UNSORTED);
     }  // !speculated
     t->countProducts = 0.f;
     t->loadBalanceCounting = 0.f;
@@ -1820,13 +1812,8 @@ int multiply_impl(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, spe
     own_ro = false;
     // the staged offsets -> C.row_offsets: by extra workgroups of the numeric light launch when there is one, else by a
     // copy of its own (enqueue_back)
-    struct Unstage {
-        speck_config* c;
-        ~Unstage() { c->stage_off_src = nullptr, c->stage_off_dst = nullptr, c->stage_off_n = 0; }
-    } unstage{c};
-    c->stage_off_src = sc.offsets;
-    c->stage_off_dst = c_ro;
-    c->stage_off_n = m + 1;
+    CallForm staged;
+    staged.off_src = sc.offsets, staged.off_dst = c_ro, staged.off_n = m + 1;
     t->allocC = st.lap();
     t->loadBalanceNumeric = 0.f;
 
@@ -1837,7 +1824,7 @@ int multiply_impl(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, spe
         tm.ev_num = tm.ev;
         (void)hipEventRecord(kernel_event(c, tm.ev++), s);
     }
-    rc = enqueue_back<T>(c, s, A, B, sc, c_col, static_cast<T*>(c_val), num_mask, c->h_stats->num.count, &tm);
+    rc = enqueue_back<T>(c, s, A, B, sc, staged, c_col, static_cast<T*>(c_val), num_mask, c->h_stats->num.count, &tm);
     if (rc != SPECK_OK) return rc;
     ev_num_end = tm.ev;
     if (c->profile_kernels) (void)hipEventRecord(kernel_event(c, tm.ev++), s);
@@ -2293,7 +2280,11 @@ int speck_symbolic(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, ui
     const u32 nf_was = c->cp.nf_min_ops, gh_was = c->cp.gh_per_window;
     c->cp.nf_min_ops = 0;  // structure only: no values here, every row through a symbolic kernel
     c->cp.gh_per_window = 0;  // ... one that needs no scratch pool
-    rc = enqueue_front(c, s, A, B, sc, 8, ~0ull, kAllSym, kAllNum, false, nullptr);
+    CallForm f;  // (no form of a multiply: only the window the symbolic phase's numeric-first launch is sized with)
+    f.nf_wcols = c->nf_wcols;
+    FrontArgs fa;
+    fa.classify_numeric = false;
+    rc = enqueue_front(c, s, A, B, sc, 8, f, fa, nullptr);
     c->cp.nf_min_ops = nf_was;
     c->cp.gh_per_window = gh_was;
     if (rc != SPECK_OK) return rc;
