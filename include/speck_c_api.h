@@ -570,8 +570,8 @@ int speck_scale_f32(speck_config *cfg, const speck_dcsr *A, const speck_scale_pa
  *  The entries are walked in tiles of SPECK_SPMV_TILE_ENTRIES, the reduction's, aligned to absolute positions; one path for
  *      every row length.  The 16-byte loads need data and col_ids on 16-byte boundaries; elsewhere the entries are loaded
  *      one by one, with the same results.
- *  Not built: A^T x (transpose, then spmv); several right-hand sides; vectors in float; a semiring other than (+, x); a
- *      spmv fused into the product that made A. ---- */
+ *  Not built: A^T x (transpose, then spmv); vectors in float; a semiring other than (+, x); a spmv fused into the product
+ *      that made A.  (Several right-hand sides: speck_spmm_* below.) ---- */
 #define SPECK_SPMV_TILE_ENTRIES 4096
 typedef struct speck_spmv_info {
     uint64_t rows_empty;   /* rows without an entry: s_i = +0.0 */
@@ -583,6 +583,54 @@ int speck_spmv_f64(speck_config *cfg, double alpha, const speck_dcsr *A, const d
                    speck_spmv_info *info /* may be NULL */);
 int speck_spmv_f32(speck_config *cfg, double alpha, const speck_dcsr *A, const double *d_x, double beta, double *d_y,
                    speck_spmv_info *info);
+
+/* ---- product with several right-hand sides (new: the reference has no counterpart): Y = alpha A X + beta Y, the block of
+ *      k vectors a block power or LOBPCG iteration, personalised PageRank for many seeds, a smoother applied to several
+ *      near-null-space vectors, the feature aggregation A X of a graph layer or a check with several probes holds.  A is
+ *      read ONCE for all k columns; the offsets and the ids are checked once and there is one read-back, where k calls of
+ *      speck_spmv_* read data and col_ids k times, queue 4 k launches and wait for k read-backs.
+ *  X is cols x k and Y is rows x k, both ROW-MAJOR DEVICE arrays of doubles for both value types: X(j,c) = d_X[j ldx + c],
+ *      Y(i,c) = d_Y[i ldy + c] with ldx >= k, ldy >= k -- a contiguous torch tensor or a column slice of one.  (Row-major
+ *      makes the gather of an entry's k values one contiguous read.)  The padding [k, ldx) of every row of X is never
+ *      read; the padding [k, ldy) of every row of Y is never read or written.  Y is indexed by the row INSIDE A: for a
+ *      row-range view the caller offsets the pointer by r0 ldy.  All index arithmetic i ld + c is 64-bit.
+ *  The defining property: for every c < k, column c of Y is BIT FOR BIT what speck_spmv_*(alpha, A, X(:,c), beta, Y(:,c))
+ *      writes on contiguous copies of the two columns.  So everything said there holds per column: the term
+ *      (double)a * X(j,c) rounded once, nothing fused; the tree of speck_reduce_*(SUM) over the absolute positions of the
+ *      entries; the same bits from run to run; a row-range view gives the rows of the whole result; beta == 0.0 does NOT
+ *      READ Y; alpha is always applied; a NaN or 0 * inf of X(j,c) lands in column c of exactly the rows that reference
+ *      j and nowhere else; duplicates add, rows need not be sorted.  k == 1 with ldx == ldy == 1 is speck_spmv_*.  No
+ *      floating-point atomic anywhere.
+ *  Refused before anything runs: all that speck_spmv_* refuses, with the vectors' ranges replaced by the SPANS
+ *      [d_X, d_X + (cols - 1) ldx + k) and [d_Y, d_Y + (rows - 1) ldy + k) -- padding between the rows included, so two
+ *      column slices of ONE tensor interleave and are refused (SPECK_ERR_INVALID) although they share no element; spans
+ *      that touch are served.  ldx < k or ldy < k: SPECK_ERR_INVALID.  k > SPECK_SPMM_MAX_RHS, ldx or ldy > 2^32, rows or
+ *      cols > 2^27: SPECK_ERR_DIM_LIMIT.  k == 0 or rows == 0: SPECK_OK, nothing written, *info zero.  nnz == 0 is valid
+ *      and gives Y = alpha * (+0.0) + beta * Y.
+ *  On any error NOTHING of Y is written (*info is zero once the arguments have passed).  No offset or column id is used as
+ *      an address before it was checked; an id >= cols raises the verdict, is clamped and never followed; the row sums
+ *      wait in a temporary of rows k doubles until the kernel queued last has seen the verdict of EVERY tile -- only it
+ *      writes Y, each element once by one thread.  One read-back, at the end.
+ *  Config stream, cfg == NULL and the guard_bytes canary zones as for speck_spmv_*; the temporaries are grow-only buffers
+ *      of the config's own, neither the multiply's arena nor those of speck_spmv_*.
+ *  The tiles are speck_spmv_*'s, each walked once: a thread keeps its 16 values and checked ids and takes the k columns in
+ *      blocks of SPECK_SPMM_COLUMN_BLOCK whose gathers are in flight together -- one 16-byte load per entry and pair of
+ *      columns where d_X lies on a 16-byte boundary and ldx is even, 8-byte loads elsewhere, with the same results.
+ *  info: rows_empty, rows_split, tiles and entries as speck_spmv_info -- they describe A, not k.
+ *  Not built: A^T X; column-major or float vectors; a semiring other than (+, x). ---- */
+#define SPECK_SPMM_MAX_RHS 1024
+#define SPECK_SPMM_COLUMN_BLOCK 4
+typedef struct speck_spmm_info {
+    uint64_t rows_empty;   /* rows without an entry: s(i,c) = +0.0 */
+    uint64_t rows_split;   /* rows whose entries lie in more than one tile */
+    uint64_t tiles;        /* tiles walked (each once, for all columns) */
+    uint64_t entries;      /* entries read = nnz */
+    uint64_t terms;        /* products formed = entries * k */
+} speck_spmm_info;
+int speck_spmm_f64(speck_config *cfg, double alpha, const speck_dcsr *A, const double *d_X, uint64_t ldx, uint32_t k,
+                   double beta, double *d_Y, uint64_t ldy, speck_spmm_info *info /* may be NULL */);
+int speck_spmm_f32(speck_config *cfg, double alpha, const speck_dcsr *A, const double *d_X, uint64_t ldx, uint32_t k,
+                   double beta, double *d_Y, uint64_t ldy, speck_spmm_info *info);
 
 /* ---- row-sharded multi-GPU (new: the reference is single-GPU, source/Executor.cpp:25).  One process per GPU;
  *      rank p multiplies the row range [b_p, b_{p+1}) of A (a view with absolute offsets, boundaries from

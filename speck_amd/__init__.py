@@ -18,4 +18,5 @@ from .api import (  # noqa: F401
     scale, normalize_rows, pattern_ones, ScaleInfo, MAP_IDENTITY, MAP_ABS, MAP_SQUARE, MAP_ONE, SCALE_MAPS,
     SCALE_NONE, SCALE_MUL, SCALE_DIV, SCALE_TILE_ENTRIES,
     spmv, SpmvInfo, SPMV_TILE_ENTRIES,
+    spmm, SpmmInfo, SPMM_MAX_RHS, SPMM_COLUMN_BLOCK,
 )

@@ -91,6 +91,12 @@ class CSpmvInfo(C.Structure):
     _fields_ = [("rows_empty", C.c_uint64), ("rows_split", C.c_uint64), ("tiles", C.c_uint64), ("entries", C.c_uint64)]
 
 
+class CSpmmInfo(C.Structure):
+    # include/speck_c_api.h: speck_spmm_info
+    _fields_ = [("rows_empty", C.c_uint64), ("rows_split", C.c_uint64), ("tiles", C.c_uint64), ("entries", C.c_uint64),
+                ("terms", C.c_uint64)]
+
+
 # every symbol include/speck_c_api.h declares, with its ctypes signature
 _P = C.POINTER
 _SIGS = {
@@ -134,6 +140,10 @@ _SIGS = {
     "speck_scale_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(CScaleParams), _P(DCsr), _P(CScaleInfo)]),
     "speck_spmv_f64": (C.c_int, [C.c_void_p, C.c_double, _P(DCsr), C.c_void_p, C.c_double, C.c_void_p, _P(CSpmvInfo)]),
     "speck_spmv_f32": (C.c_int, [C.c_void_p, C.c_double, _P(DCsr), C.c_void_p, C.c_double, C.c_void_p, _P(CSpmvInfo)]),
+    "speck_spmm_f64": (C.c_int, [C.c_void_p, C.c_double, _P(DCsr), C.c_void_p, C.c_uint64, C.c_uint32, C.c_double, C.c_void_p,
+                                 C.c_uint64, _P(CSpmmInfo)]),
+    "speck_spmm_f32": (C.c_int, [C.c_void_p, C.c_double, _P(DCsr), C.c_void_p, C.c_uint64, C.c_uint32, C.c_double, C.c_void_p,
+                                 C.c_uint64, _P(CSpmmInfo)]),
     "speck_compare_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), C.c_int, C.c_double, _P(C.c_uint64)]),
     "speck_compare_bounded_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), _P(DCsr), C.c_double, _P(C.c_uint64),
                                             _P(C.c_uint64)]),

@@ -826,3 +826,87 @@ def spmv(A, x, config, alpha=1.0, beta=0.0, y=None):
         _check(L.speck_dcsr_download(C.byref(buf._c), None, None, out.ctypes.data, 8), "spmv: download")
         out = out[:A.rows]
     return out, SpmvInfo(info)
+
+
+# include/speck_c_api.h: the most right-hand sides one call takes
+SPMM_MAX_RHS = 1024
+# ... and the columns a tile takes per round (SPECK_SPMM_COLUMN_BLOCK)
+SPMM_COLUMN_BLOCK = 4
+
+
+class SpmmInfo:
+    """speck_spmm_info: what the product with several right-hand sides walked (A's counts, and terms = entries * k)."""
+
+    def __init__(self, c):
+        self.rows_empty = int(c.rows_empty)
+        self.rows_split = int(c.rows_split)
+        self.tiles = int(c.tiles)
+        self.entries = int(c.entries)
+        self.terms = int(c.terms)
+
+    def __repr__(self):
+        return (f"SpmmInfo(rows_empty={self.rows_empty}, rows_split={self.rows_split}, tiles={self.tiles}, "
+                f"entries={self.entries}, terms={self.terms})")
+
+
+def _device_block(v, n, k, ld, what):
+    """(address, k, ld) of a row-major n x k block of float64: a device address with k and ld given, or a 2-D object with
+    data_ptr(), shape, stride() and dtype (a torch tensor, a column slice of one) checked"""
+    who = f"spmm: {what}"
+    if hasattr(v, "data_ptr"):
+        if not all(hasattr(v, a) for a in ("shape", "stride", "dtype")):
+            raise ValueError(f"{who} must have shape, stride() and dtype beside data_ptr()")
+        if str(v.dtype) not in ("torch.float64", "float64"):
+            raise ValueError(f"{who} must be float64, not {v.dtype}")
+        shape = tuple(int(d) for d in v.shape)
+        if len(shape) != 2 or shape[0] != n or (k is not None and shape[1] != int(k)):
+            raise ValueError(f"{who} has shape {shape}, the call asks for ({n}, {'k' if k is None else int(k)})")
+        k = shape[1]
+        s0, s1 = int(v.stride(0)), int(v.stride(1))
+        if k > 1 and s1 != 1:
+            raise ValueError(f"{who} must be row-major (stride(1) == 1), not stride {s1}")
+        if n > 1 and s0 < k:
+            raise ValueError(f"{who} has rows {s0} apart, fewer than its {k} columns")
+        if ld is not None and n > 1 and int(ld) != s0:
+            raise ValueError(f"{who} has rows {s0} apart, not ld = {int(ld)}")
+        return int(v.data_ptr()), k, max(s0, k) if n > 1 else (k if ld is None else int(ld))
+    if isinstance(v, (bool, float)) or not hasattr(v, "__index__"):
+        raise ValueError(f"{who} must be a 2-D float64 device tensor or a device address, not {type(v).__name__}")
+    if k is None:
+        raise ValueError(f"{who} is a device address: k must be given")
+    return int(v), int(k), int(k) if ld is None else int(ld)
+
+
+def spmm(A, X, config, alpha=1.0, beta=0.0, Y=None, k=None, ldx=None, ldy=None):
+    """Y = alpha A X + beta Y on a device matrix with k right-hand sides (speck_spmm_f64 / _f32).  X (A.cols x k) and Y
+    (A.rows x k, indexed by the row inside A: for a row_view pass the slice) are row-major device blocks of float64 for both
+    value types: a 2-D object with data_ptr(), shape, stride() and dtype -- a torch tensor or a column slice Z[:, a:b] of
+    one, with stride(1) == 1 and stride(0) >= k -- or a device address with k (and ldx / ldy, default k) given.  A is read
+    once for all columns; column c of Y is bit for bit spmv(A, X[:, c], ..., y=Y[:, c]) on contiguous copies, so all that
+    spmv promises holds per column; the padding between the rows of Y is neither read nor written.  The memory X spans
+    and the memory Y spans must not overlap (two column slices of one tensor do and are refused).  Y=None is allowed only
+    with beta == 0: the result is then a (rows, k) numpy array downloaded from a buffer of the library's allocator.
+    config may be None.  Returns (that array, or None where Y was given and holds the result on the device, SpmmInfo)."""
+    if Y is None and float(beta) != 0.0:
+        raise ValueError("spmm: beta != 0 needs a Y to read")
+    x_ptr, k, ldx = _device_block(X, A.cols, k, ldx, "X")
+    if Y is not None:
+        y_ptr, _, ldy = _device_block(Y, A.rows, k, ldy, "Y")
+    if k < 0 or ldx < k or (Y is not None and ldy < k):
+        raise ValueError(f"spmm: k = {k} with ldx = {ldx}, ldy = {ldy}: a leading dimension is at least k >= 0")
+    L = _lib.load()
+    fn = L.speck_spmm_f32 if A.dtype == np.float32 else L.speck_spmm_f64
+    buf = None
+    if Y is None:
+        buf = dCSR(np.float64)  # (its data array: A.rows k doubles)
+        buf.alloc(0, 0, max(A.rows * k, 1), allocOffsets=False)
+        y_ptr, ldy = buf._c.data, k
+    info = _lib.CSpmmInfo()
+    _check(fn(config._h if config is not None else None, float(alpha), C.byref(A._c), x_ptr, ldx, k, float(beta), y_ptr, ldy,
+              C.byref(info)), "spmm")
+    out = None
+    if buf is not None:
+        out = np.zeros(max(A.rows * k, 1), dtype=np.float64)
+        _check(L.speck_dcsr_download(C.byref(buf._c), None, None, out.ctypes.data, 8), "spmm: download")
+        out = out[:A.rows * k].reshape(A.rows, k)
+    return out, SpmmInfo(info)

@@ -33,6 +33,7 @@
 #include "add.hpp"
 #include "reduce.hpp"
 #include "scale.hpp"
+#include "spmm.hpp"
 #include "spmv.hpp"
 #include "sort_rows.hpp"
 
@@ -227,6 +228,7 @@ struct speck_config {
     ReduceScratch reduce;  // ... and of speck_reduce_* (reduce.hip)
     ScaleScratch scale;  // ... and of speck_scale_* (scale.hip)
     SpmvScratch spmv;  // ... and of speck_spmv_* (spmv.hip)
+    SpmmScratch spmm;  // ... and of speck_spmm_* (spmm.hip)
     const void* zones_arena = nullptr;
     u64 zones_m = 0, zones_nnz = 0, zones_gap = 0;
     bool gpool_zones_filled = false;
@@ -1920,6 +1922,7 @@ AddScratch* add_scratch(speck_config* c) { return &c->add; }
 ReduceScratch* reduce_scratch(speck_config* c) { return &c->reduce; }
 ScaleScratch* scale_scratch(speck_config* c) { return &c->scale; }
 SpmvScratch* spmv_scratch(speck_config* c) { return &c->spmv; }
+SpmmScratch* spmm_scratch(speck_config* c) { return &c->spmm; }
 }  // namespace speck
 
 extern "C" {
@@ -2039,6 +2042,7 @@ int speck_config_destroy(speck_config* c)
     c->reduce.release();
     c->scale.release();
     c->spmv.release();
+    c->spmm.release();
     if (c->pred.off) (void)guarded_free(c->pred.off);
     if (c->gpred.off) (void)guarded_free(c->gpred.off);
     if (c->d_stats) (void)hipFree(c->d_stats);
@@ -2126,6 +2130,7 @@ int speck_config_set_option(speck_config* c, const char* name, int64_t value)
         c->reduce.release();
         c->scale.release();
         c->spmv.release();
+        c->spmm.release();
     }
     else if (n == "sort_reg_max") c->sort.reg_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_REG_MAX);
     else if (n == "sort_lds_max") c->sort.lds_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_LDS_MAX);

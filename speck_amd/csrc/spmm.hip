@@ -1,0 +1,362 @@
+// spmm.hip -- speck_spmm_*: Y = alpha A X + beta Y on a device CSR, X (cols x k) and Y (rows x k) row-major device arrays of
+// doubles with leading dimensions ldx, ldy.  The walk of spmv.hip with A read ONCE for all k columns: the same entry
+// tiles, the same combination tree (tile_combine.hpp) per column, so column c of Y is bit for bit what speck_spmv_* writes
+// for X(:,c) and Y(:,c).  The reference has no counterpart.
+//
+//   tile_check_kernel     (tile_combine.hpp) a thread per row: the offsets, the empty rows, the rows of every tile's first
+//                         and last entry.  Raises `invalid` in the status block.
+//   spmm_tile_kernel      queued behind it, looks at that verdict first.  A workgroup per ENTRY TILE; a thread takes its 16
+//                         values and its 16 column ids ONCE (16-byte loads under spmv's condition, entry by entry
+//                         elsewhere), checks and clamps the ids ONCE (an id >= cols raises `bad_id` and is NOT followed),
+//                         builds the tile's row-start bitmap ONCE (tile_begin), then walks the k columns in blocks of
+//                         kCB = 4: all 16 kCB gathers X[id ldx + c0 ..) of a block are issued before the first term
+//                         -- one 16-byte load per entry and pair of columns where d_X lies on 16 bytes and ldx is even,
+//                         8-byte loads elsewhere, the same bits -- then per column the terms and the segmented combine
+//                         (combine_terms), with a barrier before the next column takes the LDS.  What k leaves over
+//                         goes in a pair and alone.  A row whole in the tile leaves its sum in sums[r k + c], the rest
+//                         in the record of (tile, column).  The 64 gathered doubles of a block put the kernel at 245
+//                         registers and two waves per SIMD, not the four the LDS allows: measured against one column
+//                         per round at 99 registers and four waves, and 1.4 to 2.9 times faster from k = 8 on where X
+//                         does not stay in the cache.
+//   spmm_finish_kernel    queued last: it sees the verdict of EVERY tile, and only it writes Y.  Three kinds of workgroups:
+//                         a wave per (tile, column) finishes the row that leaves the tile open; a thread per (row, column),
+//                         adjacent lanes on adjacent columns, writes a row that lies in one tile (from `sums`) or holds
+//                         no entry (+0.0); one workgroup counts the split rows.  Every Y(i,c) is written once by one thread,
+//                         which reads it itself where beta != 0.  The padding [k, ldy) of a row is neither read nor written.
+// All index arithmetic i ld + c is 64-bit.  No floating-point atomic; one read-back, at the end.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+
+#include "entry_tiles.hpp"
+#include "launch.hpp"
+#include "row_tiles.hpp"
+#include "side_call.hpp"
+#include "spmm.hpp"
+#include "tile_combine.hpp"
+
+// every product and every sum is rounded on its own: the terms and the sums are those of spmv.hip
+#pragma clang fp contract(off)
+
+using namespace speck;
+
+namespace {
+
+using namespace speck::tile_combine;
+static_assert(kTile == SPECK_SPMV_TILE_ENTRIES, "spmv's tiles");
+using Sum = Op<SPECK_REDUCE_SUM>;
+
+// the columns whose gathers are in flight together (the registers: DESIGN.md 4.17)
+constexpr u32 kCB = SPECK_SPMM_COLUMN_BLOCK;
+static_assert(kCB % 2 == 0, "a 16-byte gather takes two columns");
+
+struct SpmmStatus {
+    u32 invalid;  // the offsets (tile_check_kernel)
+    u32 base;     // row_offsets[0]
+    unsigned long long rows_empty, rows_split;
+    u32 bad_id;   // a column id >= cols (spmm_tile_kernel)
+};
+
+template <typename T>
+struct SpmmArgs {
+    const u32* ro;
+    const u32* col;
+    const T* data;
+    const double* x;
+    double* sums;  // rows k doubles: s(i,c) of the rows that lie whole in one tile
+    u64 nnz, ldx;
+    u32 rows, cols;  // cols >= 1
+    u32 k;           // >= 1
+    u32 max_tiles;   // the records of column c start at recs + c max_tiles
+    u32 aligned;     // data and col start on 16-byte boundaries
+    u32 pairs;       // x starts on a 16-byte boundary and ldx is even: X(j, c) with even c lies on one
+    TileRec* recs;
+    const u32* tile_rows;
+    SpmmStatus* st;
+};
+
+template <typename V, u32 N>
+struct alignas(16) Vec {
+    V v[N];
+};
+
+// ------------------------------------------------------------------------------------------------ tiles
+// The columns [c0, c0 + W) of a tile whose row-start bitmap stands (tile_begin): all 16 W gathers X[id ldx + c0 ..) are
+// issued before the first term, then per column the terms and the segmented combine, with a barrier before the next
+// column takes the LDS.  PAIR: X(j, c0) lies on a 16-byte boundary for every j and W is even -- one 16-byte load per entry
+// and pair of columns.  a: the thread's values, in double; c: its ids, checked, < cols; in_mask: which entries the
+// matrix reaches.
+template <u32 W, bool PAIR, typename T>
+__device__ __forceinline__ void column_block(const SpmmArgs<T>& g, TileLds& s_tile, const TileRows rows, const double (&a)[kPer],
+                                             u32 (&c)[kPer], u32 in_mask, u64 tile0, u64 lo, u64 hi, u32 c0)
+{
+#pragma clang fp contract(off)
+    static_assert(!PAIR || W % 2 == 0, "a 16-byte gather takes two columns");
+    // (the ids pass through an empty asm: the 16 addresses derived from them -- 32 registers -- are then computed per
+    //  block and not kept over the whole column loop)
+#pragma unroll
+    for (u32 e = 0; e < kPer; ++e) asm volatile("" : "+v"(c[e]));
+    double xv[W][kPer];
+#pragma unroll
+    for (u32 e = 0; e < kPer; ++e) {
+        const double* src = g.x + (u64(c[e]) * g.ldx + c0);
+        if (PAIR) {
+#pragma unroll
+            for (u32 j = 0; j < W; j += 2) {
+                const Vec<double, 2> p = reinterpret_cast<const Vec<double, 2>*>(src)[j / 2];
+                xv[j][e] = p.v[0], xv[j + 1][e] = p.v[1];
+            }
+        } else {
+#pragma unroll
+            for (u32 j = 0; j < W; ++j) xv[j][e] = src[j];
+        }
+    }
+    double* const sums = g.sums;
+    const u32 nk = g.k;
+#pragma unroll
+    for (u32 j = 0; j < W; ++j) {
+        double v[kPer];
+#pragma unroll
+        for (u32 e = 0; e < kPer; ++e) v[e] = ((in_mask >> e) & 1u) ? a[e] * xv[j][e] : Sum::ident();
+        const u32 cc = c0 + j;
+        combine_terms<Sum>(s_tile, rows, v, g.ro, g.recs + (u64(cc) * g.max_tiles + blockIdx.x), tile0, lo, hi,
+                           [sums, nk, cc](u32 r, double val) { sums[u64(r) * nk + cc] = val; });
+        // the rows that end in the tile were read from val and incl: the next column overwrites both
+        __syncthreads();
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void spmm_tile_kernel(const SpmmArgs<T> g)
+{
+    SPECK_POISON();
+    __shared__ TileLds s_tile;
+    if (g.st->invalid) return;  // (the verdict of tile_check_kernel: nothing below runs on offsets it refused)
+    const u32 t = threadIdx.x;
+    const u64 base = g.st->base, end = base + g.nnz;
+    const u64 tile0 = (base / kTile + blockIdx.x) * kTile;
+    if (tile0 >= end) return;  // (the grid is sized without knowing the base)
+    const u64 lo = std::max(tile0, base), hi = std::min(tile0 + kTile, end);
+    const bool whole = lo == tile0 && hi == tile0 + kTile;
+
+    // the thread's 16 entries (as doubles: the conversion is exact and happens once) and their column ids, once for all
+    // columns; where the matrix does not reach: id 0, never used
+    double a[kPer];
+    u32 c[kPer];
+    const u64 q0 = tile0 + u64(t) * kPer;
+    if (whole && g.aligned) {
+        constexpr u32 N = 16 / sizeof(T);
+        const Vec<T, N>* src = reinterpret_cast<const Vec<T, N>*>(g.data + q0);
+        const Vec<u32, 4>* cs = reinterpret_cast<const Vec<u32, 4>*>(g.col + q0);
+        Vec<T, N> av[kPer / N];
+        Vec<u32, 4> cv[kPer / 4];
+#pragma unroll
+        for (u32 e = 0; e < kPer / N; ++e) av[e] = src[e];
+#pragma unroll
+        for (u32 e = 0; e < kPer / 4; ++e) cv[e] = cs[e];
+#pragma unroll
+        for (u32 e = 0; e < kPer; ++e) a[e] = av[e / N].v[e % N], c[e] = cv[e / 4].v[e % 4];
+    } else {
+#pragma unroll
+        for (u32 e = 0; e < kPer; ++e) {
+            const u64 p = q0 + e;
+            const bool in = p >= lo && p < hi;
+            a[e] = in ? (double)g.data[p] : 0.0;
+            c[e] = in ? g.col[p] : 0u;
+        }
+    }
+
+    // an id the matrix has no column for is reported and not followed: from here on c holds ids < cols only
+    const u32 last = g.cols - 1u;
+    bool bad = false;
+#pragma unroll
+    for (u32 e = 0; e < kPer; ++e) {
+        bad |= c[e] > last;
+        c[e] = std::min(c[e], last);
+    }
+    if (bad) g.st->bad_id = 1;
+    // (the entries of a tile that is not whole which the matrix does not reach: their term is the identity)
+    u32 in_mask = 0xFFFFu;
+    if (!whole) {
+        in_mask = 0;
+#pragma unroll
+        for (u32 e = 0; e < kPer; ++e) in_mask |= u32(q0 + e >= lo && q0 + e < hi) << e;
+    }
+
+    const TileRows rows = tile_begin(s_tile, g.ro, g.tile_rows, tile0);
+    // the columns in blocks of kCB, then what is left in pairs and alone; one straight path per form of block
+    const u32 nk = g.k;
+    u32 c0 = 0;
+    if (g.pairs) {
+        for (; c0 + kCB <= nk; c0 += kCB) column_block<kCB, true>(g, s_tile, rows, a, c, in_mask, tile0, lo, hi, c0);
+        for (; c0 + 2 <= nk; c0 += 2) column_block<2, true>(g, s_tile, rows, a, c, in_mask, tile0, lo, hi, c0);
+    } else {
+        for (; c0 + kCB <= nk; c0 += kCB) column_block<kCB, false>(g, s_tile, rows, a, c, in_mask, tile0, lo, hi, c0);
+    }
+    for (; c0 < nk; ++c0) column_block<1, false>(g, s_tile, rows, a, c, in_mask, tile0, lo, hi, c0);
+}
+
+// ------------------------------------------------------------------------------------------------ finish, and Y
+__device__ __forceinline__ void write_y(double* __restrict__ y, u64 at, double s, double alpha, double beta)
+{
+#pragma clang fp contract(off)
+    const double as = alpha * s;
+    if (beta == 0.0) y[at] = as;  // (Y is not read: what it held does not survive)
+    else {
+        const double by = beta * y[at];
+        y[at] = as + by;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void spmm_finish_kernel(const u32* __restrict__ ro, u32 rows, u64 nnz, u32 k, u32 max_tiles,
+                                                               u32 chain_blocks, u32 row_blocks, const double* __restrict__ sums,
+                                                               const TileRec* __restrict__ recs, double alpha, double beta,
+                                                               double* __restrict__ y, u64 ldy, SpmmStatus* st)
+{
+    SPECK_POISON();
+    __shared__ double s_w[kWaves];
+    __shared__ u32 s_split[kWaves];
+    if (st->invalid || st->bad_id) return;  // (every tile has run: the verdict is complete, and nothing of Y was written)
+    const u32 t = threadIdx.x, lane = lane_id(), wid = t >> 6;
+    const u64 base = st->base;
+    const u32 ntiles = tiles_touched(base, nnz);
+    if (blockIdx.x < chain_blocks) {
+        // a wave per (tile, column), the tiles of a column side by side
+        const u64 w = u64(blockIdx.x) * kWaves + wid;
+        const u32 c = (u32)(w / max_tiles), i = (u32)(w - u64(c) * max_tiles);
+        u32 row;
+        double val;
+        if (c < k && chain_finish<Sum>(recs + u64(c) * max_tiles, i, ntiles, base / kTile, &row, &val) && lane == 0)
+            write_y(y, u64(row) * ldy + c, val, alpha, beta);
+    } else if (blockIdx.x < chain_blocks + row_blocks) {
+        // a thread per (row, column), adjacent lanes on adjacent columns: (r, c) = divmod(256 block + t, k), the 64-bit
+        // division once per workgroup
+        const u64 first = u64(blockIdx.x - chain_blocks) * kThreads;
+        const u64 r0 = first / k;
+        const u32 in = (u32)(first - r0 * k) + t;  // < k + 256
+        const u64 r64 = r0 + in / k;
+        const u32 c = in % k;
+        if (r64 >= rows) return;
+        const u32 r = (u32)r64;
+        const u32 b = ro[r], e = ro[r + 1];
+        if (b == e) write_y(y, u64(r) * ldy + c, Sum::ident(), alpha, beta);
+        else if (b / kTile == (e - 1u) / kTile) write_y(y, u64(r) * ldy + c, sums[u64(r) * k + c], alpha, beta);  // (else: the chain above)
+    } else {
+        // (which rows are split is a matter of A alone: column 0's records tell)
+        double total;
+        u32 split;
+        if (totals_finish<Sum>(recs, ntiles, s_w, s_split, &total, &split)) st->rows_split = split;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ host
+bool on_16_bytes(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+template <typename T>
+int spmm_run(SpmmScratch* sc, hipStream_t s, double alpha, const speck_dcsr* A, const double* d_X, u64 ldx, u32 k, double beta,
+             double* d_Y, u64 ldy, SpmmStatus* h)
+{
+    const u32 rows = (u32)A->rows;
+    const u32 max_tiles = entry_tiles_at_most(A->nnz, kTile);
+    static_assert(sizeof(SpmmStatus) <= 256, "status block");
+    int rc = sc->fixed.ensure(256);
+    if (rc != SPECK_OK) return rc;
+    const size_t rec_bytes = up256(size_t(std::max(max_tiles, 1u)) * k * sizeof(TileRec));
+    rc = sc->var.ensure(rec_bytes + up256(size_t(std::max(max_tiles, 1u)) * 8));
+    if (rc != SPECK_OK) return rc;
+    rc = sc->sums.ensure(up256(size_t(rows) * k * 8));
+    if (rc != SPECK_OK) return rc;
+    SpmmStatus* st = static_cast<SpmmStatus*>(sc->fixed.p);
+    TileRec* recs = static_cast<TileRec*>(sc->var.p);
+    u32* tile_rows = reinterpret_cast<u32*>(static_cast<unsigned char*>(sc->var.p) + rec_bytes);
+    double* sums = static_cast<double*>(sc->sums.p);
+
+    HIP_TRY(hipMemsetAsync(st, 0, sizeof(SpmmStatus), s));
+    SPECK_LAUNCH(tile_check_kernel<SpmmStatus>, dim3((rows + kThreads - 1) / kThreads), dim3(kThreads), 0, s, A->row_offsets, rows,
+                 A->nnz, max_tiles, tile_rows, st);
+    if (max_tiles) {
+        const SpmmArgs<T> g{A->row_offsets, A->col_ids, static_cast<const T*>(A->data), d_X, sums, A->nnz, ldx, rows, (u32)A->cols, k,
+                            max_tiles, on_16_bytes(A->data) && on_16_bytes(A->col_ids) ? 1u : 0u,
+                            on_16_bytes(d_X) && ldx % 2 == 0 ? 1u : 0u, recs, tile_rows, st};
+        SPECK_LAUNCH(spmm_tile_kernel<T>, dim3(max_tiles), dim3(kThreads), 0, s, g);
+    }
+    // (rows <= 2^27, k <= 2^10, tiles <= 2^20 + 1: the grid stays below 2^30)
+    const u32 chain_blocks = (u32)((u64(max_tiles) * k + kWaves - 1) / kWaves);
+    const u32 row_blocks = (u32)((u64(rows) * k + kThreads - 1) / kThreads);
+    SPECK_LAUNCH(spmm_finish_kernel, dim3(chain_blocks + row_blocks + 1u), dim3(kThreads), 0, s, A->row_offsets, rows, A->nnz, k,
+                 max_tiles, chain_blocks, row_blocks, sums, recs, alpha, beta, d_Y, ldy, st);
+    // the ONE read-back of the call: the two verdicts, the counters
+    rc = read_status(s, st, h);
+    if (rc != SPECK_OK) return rc;
+    return (h->invalid || h->bad_id) ? SPECK_ERR_INVALID : SPECK_OK;
+}
+
+const char* const kGuardNames[3] = {"spmm status", "spmm tile records and rows", "spmm row sums"};
+
+bool is_one_of(const void* v, const speck_dcsr* X) { return v == X->data || v == X->col_ids || v == X->row_offsets; }
+
+template <typename T>
+int spmm_impl(speck_config* cfg, double alpha, const speck_dcsr* A, const double* d_X, u64 ldx, u32 k, double beta, double* d_Y,
+              u64 ldy, speck_spmm_info* info)
+{
+    if (!A || alpha != alpha || beta != beta) return SPECK_ERR_INVALID;
+    if (A->rows > (1ull << 27) || A->cols > (1ull << 27) || k > SPECK_SPMM_MAX_RHS) return SPECK_ERR_DIM_LIMIT;
+    if (ldx > (1ull << 32) || ldy > (1ull << 32)) return SPECK_ERR_DIM_LIMIT;  // (the spans below stay inside 64 bits)
+    if (A->nnz >= (1ull << 32)) return SPECK_ERR_NNZ_OVERFLOW;
+    if (ldx < k || ldy < k) return SPECK_ERR_INVALID;
+    if (A->rows && (!A->row_offsets || (k && !d_Y))) return SPECK_ERR_INVALID;
+    if (A->nnz && (!A->data || !A->col_ids || (k && !d_X))) return SPECK_ERR_INVALID;
+    // (entries without a row to hold them; entries without a column to point at: every id is >= cols)
+    if (A->nnz && (A->rows == 0 || A->cols == 0)) return SPECK_ERR_INVALID;
+    if ((d_X && is_one_of(d_X, A)) || (d_Y && is_one_of(d_Y, A))) return SPECK_ERR_INVALID;
+    if (d_X && d_Y && A->rows && A->cols && k) {
+        // what the call may touch: [d_X, d_X + (cols - 1) ldx + k) and [d_Y, d_Y + (rows - 1) ldy + k), padding inside included
+        const u64 x0 = reinterpret_cast<uintptr_t>(d_X), y0 = reinterpret_cast<uintptr_t>(d_Y);
+        const u64 xs = 8 * ((A->cols - 1) * ldx + k), ys = 8 * ((A->rows - 1) * ldy + k);
+        if (x0 < y0 + ys && y0 < x0 + xs) return SPECK_ERR_INVALID;
+    }
+    if (info) *info = speck_spmm_info{};
+    if (!cfg && !device_present()) return SPECK_ERR_NO_DEVICE;
+    if (A->rows == 0 || k == 0) return SPECK_OK;  // no row or no column: nothing to write
+    SpmmScratch own;
+    SpmmScratch* sc = cfg ? spmm_scratch(cfg) : &own;
+    const hipStream_t s = cfg ? call_stream(cfg) : nullptr;
+    (void)take_launch_error();
+    SpmmStatus h{};
+    int rc = spmm_run<T>(sc, s, alpha, A, d_X, ldx, k, beta, d_Y, ldy, &h);
+    if (rc != SPECK_OK) (void)hipStreamSynchronize(s);
+    const void* whole[] = {sc->fixed.p, sc->var.p, sc->sums.p};
+    rc = guard_check_buffers(whole, kGuardNames, 3, s, " by the product with several right-hand sides", rc);
+    if (!cfg) {
+        (void)hipStreamSynchronize(s);
+        own.release();
+    }
+    if (rc != SPECK_OK) return rc;
+    if (info) {
+        info->rows_empty = h.rows_empty;
+        info->rows_split = h.rows_split;
+        info->tiles = A->nnz ? (u64(h.base) + A->nnz - 1) / kTile - u64(h.base) / kTile + 1 : 0;
+        info->entries = A->nnz;
+        info->terms = A->nnz * k;
+    }
+    return SPECK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int speck_spmm_f64(speck_config* cfg, double alpha, const speck_dcsr* A, const double* d_X, uint64_t ldx, uint32_t k, double beta,
+                   double* d_Y, uint64_t ldy, speck_spmm_info* info)
+{
+    return spmm_impl<double>(cfg, alpha, A, d_X, ldx, k, beta, d_Y, ldy, info);
+}
+
+int speck_spmm_f32(speck_config* cfg, double alpha, const speck_dcsr* A, const double* d_X, uint64_t ldx, uint32_t k, double beta,
+                   double* d_Y, uint64_t ldy, speck_spmm_info* info)
+{
+    return spmm_impl<float>(cfg, alpha, A, d_X, ldx, k, beta, d_Y, ldy, info);
+}
+
+}  // extern "C"

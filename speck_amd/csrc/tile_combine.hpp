@@ -1,4 +1,4 @@
-// tile_combine.hpp -- the segmented combine over ENTRY TILES that reduce.hip and spmv.hip share: a workgroup of 256 threads
+// tile_combine.hpp -- the segmented combine over ENTRY TILES that reduce.hip, spmv.hip and spmm.hip share: a workgroup of 256 threads
 // holds the 4096 terms of a tile, 16 consecutive ones per thread, and combines them per row -- serially in the thread,
 // across the lanes with DPP shifts, across the four waves through LDS; a row that ends in the tile goes to the caller's
 // sink, a row open at the tile's start or end leaves its partial in the tile's record (TileRec), and chain_finish puts
@@ -128,19 +128,18 @@ struct TileLds {
 // where the running value at entry i of the tile rests in LDS (a thread's 16 entries 17 doubles apart: two lanes per bank)
 __device__ __forceinline__ u32 val_slot(u32 i) { return i + (i >> 4); }
 
-// The workgroup of tile `i` = blockIdx.x, the absolute entries [tile0, tile0 + kTile) of which [lo, hi) belong to the
-// matrix: v holds the terms of the thread's 16 entries, the identity where the matrix does not reach.  row_done(r, val)
-// receives every row that lies whole in the tile (rows without entries: the caller's own pass); rec receives the rest.
-// All 256 threads call it; the offsets were checked.
-template <typename O, typename RowDone>
-__device__ __forceinline__ void combine_tile(TileLds& s, const double (&v)[kPer], const u32* __restrict__ ro,
-                                             const u32* __restrict__ tile_rows, TileRec* rec, u64 tile0, u64 lo, u64 hi,
-                                             RowDone&& row_done)
-{
-#pragma clang fp contract(off)
-    const u32 t = threadIdx.x, lane = lane_id(), wid = t >> 6;
+// The rows of the tile's first and last entry: what a tile's workgroup works out ONCE, whatever number of term vectors it
+// combines afterwards (tile_begin)
+struct TileRows {
+    u32 r_lo, r_hi;
+};
 
-    // the rows of the tile's first and last entry (tile_check_kernel), and the row starts inside the tile as a bitmap
+// Once per tile: the rows of the tile's first and last entry (tile_check_kernel) and the row starts inside the tile
+// [tile0, tile0 + kTile) as a bitmap in s.bits, which every combine_terms that follows reads.  All 256 threads call it;
+// it ends behind a barrier.
+__device__ __forceinline__ TileRows tile_begin(TileLds& s, const u32* __restrict__ ro, const u32* __restrict__ tile_rows, u64 tile0)
+{
+    const u32 t = threadIdx.x;
     if (t < kTile / 32) s.bits[t] = 0;
     const u32 r_lo = tile_rows[2 * blockIdx.x], r_hi = tile_rows[2 * blockIdx.x + 1];
     __syncthreads();
@@ -149,6 +148,21 @@ __device__ __forceinline__ void combine_tile(TileLds& s, const double (&v)[kPer]
         if (o >= tile0 && o < tile0 + kTile) atomicOr(&s.bits[(u32)(o - tile0) >> 5], 1u << ((u32)(o - tile0) & 31u));
     }
     __syncthreads();
+    return TileRows{r_lo, r_hi};
+}
+
+// The combine of ONE vector of terms of the tile tile_begin prepared, the absolute entries [tile0, tile0 + kTile) of which
+// [lo, hi) belong to the matrix: v holds the terms of the thread's 16 entries, the identity where the matrix does not
+// reach.  row_done(r, val) receives every row that lies whole in the tile (rows without entries: the caller's own pass);
+// rec receives the rest.  All 256 threads call it; the offsets were checked.  It leaves s.val and s.incl in use by the
+// threads that are still collecting their rows: a caller that combines another vector puts a barrier in between.
+template <typename O, typename RowDone>
+__device__ __forceinline__ void combine_terms(TileLds& s, const TileRows rows, const double (&v)[kPer], const u32* __restrict__ ro,
+                                              TileRec* rec, u64 tile0, u64 lo, u64 hi, RowDone&& row_done)
+{
+#pragma clang fp contract(off)
+    const u32 t = threadIdx.x, lane = lane_id(), wid = t >> 6;
+    const u32 r_lo = rows.r_lo, r_hi = rows.r_hi;
 
     // in the thread: the running value restarts at every row start; what it was in front of one, and at the thread's
     // last entry, goes to LDS
@@ -200,6 +214,16 @@ __device__ __forceinline__ void combine_tile(TileLds& s, const double (&v)[kPer]
         for (u32 u = 1; u < kWaves; ++u) total = O::comb(total, s.wtot[u]);
         rec->total = total;
     }
+}
+
+// The workgroup of tile `i` = blockIdx.x with one vector of terms: the two above in sequence.
+template <typename O, typename RowDone>
+__device__ __forceinline__ void combine_tile(TileLds& s, const double (&v)[kPer], const u32* __restrict__ ro,
+                                             const u32* __restrict__ tile_rows, TileRec* rec, u64 tile0, u64 lo, u64 hi,
+                                             RowDone&& row_done)
+{
+    const TileRows rows = tile_begin(s, ro, tile_rows, tile0);
+    combine_terms<O>(s, rows, v, ro, rec, tile0, lo, hi, row_done);
 }
 
 // ------------------------------------------------------------------------------------------------ finish
