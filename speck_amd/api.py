@@ -430,18 +430,23 @@ COMPARE_MAX_WAVES = 32768
 COPY_MAX_THREADS = 2097152
 
 
-class SortInfo:
-    """speck_sort_info: what a sort_rows call found and did."""
+class _Info:
+    """What a call reports: the fields of its C struct (include/speck_c_api.h, _lib.C*Info) as int, an array field as a
+    tuple of ints.  A subclass is a name, a docstring and `_fields`."""
+    _fields = ()
 
     def __init__(self, c):
-        self.rows_in_order = int(c.rows_in_order)
-        self.rows_sorted = tuple(int(x) for x in c.rows_sorted)  # register / LDS / global-memory class
-        self.duplicates = int(c.duplicates)
-        self.nnz_out = int(c.nnz_out)
+        for f in self._fields:
+            v = getattr(c, f)
+            setattr(self, f, int(v) if isinstance(v, int) else tuple(int(x) for x in v))
 
     def __repr__(self):
-        return (f"SortInfo(rows_in_order={self.rows_in_order}, rows_sorted={self.rows_sorted}, "
-                f"duplicates={self.duplicates}, nnz_out={self.nnz_out})")
+        return f"{type(self).__name__}({', '.join(f'{f}={getattr(self, f)}' for f in self._fields)})"
+
+
+class SortInfo(_Info):
+    """speck_sort_info: what a sort_rows call found and did."""
+    _fields = ("rows_in_order", "rows_sorted", "duplicates", "nnz_out")  # rows_sorted: register / LDS / global-memory class
 
 
 def sort_rows(M, config, sum_duplicates=False):
@@ -463,19 +468,9 @@ MASK_GROUP_MAX = 256
 MASK_LDS_MAX = 4096
 
 
-class MaskedInfo:
+class MaskedInfo(_Info):
     """speck_masked_info: what a multiply_masked call found and did."""
-
-    def __init__(self, c):
-        self.rows_idle = int(c.rows_idle)
-        self.rows_class = tuple(int(x) for x in c.rows_class)  # group / LDS / global-memory class
-        self.products = int(c.products)
-        self.hits = int(c.hits)
-        self.nnz_out = int(c.nnz_out)
-
-    def __repr__(self):
-        return (f"MaskedInfo(rows_idle={self.rows_idle}, rows_class={self.rows_class}, products={self.products}, "
-                f"hits={self.hits}, nnz_out={self.nnz_out})")
+    _fields = ("rows_idle", "rows_class", "products", "hits", "nnz_out")  # rows_class: group / LDS / global-memory class
 
 
 def multiply_masked(A, B, M, config, matOut=None, full_pattern=False):
@@ -507,18 +502,9 @@ SELECT_LONG_ROW_AVG = 32
 _INT64_MIN, _INT64_MAX = -(1 << 63), (1 << 63) - 1
 
 
-class SelectInfo:
+class SelectInfo(_Info):
     """speck_select_info: what a select call kept and dropped."""
-
-    def __init__(self, c):
-        self.kept = int(c.kept)
-        self.dropped = int(c.dropped)
-        self.rows_unchanged = int(c.rows_unchanged)
-        self.nnz_out = int(c.nnz_out)
-
-    def __repr__(self):
-        return (f"SelectInfo(kept={self.kept}, dropped={self.dropped}, rows_unchanged={self.rows_unchanged}, "
-                f"nnz_out={self.nnz_out})")
+    _fields = ("kept", "dropped", "rows_unchanged", "nnz_out")
 
 
 def select(A, config, band=None, abs_gt=None, pattern=None, negate=(), row_base=0, matOut=None):
@@ -582,17 +568,9 @@ ADD_LONG_ROW_AVG = 32
 ADD_TILE_ENTRIES = 4096
 
 
-class AddInfo:
+class AddInfo(_Info):
     """speck_add_info: where the entries of the sum come from."""
-
-    def __init__(self, c):
-        self.only_a = int(c.only_a)
-        self.only_b = int(c.only_b)
-        self.both = int(c.both)
-        self.nnz_out = int(c.nnz_out)
-
-    def __repr__(self):
-        return f"AddInfo(only_a={self.only_a}, only_b={self.only_b}, both={self.both}, nnz_out={self.nnz_out})"
+    _fields = ("only_a", "only_b", "both", "nnz_out")
 
 
 def add(A, B, config, alpha=1.0, beta=1.0, matOut=None):
@@ -631,18 +609,23 @@ REDUCE_THREAD_ENTRIES = 16
 REDUCE_WAVE_ENTRIES = 1024
 
 
-class ReduceInfo:
+class ReduceInfo(_Info):
     """speck_reduce_info: what the reduction walked."""
+    _fields = ("rows_empty", "rows_split", "tiles", "entries")
 
-    def __init__(self, c):
-        self.rows_empty = int(c.rows_empty)
-        self.rows_split = int(c.rows_split)
-        self.tiles = int(c.tiles)
-        self.entries = int(c.entries)
 
-    def __repr__(self):
-        return (f"ReduceInfo(rows_empty={self.rows_empty}, rows_split={self.rows_split}, tiles={self.tiles}, "
-                f"entries={self.entries})")
+def _dev_f64(n):
+    """n doubles (one at least) from the library's allocator: the data array of a dCSR without rows"""
+    d = dCSR(np.float64)
+    d.alloc(0, 0, max(int(n), 1), allocOffsets=False)
+    return d
+
+
+def _download_f64(buf, n, who):
+    """the first n doubles of a _dev_f64 buffer as a numpy array"""
+    out = np.zeros(max(int(n), 1), dtype=np.float64)
+    _check(_lib.load().speck_dcsr_download(C.byref(buf._c), None, None, out.ctypes.data, 8), f"{who}: download")
+    return out[:n]
 
 
 def reduce(A, config, op="sum", rows=True, total=True, out_ptr=None):
@@ -663,18 +646,13 @@ def reduce(A, config, op="sum", rows=True, total=True, out_ptr=None):
     fn = L.speck_reduce_f32 if A.dtype == np.float32 else L.speck_reduce_f64
     buf = None
     if out_ptr is None and rows:
-        buf = dCSR(np.float64)  # (its data array: A.rows doubles)
-        buf.alloc(0, 0, max(A.rows, 1), allocOffsets=False)
+        buf = _dev_f64(A.rows)
         out_ptr = buf._c.data
     t = C.c_double()
     info = _lib.CReduceInfo()
     _check(fn(config._h if config is not None else None, C.byref(A._c), int(op), out_ptr if rows else None,
               C.byref(t) if total else None, C.byref(info)), "reduce")
-    row_values = None
-    if buf is not None:
-        row_values = np.zeros(max(A.rows, 1), dtype=np.float64)
-        _check(L.speck_dcsr_download(C.byref(buf._c), None, None, row_values.ctypes.data, 8), "reduce: download")
-        row_values = row_values[:A.rows]
+    row_values = _download_f64(buf, A.rows, "reduce") if buf is not None else None
     return row_values, (float(t.value) if total else None), ReduceInfo(info)
 
 
@@ -685,16 +663,9 @@ SCALE_NONE, SCALE_MUL, SCALE_DIV = range(3)
 SCALE_TILE_ENTRIES = 4096
 
 
-class ScaleInfo:
+class ScaleInfo(_Info):
     """speck_scale_info: what the scaling wrote."""
-
-    def __init__(self, c):
-        self.entries = int(c.entries)
-        self.nonfinite = int(c.nonfinite)
-        self.tiles = int(c.tiles)
-
-    def __repr__(self):
-        return f"ScaleInfo(entries={self.entries}, nonfinite={self.nonfinite}, tiles={self.tiles})"
+    _fields = ("entries", "nonfinite", "tiles")
 
 
 def _device_vector(v, n, what, who="scale"):
@@ -766,8 +737,7 @@ def normalize_rows(A, config, norm="abs_sum", inplace=False):
     entries are not hidden and show up in info.nonfinite.  Rows without entries stay empty.  Returns (matrix, ScaleInfo)."""
     if norm not in _ROW_NORMS:
         raise ValueError(f"normalize_rows: unknown norm {norm!r} (one of {', '.join(_ROW_NORMS)})")
-    buf = dCSR(np.float64)  # (its data array: A.rows doubles of the library's allocator)
-    buf.alloc(0, 0, max(A.rows, 1), allocOffsets=False)
+    buf = _dev_f64(A.rows)
     reduce(A, config, norm, total=False, out_ptr=buf._c.data)
     return scale(A, config, row=buf._c.data, row_div=True, inplace=inplace)
 
@@ -782,18 +752,9 @@ def pattern_ones(A, config):
 SPMV_TILE_ENTRIES = 4096
 
 
-class SpmvInfo:
+class SpmvInfo(_Info):
     """speck_spmv_info: what the matrix-vector product walked."""
-
-    def __init__(self, c):
-        self.rows_empty = int(c.rows_empty)
-        self.rows_split = int(c.rows_split)
-        self.tiles = int(c.tiles)
-        self.entries = int(c.entries)
-
-    def __repr__(self):
-        return (f"SpmvInfo(rows_empty={self.rows_empty}, rows_split={self.rows_split}, tiles={self.tiles}, "
-                f"entries={self.entries})")
+    _fields = ("rows_empty", "rows_split", "tiles", "entries")
 
 
 def spmv(A, x, config, alpha=1.0, beta=0.0, y=None):
@@ -814,18 +775,12 @@ def spmv(A, x, config, alpha=1.0, beta=0.0, y=None):
     fn = L.speck_spmv_f32 if A.dtype == np.float32 else L.speck_spmv_f64
     buf = None
     if y is None:
-        buf = dCSR(np.float64)  # (its data array: A.rows doubles)
-        buf.alloc(0, 0, max(A.rows, 1), allocOffsets=False)
+        buf = _dev_f64(A.rows)
         y_ptr = buf._c.data
     info = _lib.CSpmvInfo()
     _check(fn(config._h if config is not None else None, float(alpha), C.byref(A._c), x_ptr, float(beta), y_ptr,
               C.byref(info)), "spmv")
-    out = None
-    if buf is not None:
-        out = np.zeros(max(A.rows, 1), dtype=np.float64)
-        _check(L.speck_dcsr_download(C.byref(buf._c), None, None, out.ctypes.data, 8), "spmv: download")
-        out = out[:A.rows]
-    return out, SpmvInfo(info)
+    return (_download_f64(buf, A.rows, "spmv") if buf is not None else None), SpmvInfo(info)
 
 
 # include/speck_c_api.h: the most right-hand sides one call takes
@@ -834,19 +789,9 @@ SPMM_MAX_RHS = 1024
 SPMM_COLUMN_BLOCK = 4
 
 
-class SpmmInfo:
+class SpmmInfo(_Info):
     """speck_spmm_info: what the product with several right-hand sides walked (A's counts, and terms = entries * k)."""
-
-    def __init__(self, c):
-        self.rows_empty = int(c.rows_empty)
-        self.rows_split = int(c.rows_split)
-        self.tiles = int(c.tiles)
-        self.entries = int(c.entries)
-        self.terms = int(c.terms)
-
-    def __repr__(self):
-        return (f"SpmmInfo(rows_empty={self.rows_empty}, rows_split={self.rows_split}, tiles={self.tiles}, "
-                f"entries={self.entries}, terms={self.terms})")
+    _fields = ("rows_empty", "rows_split", "tiles", "entries", "terms")
 
 
 def _device_block(v, n, k, ld, what):
@@ -898,15 +843,9 @@ def spmm(A, X, config, alpha=1.0, beta=0.0, Y=None, k=None, ldx=None, ldy=None):
     fn = L.speck_spmm_f32 if A.dtype == np.float32 else L.speck_spmm_f64
     buf = None
     if Y is None:
-        buf = dCSR(np.float64)  # (its data array: A.rows k doubles)
-        buf.alloc(0, 0, max(A.rows * k, 1), allocOffsets=False)
+        buf = _dev_f64(A.rows * k)
         y_ptr, ldy = buf._c.data, k
     info = _lib.CSpmmInfo()
     _check(fn(config._h if config is not None else None, float(alpha), C.byref(A._c), x_ptr, ldx, k, float(beta), y_ptr, ldy,
               C.byref(info)), "spmm")
-    out = None
-    if buf is not None:
-        out = np.zeros(max(A.rows * k, 1), dtype=np.float64)
-        _check(L.speck_dcsr_download(C.byref(buf._c), None, None, out.ctypes.data, 8), "spmm: download")
-        out = out[:A.rows * k].reshape(A.rows, k)
-    return out, SpmmInfo(info)
+    return (_download_f64(buf, A.rows * k, "spmm").reshape(A.rows, k) if buf is not None else None), SpmmInfo(info)

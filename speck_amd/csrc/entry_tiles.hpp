@@ -1,7 +1,8 @@
-// entry_tiles.hpp -- what the operations that walk a matrix in ENTRY TILES (reduce.hip, scale.hip, spmv.hip) share: the check of one
-// row's offsets in their first pass, which also tells every tile the rows of its first and of its last entry.  A tile is
-// the entries [kTile t, kTile (t + 1)) of the buffers, counted from the buffers' start and clipped to the matrix; the
-// i-th tile the matrix touches is tile row_offsets[0] / kTile + i.
+// entry_tiles.hpp -- what the operations that walk a matrix in ENTRY TILES (reduce.hip, scale.hip, spmv.hip, spmm.hip)
+// share: the check of one row's offsets in their first pass, which also tells every tile the rows of its first and of its
+// last entry.  A tile is the entries [kTile t, kTile (t + 1)) of the buffers, counted from the buffers' start and clipped
+// to the matrix; the i-th tile the matrix touches is tile row_offsets[0] / kTile + i.  (What reduce, spmv and spmm do with
+// a tile is tile_combine.hpp's; scale.hip has its own pass.)
 #pragma once
 #include <algorithm>
 

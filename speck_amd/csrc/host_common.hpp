@@ -1,12 +1,14 @@
 // host_common.hpp -- what the host side of every entry point shares: the error macro, size and grid arithmetic, the
-// grow-only device buffer the side operations keep their temporaries in, and the two questions an entry point asks of
-// its config ("is there a device at all?" when none was given, "which stream?" when one was).  Light on purpose:
-// dcsr.hip and extras.hip include it without the launch machinery (launch.hpp, chain.hpp).
+// grow-only device buffer the side operations keep their temporaries in, two questions about an address a caller
+// passed (on_16_bytes, is_one_of), and the two questions an entry point asks of its config ("is there a device at all?"
+// when none was given, "which stream?" when one was).  Light on purpose: dcsr.hip and extras.hip include it without the
+// launch machinery (launch.hpp, chain.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstddef>
+#include <cstdint>
 #include <cstdio>
 
 #include "../../include/speck_c_api.h"
@@ -53,6 +55,12 @@ struct DeviceBuffer {
         p = nullptr, bytes = 0;
     }
 };
+
+// whether a 16-byte load may start at p
+inline bool on_16_bytes(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// whether v is one of X's three arrays (a vector the caller passes may not be)
+inline bool is_one_of(const void* v, const speck_dcsr* X) { return v == X->data || v == X->col_ids || v == X->row_offsets; }
 
 // an entry point called without a config: a config exists only where a device does, so nobody has asked yet
 inline bool device_present()

@@ -31,11 +31,9 @@
 #include "masked.hpp"
 #include "select.hpp"
 #include "add.hpp"
-#include "reduce.hpp"
 #include "scale.hpp"
-#include "spmm.hpp"
-#include "spmv.hpp"
 #include "sort_rows.hpp"
+#include "tile_scratch.hpp"
 
 using namespace speck;
 
@@ -225,10 +223,10 @@ struct speck_config {
     MaskedScratch masked;  // ... and of speck_multiply_masked_* (masked.hip)
     SelectScratch select;  // ... and of speck_select_* (select.hip)
     AddScratch add;  // ... and of speck_add_* (add.hip)
-    ReduceScratch reduce;  // ... and of speck_reduce_* (reduce.hip)
+    TileScratch reduce;  // ... and of speck_reduce_* (reduce.hip)
     ScaleScratch scale;  // ... and of speck_scale_* (scale.hip)
-    SpmvScratch spmv;  // ... and of speck_spmv_* (spmv.hip)
-    SpmmScratch spmm;  // ... and of speck_spmm_* (spmm.hip)
+    TileScratch spmv;  // ... and of speck_spmv_* (spmv.hip)
+    TileScratch spmm;  // ... and of speck_spmm_* (spmm.hip): its own, a spmv after a wide spmm keeps its small buffers
     const void* zones_arena = nullptr;
     u64 zones_m = 0, zones_nnz = 0, zones_gap = 0;
     bool gpool_zones_filled = false;
@@ -1919,10 +1917,10 @@ MaskedScratch* masked_scratch(speck_config* c) { return &c->masked; }
 
 SelectScratch* select_scratch(speck_config* c) { return &c->select; }
 AddScratch* add_scratch(speck_config* c) { return &c->add; }
-ReduceScratch* reduce_scratch(speck_config* c) { return &c->reduce; }
+TileScratch* reduce_scratch(speck_config* c) { return &c->reduce; }
 ScaleScratch* scale_scratch(speck_config* c) { return &c->scale; }
-SpmvScratch* spmv_scratch(speck_config* c) { return &c->spmv; }
-SpmmScratch* spmm_scratch(speck_config* c) { return &c->spmm; }
+TileScratch* spmv_scratch(speck_config* c) { return &c->spmv; }
+TileScratch* spmm_scratch(speck_config* c) { return &c->spmm; }
 }  // namespace speck
 
 extern "C" {

@@ -23,20 +23,16 @@
 // rows of the whole matrix, and a call gives the same bits every time.  No floating-point atomic.  A NaN is carried by
 // the values themselves: the sums propagate it, and the extrema combine with "a > b or a is NaN ? a : b".
 // The combine itself -- the walk in the thread, the DPP scan, the carry across the waves, the tile record and the chain
-// finish -- lives in tile_combine.hpp: spmv.hip runs the same tree over the terms a x[j].
-// The host side stands on host_common.hpp and side_call.hpp (the status read-back); the frame of the call is its own, as
-// the row sort's is: no C is handed over.
+// finish -- lives in tile_combine.hpp, with a tile kernel's opening and the load of a thread's entries: spmv.hip and
+// spmm.hip run the same tree over the terms a x[j].  The host side stands on tile_call.hpp, which the three share: the
+// scratch, the check's launch, the frame of a call that hands over no C.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
 
-#include "entry_tiles.hpp"
 #include "launch.hpp"
-#include "reduce.hpp"
-#include "row_tiles.hpp"
-#include "side_call.hpp"
-#include "tile_combine.hpp"
+#include "tile_call.hpp"
 
 // every square and every sum is rounded on its own: all code paths add the same terms (add.hip does the same per function)
 #pragma clang fp contract(off)
@@ -69,11 +65,6 @@ struct ReduceArgs {
     ReduceStatus* st;
 };
 
-template <typename T>
-struct alignas(16) Vec16 {
-    T v[16 / sizeof(T)];
-};
-
 template <typename T, int OP>
 __global__ __launch_bounds__(kThreads) void reduce_tile_kernel(const ReduceArgs<T> g)
 {
@@ -81,34 +72,24 @@ __global__ __launch_bounds__(kThreads) void reduce_tile_kernel(const ReduceArgs<
     using O = Op<OP>;
     __shared__ TileLds s_tile;
     if (g.st->invalid) return;  // (the verdict of tile_check_kernel: nothing below runs on offsets it refused)
-    const u32 t = threadIdx.x;
-    const u64 base = g.st->base, end = base + g.nnz;
-    const u64 tile0 = (base / kTile + blockIdx.x) * kTile;
-    if (tile0 >= end) return;  // (the grid is sized without knowing the base)
-    const u64 lo = std::max(tile0, base), hi = std::min(tile0 + kTile, end);
+    TileFrame f;
+    if (!tile_frame(g.st->base, g.nnz, blockIdx.x, &f)) return;
 
-    // the thread's 16 entries: their terms, the identity where the matrix does not reach
+    // the thread's 16 entries: their terms, the identity where the matrix does not reach (a whole tile asks nothing per entry)
+    T a[kPer];
+    load_entries<false>(f, f.whole, g.data, nullptr, a, nullptr);
     double v[kPer];
-    const u64 q0 = tile0 + u64(t) * kPer;
-    if (lo == tile0 && hi == tile0 + kTile) {
-        constexpr u32 N = 16 / sizeof(T);
-        const Vec16<T>* src = reinterpret_cast<const Vec16<T>*>(g.data + q0);
-        Vec16<T> x[kPer / N];
 #pragma unroll
-        for (u32 k = 0; k < kPer / N; ++k) x[k] = src[k];
+    for (u32 k = 0; k < kPer; ++k) v[k] = O::term((double)a[k]);
+    if (!f.whole) {
 #pragma unroll
-        for (u32 k = 0; k < kPer; ++k) v[k] = O::term((double)x[k / N].v[k % N]);
-    } else {
-#pragma unroll
-        for (u32 k = 0; k < kPer; ++k) {
-            const u64 p = q0 + k;
-            v[k] = (p >= lo && p < hi) ? O::term((double)g.data[p]) : O::ident();
-        }
+        for (u32 k = 0; k < kPer; ++k)
+            if (!entry_in(f, k)) v[k] = O::ident();
     }
 
     // (rows without entries: reduce_finish_kernel)
     double* const row_out = g.row_out;
-    combine_tile<O>(s_tile, v, g.ro, g.tile_rows, g.recs + blockIdx.x, tile0, lo, hi, [row_out](u32 r, double val) {
+    combine_tile<O>(s_tile, v, g.ro, g.tile_rows, g.recs + blockIdx.x, f.tile0, f.lo, f.hi, [row_out](u32 r, double val) {
         if (row_out) row_out[r] = val;
     });
 }
@@ -146,17 +127,16 @@ __global__ __launch_bounds__(kThreads) void reduce_finish_kernel(const u32* __re
 
 // ------------------------------------------------------------------------------------------------ host
 template <typename T, int OP>
-void reduce_launch(hipStream_t s, const speck_dcsr* A, double* d_row_out, u32 max_tiles, TileRec* recs, const u32* tile_rows,
-                   ReduceStatus* st)
+void reduce_launch(hipStream_t s, const speck_dcsr* A, double* d_row_out, const TileWork<ReduceStatus>& w)
 {
     const u32 rows = (u32)A->rows;
-    if (max_tiles) {
-        const ReduceArgs<T> g{A->row_offsets, static_cast<const T*>(A->data), rows, A->nnz, d_row_out, recs, tile_rows, st};
-        SPECK_LAUNCH((reduce_tile_kernel<T, OP>), dim3(max_tiles), dim3(kThreads), 0, s, g);
+    if (w.max_tiles) {
+        const ReduceArgs<T> g{A->row_offsets, static_cast<const T*>(A->data), rows, A->nnz, d_row_out, w.recs, w.tile_rows, w.st};
+        SPECK_LAUNCH((reduce_tile_kernel<T, OP>), dim3(w.max_tiles), dim3(kThreads), 0, s, g);
     }
-    const u32 chain_blocks = (max_tiles + kWaves - 1) / kWaves, row_blocks = (rows + kThreads - 1) / kThreads;
+    const u32 chain_blocks = (w.max_tiles + kWaves - 1) / kWaves, row_blocks = (rows + kThreads - 1) / kThreads;
     SPECK_LAUNCH(reduce_finish_kernel<OP>, dim3(chain_blocks + row_blocks + 1u), dim3(kThreads), 0, s, A->row_offsets, rows, A->nnz,
-                 chain_blocks, row_blocks, d_row_out, recs, st);
+                 chain_blocks, row_blocks, d_row_out, w.recs, w.st);
 }
 
 double identity_of(int op)
@@ -165,33 +145,21 @@ double identity_of(int op)
 }
 
 template <typename T>
-int reduce_run(ReduceScratch* sc, hipStream_t s, const speck_dcsr* A, int op, double* d_row_out, ReduceStatus* h)
+int reduce_run(TileScratch* sc, hipStream_t s, const speck_dcsr* A, int op, double* d_row_out, ReduceStatus* h)
 {
-    const u32 max_tiles = entry_tiles_at_most(A->nnz, kTile);
-    int rc = sc->fixed.ensure(256);
+    TileWork<ReduceStatus> w;
+    int rc = carve_and_check(sc, s, A, 1, 0, &w);
     if (rc != SPECK_OK) return rc;
-    const size_t rec_bytes = up256(size_t(std::max(max_tiles, 1u)) * sizeof(TileRec));
-    rc = sc->var.ensure(rec_bytes + up256(size_t(std::max(max_tiles, 1u)) * 8));
-    if (rc != SPECK_OK) return rc;
-    static_assert(sizeof(ReduceStatus) <= 256, "status block");
-    ReduceStatus* st = static_cast<ReduceStatus*>(sc->fixed.p);
-    TileRec* recs = static_cast<TileRec*>(sc->var.p);
-    u32* tile_rows = reinterpret_cast<u32*>(static_cast<unsigned char*>(sc->var.p) + rec_bytes);
-
-    HIP_TRY(hipMemsetAsync(st, 0, sizeof(ReduceStatus), s));
-    const u32 rows = (u32)A->rows;
-    SPECK_LAUNCH(tile_check_kernel<ReduceStatus>, dim3((rows + kThreads - 1) / kThreads), dim3(kThreads), 0, s, A->row_offsets, rows, A->nnz,
-                 max_tiles, tile_rows, st);
     switch (op) {
-    case SPECK_REDUCE_SUM: reduce_launch<T, SPECK_REDUCE_SUM>(s, A, d_row_out, max_tiles, recs, tile_rows, st); break;
-    case SPECK_REDUCE_ABS_SUM: reduce_launch<T, SPECK_REDUCE_ABS_SUM>(s, A, d_row_out, max_tiles, recs, tile_rows, st); break;
-    case SPECK_REDUCE_SQ_SUM: reduce_launch<T, SPECK_REDUCE_SQ_SUM>(s, A, d_row_out, max_tiles, recs, tile_rows, st); break;
-    case SPECK_REDUCE_MAX: reduce_launch<T, SPECK_REDUCE_MAX>(s, A, d_row_out, max_tiles, recs, tile_rows, st); break;
-    case SPECK_REDUCE_MIN: reduce_launch<T, SPECK_REDUCE_MIN>(s, A, d_row_out, max_tiles, recs, tile_rows, st); break;
-    default: reduce_launch<T, SPECK_REDUCE_ABS_MAX>(s, A, d_row_out, max_tiles, recs, tile_rows, st); break;
+    case SPECK_REDUCE_SUM: reduce_launch<T, SPECK_REDUCE_SUM>(s, A, d_row_out, w); break;
+    case SPECK_REDUCE_ABS_SUM: reduce_launch<T, SPECK_REDUCE_ABS_SUM>(s, A, d_row_out, w); break;
+    case SPECK_REDUCE_SQ_SUM: reduce_launch<T, SPECK_REDUCE_SQ_SUM>(s, A, d_row_out, w); break;
+    case SPECK_REDUCE_MAX: reduce_launch<T, SPECK_REDUCE_MAX>(s, A, d_row_out, w); break;
+    case SPECK_REDUCE_MIN: reduce_launch<T, SPECK_REDUCE_MIN>(s, A, d_row_out, w); break;
+    default: reduce_launch<T, SPECK_REDUCE_ABS_MAX>(s, A, d_row_out, w); break;
     }
     // the ONE read-back of the call: the verdict, the counters, the total
-    rc = read_status(s, st, h);
+    rc = read_status(s, w.st, h);
     if (rc != SPECK_OK) return rc;
     return h->invalid ? SPECK_ERR_INVALID : SPECK_OK;
 }
@@ -207,38 +175,22 @@ int reduce_impl(speck_config* cfg, const speck_dcsr* A, int op, double* d_row_ou
     if (A->nnz >= (1ull << 32)) return SPECK_ERR_NNZ_OVERFLOW;
     // (col_ids is never read: it may be NULL)
     if ((A->rows && !A->row_offsets) || (A->nnz && !A->data) || (A->rows == 0 && A->nnz)) return SPECK_ERR_INVALID;
-    if (d_row_out && (d_row_out == A->data || (void*)d_row_out == (void*)A->col_ids || (void*)d_row_out == (void*)A->row_offsets))
-        return SPECK_ERR_INVALID;
+    if (d_row_out && is_one_of(d_row_out, A)) return SPECK_ERR_INVALID;
     if (!cfg && !device_present()) return SPECK_ERR_NO_DEVICE;
     if (A->rows == 0) {  // no row, no entry: the identity
         if (h_total) *h_total = identity_of(op);
         if (info) *info = speck_reduce_info{};
         return SPECK_OK;
     }
-    ReduceScratch own;
-    ReduceScratch* sc = cfg ? reduce_scratch(cfg) : &own;
-    const hipStream_t s = cfg ? call_stream(cfg) : nullptr;
-    (void)take_launch_error();
     ReduceStatus h{};
-    int rc = reduce_run<T>(sc, s, A, op, d_row_out, &h);
-    if (rc != SPECK_OK) (void)hipStreamSynchronize(s);
-    const void* whole[] = {sc->fixed.p, sc->var.p};
-    rc = guard_check_buffers(whole, kGuardNames, 2, s, " by the reduction", rc);
-    if (!cfg) {
-        (void)hipStreamSynchronize(s);
-        own.release();
-    }
+    const int rc = run_tile_call(cfg, reduce_scratch, kGuardNames, 2, " by the reduction",
+                                 [&](TileScratch* sc, hipStream_t s) { return reduce_run<T>(sc, s, A, op, d_row_out, &h); });
     if (rc != SPECK_OK) {
         if (info) *info = speck_reduce_info{};
         return rc;
     }
     if (h_total) *h_total = h.total;
-    if (info) {
-        info->rows_empty = h.rows_empty;
-        info->rows_split = h.rows_split;
-        info->tiles = A->nnz ? (u64(h.base) + A->nnz - 1) / kTile - u64(h.base) / kTile + 1 : 0;
-        info->entries = A->nnz;
-    }
+    if (info) fill_tile_info(info, h, A);
     return SPECK_OK;
 }
 

@@ -316,8 +316,6 @@ __global__ __launch_bounds__(kThreads) void scale_offsets_kernel(const u32* __re
 }
 
 // ------------------------------------------------------------------------------------------------ host
-bool on_16_bytes(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 template <typename T>
 int scale_run(ScaleScratch* sc, hipStream_t s, const speck_dcsr* A, const speck_scale_params* p, speck_dcsr* C,
               speck_scale_info* info, COut* out)
@@ -379,8 +377,6 @@ int scale_run(ScaleScratch* sc, hipStream_t s, const speck_dcsr* A, const speck_
 
 const char* const kGuardNamesC[5] = {"scale status", "scale tile rows", "C.data", "C.col_ids", "C.row_offsets"};
 const char* const kGuardNamesA[5] = {"scale status", "scale tile rows", "A.data", "A.col_ids", "A.row_offsets"};
-
-bool is_one_of(const void* v, const speck_dcsr* X) { return v == X->data || v == X->col_ids || v == X->row_offsets; }
 
 template <typename T>
 int scale_impl(speck_config* cfg, const speck_dcsr* A, const speck_scale_params* p, speck_dcsr* C, speck_scale_info* info)

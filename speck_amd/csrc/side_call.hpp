@@ -1,6 +1,7 @@
 // side_call.hpp -- the host side of what the side operations (sort_rows.hip, masked.hip, select.hip, add.hip) share beside
 // C's buffers (compact.hpp): how a call carves its fixed scratch, reads its status block, checks the canary zones (debug
-// option guard_bytes), and the frame around its body.
+// option guard_bytes), and the frame around its body.  (The calls that hand over no C but a vector -- reduce, spmv, spmm --
+// have theirs in tile_call.hpp, which takes read_status from here.)
 #pragma once
 #include "compact.hpp"
 #include "launch.hpp"

@@ -24,17 +24,15 @@
 //                         no entry (+0.0); one workgroup counts the split rows.  Every Y(i,c) is written once by one thread,
 //                         which reads it itself where beta != 0.  The padding [k, ldy) of a row is neither read nor written.
 // All index arithmetic i ld + c is 64-bit.  No floating-point atomic; one read-back, at the end.
+// What is spmv.hip's word for word -- a tile kernel's opening, the load of the entries, the check of the ids, the write of
+// a y; the scratch, the check's launch, the frame of the call -- is tile_combine.hpp's and tile_call.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
 
-#include "entry_tiles.hpp"
 #include "launch.hpp"
-#include "row_tiles.hpp"
-#include "side_call.hpp"
-#include "spmm.hpp"
-#include "tile_combine.hpp"
+#include "tile_call.hpp"
 
 // every product and every sum is rounded on its own: the terms and the sums are those of spmv.hip
 #pragma clang fp contract(off)
@@ -51,13 +49,6 @@ using Sum = Op<SPECK_REDUCE_SUM>;
 constexpr u32 kCB = SPECK_SPMM_COLUMN_BLOCK;
 static_assert(kCB % 2 == 0, "a 16-byte gather takes two columns");
 
-struct SpmmStatus {
-    u32 invalid;  // the offsets (tile_check_kernel)
-    u32 base;     // row_offsets[0]
-    unsigned long long rows_empty, rows_split;
-    u32 bad_id;   // a column id >= cols (spmm_tile_kernel)
-};
-
 template <typename T>
 struct SpmmArgs {
     const u32* ro;
@@ -73,12 +64,7 @@ struct SpmmArgs {
     u32 pairs;       // x starts on a 16-byte boundary and ldx is even: X(j, c) with even c lies on one
     TileRec* recs;
     const u32* tile_rows;
-    SpmmStatus* st;
-};
-
-template <typename V, u32 N>
-struct alignas(16) Vec {
-    V v[N];
+    ProductStatus* st;
 };
 
 // ------------------------------------------------------------------------------------------------ tiles
@@ -89,7 +75,7 @@ struct alignas(16) Vec {
 // matrix reaches.
 template <u32 W, bool PAIR, typename T>
 __device__ __forceinline__ void column_block(const SpmmArgs<T>& g, TileLds& s_tile, const TileRows rows, const double (&a)[kPer],
-                                             u32 (&c)[kPer], u32 in_mask, u64 tile0, u64 lo, u64 hi, u32 c0)
+                                             u32 (&c)[kPer], u32 in_mask, const TileFrame& f, u32 c0)
 {
 #pragma clang fp contract(off)
     static_assert(!PAIR || W % 2 == 0, "a 16-byte gather takes two columns");
@@ -120,7 +106,7 @@ __device__ __forceinline__ void column_block(const SpmmArgs<T>& g, TileLds& s_ti
 #pragma unroll
         for (u32 e = 0; e < kPer; ++e) v[e] = ((in_mask >> e) & 1u) ? a[e] * xv[j][e] : Sum::ident();
         const u32 cc = c0 + j;
-        combine_terms<Sum>(s_tile, rows, v, g.ro, g.recs + (u64(cc) * g.max_tiles + blockIdx.x), tile0, lo, hi,
+        combine_terms<Sum>(s_tile, rows, v, g.ro, g.recs + (u64(cc) * g.max_tiles + blockIdx.x), f.tile0, f.lo, f.hi,
                            [sums, nk, cc](u32 r, double val) { sums[u64(r) * nk + cc] = val; });
         // the rows that end in the tile were read from val and incl: the next column overwrites both
         __syncthreads();
@@ -133,86 +119,50 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
     SPECK_POISON();
     __shared__ TileLds s_tile;
     if (g.st->invalid) return;  // (the verdict of tile_check_kernel: nothing below runs on offsets it refused)
-    const u32 t = threadIdx.x;
-    const u64 base = g.st->base, end = base + g.nnz;
-    const u64 tile0 = (base / kTile + blockIdx.x) * kTile;
-    if (tile0 >= end) return;  // (the grid is sized without knowing the base)
-    const u64 lo = std::max(tile0, base), hi = std::min(tile0 + kTile, end);
-    const bool whole = lo == tile0 && hi == tile0 + kTile;
+    TileFrame f;
+    if (!tile_frame(g.st->base, g.nnz, blockIdx.x, &f)) return;
 
     // the thread's 16 entries (as doubles: the conversion is exact and happens once) and their column ids, once for all
     // columns; where the matrix does not reach: id 0, never used
+    T at[kPer];
     double a[kPer];
     u32 c[kPer];
-    const u64 q0 = tile0 + u64(t) * kPer;
-    if (whole && g.aligned) {
-        constexpr u32 N = 16 / sizeof(T);
-        const Vec<T, N>* src = reinterpret_cast<const Vec<T, N>*>(g.data + q0);
-        const Vec<u32, 4>* cs = reinterpret_cast<const Vec<u32, 4>*>(g.col + q0);
-        Vec<T, N> av[kPer / N];
-        Vec<u32, 4> cv[kPer / 4];
+    load_entries<true>(f, f.whole && g.aligned, g.data, g.col, at, c);
 #pragma unroll
-        for (u32 e = 0; e < kPer / N; ++e) av[e] = src[e];
-#pragma unroll
-        for (u32 e = 0; e < kPer / 4; ++e) cv[e] = cs[e];
-#pragma unroll
-        for (u32 e = 0; e < kPer; ++e) a[e] = av[e / N].v[e % N], c[e] = cv[e / 4].v[e % 4];
-    } else {
-#pragma unroll
-        for (u32 e = 0; e < kPer; ++e) {
-            const u64 p = q0 + e;
-            const bool in = p >= lo && p < hi;
-            a[e] = in ? (double)g.data[p] : 0.0;
-            c[e] = in ? g.col[p] : 0u;
-        }
-    }
+    for (u32 e = 0; e < kPer; ++e) a[e] = (double)at[e];
 
     // an id the matrix has no column for is reported and not followed: from here on c holds ids < cols only
     const u32 last = g.cols - 1u;
     bool bad = false;
 #pragma unroll
-    for (u32 e = 0; e < kPer; ++e) {
-        bad |= c[e] > last;
-        c[e] = std::min(c[e], last);
-    }
+    for (u32 e = 0; e < kPer; ++e) c[e] = clamp_id(c[e], last, &bad);
     if (bad) g.st->bad_id = 1;
     // (the entries of a tile that is not whole which the matrix does not reach: their term is the identity)
     u32 in_mask = 0xFFFFu;
-    if (!whole) {
+    if (!f.whole) {
         in_mask = 0;
 #pragma unroll
-        for (u32 e = 0; e < kPer; ++e) in_mask |= u32(q0 + e >= lo && q0 + e < hi) << e;
+        for (u32 e = 0; e < kPer; ++e) in_mask |= u32(entry_in(f, e)) << e;
     }
 
-    const TileRows rows = tile_begin(s_tile, g.ro, g.tile_rows, tile0);
+    const TileRows rows = tile_begin(s_tile, g.ro, g.tile_rows, f.tile0);
     // the columns in blocks of kCB, then what is left in pairs and alone; one straight path per form of block
     const u32 nk = g.k;
     u32 c0 = 0;
     if (g.pairs) {
-        for (; c0 + kCB <= nk; c0 += kCB) column_block<kCB, true>(g, s_tile, rows, a, c, in_mask, tile0, lo, hi, c0);
-        for (; c0 + 2 <= nk; c0 += 2) column_block<2, true>(g, s_tile, rows, a, c, in_mask, tile0, lo, hi, c0);
+        for (; c0 + kCB <= nk; c0 += kCB) column_block<kCB, true>(g, s_tile, rows, a, c, in_mask, f, c0);
+        for (; c0 + 2 <= nk; c0 += 2) column_block<2, true>(g, s_tile, rows, a, c, in_mask, f, c0);
     } else {
-        for (; c0 + kCB <= nk; c0 += kCB) column_block<kCB, false>(g, s_tile, rows, a, c, in_mask, tile0, lo, hi, c0);
+        for (; c0 + kCB <= nk; c0 += kCB) column_block<kCB, false>(g, s_tile, rows, a, c, in_mask, f, c0);
     }
-    for (; c0 < nk; ++c0) column_block<1, false>(g, s_tile, rows, a, c, in_mask, tile0, lo, hi, c0);
+    for (; c0 < nk; ++c0) column_block<1, false>(g, s_tile, rows, a, c, in_mask, f, c0);
 }
 
 // ------------------------------------------------------------------------------------------------ finish, and Y
-__device__ __forceinline__ void write_y(double* __restrict__ y, u64 at, double s, double alpha, double beta)
-{
-#pragma clang fp contract(off)
-    const double as = alpha * s;
-    if (beta == 0.0) y[at] = as;  // (Y is not read: what it held does not survive)
-    else {
-        const double by = beta * y[at];
-        y[at] = as + by;
-    }
-}
-
 __global__ __launch_bounds__(kThreads) void spmm_finish_kernel(const u32* __restrict__ ro, u32 rows, u64 nnz, u32 k, u32 max_tiles,
                                                                u32 chain_blocks, u32 row_blocks, const double* __restrict__ sums,
                                                                const TileRec* __restrict__ recs, double alpha, double beta,
-                                                               double* __restrict__ y, u64 ldy, SpmmStatus* st)
+                                                               double* __restrict__ y, u64 ldy, ProductStatus* st)
 {
     SPECK_POISON();
     __shared__ double s_w[kWaves];
@@ -251,50 +201,32 @@ __global__ __launch_bounds__(kThreads) void spmm_finish_kernel(const u32* __rest
 }
 
 // ------------------------------------------------------------------------------------------------ host
-bool on_16_bytes(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 template <typename T>
-int spmm_run(SpmmScratch* sc, hipStream_t s, double alpha, const speck_dcsr* A, const double* d_X, u64 ldx, u32 k, double beta,
-             double* d_Y, u64 ldy, SpmmStatus* h)
+int spmm_run(TileScratch* sc, hipStream_t s, double alpha, const speck_dcsr* A, const double* d_X, u64 ldx, u32 k, double beta,
+             double* d_Y, u64 ldy, ProductStatus* h)
 {
     const u32 rows = (u32)A->rows;
-    const u32 max_tiles = entry_tiles_at_most(A->nnz, kTile);
-    static_assert(sizeof(SpmmStatus) <= 256, "status block");
-    int rc = sc->fixed.ensure(256);
+    TileWork<ProductStatus> w;
+    int rc = carve_and_check(sc, s, A, k, size_t(rows) * k, &w);
     if (rc != SPECK_OK) return rc;
-    const size_t rec_bytes = up256(size_t(std::max(max_tiles, 1u)) * k * sizeof(TileRec));
-    rc = sc->var.ensure(rec_bytes + up256(size_t(std::max(max_tiles, 1u)) * 8));
-    if (rc != SPECK_OK) return rc;
-    rc = sc->sums.ensure(up256(size_t(rows) * k * 8));
-    if (rc != SPECK_OK) return rc;
-    SpmmStatus* st = static_cast<SpmmStatus*>(sc->fixed.p);
-    TileRec* recs = static_cast<TileRec*>(sc->var.p);
-    u32* tile_rows = reinterpret_cast<u32*>(static_cast<unsigned char*>(sc->var.p) + rec_bytes);
-    double* sums = static_cast<double*>(sc->sums.p);
-
-    HIP_TRY(hipMemsetAsync(st, 0, sizeof(SpmmStatus), s));
-    SPECK_LAUNCH(tile_check_kernel<SpmmStatus>, dim3((rows + kThreads - 1) / kThreads), dim3(kThreads), 0, s, A->row_offsets, rows,
-                 A->nnz, max_tiles, tile_rows, st);
-    if (max_tiles) {
-        const SpmmArgs<T> g{A->row_offsets, A->col_ids, static_cast<const T*>(A->data), d_X, sums, A->nnz, ldx, rows, (u32)A->cols, k,
-                            max_tiles, on_16_bytes(A->data) && on_16_bytes(A->col_ids) ? 1u : 0u,
-                            on_16_bytes(d_X) && ldx % 2 == 0 ? 1u : 0u, recs, tile_rows, st};
-        SPECK_LAUNCH(spmm_tile_kernel<T>, dim3(max_tiles), dim3(kThreads), 0, s, g);
+    if (w.max_tiles) {
+        const SpmmArgs<T> g{A->row_offsets, A->col_ids, static_cast<const T*>(A->data), d_X, w.sums, A->nnz, ldx, rows, (u32)A->cols, k,
+                            w.max_tiles, on_16_bytes(A->data) && on_16_bytes(A->col_ids) ? 1u : 0u,
+                            on_16_bytes(d_X) && ldx % 2 == 0 ? 1u : 0u, w.recs, w.tile_rows, w.st};
+        SPECK_LAUNCH(spmm_tile_kernel<T>, dim3(w.max_tiles), dim3(kThreads), 0, s, g);
     }
     // (rows <= 2^27, k <= 2^10, tiles <= 2^20 + 1: the grid stays below 2^30)
-    const u32 chain_blocks = (u32)((u64(max_tiles) * k + kWaves - 1) / kWaves);
+    const u32 chain_blocks = (u32)((u64(w.max_tiles) * k + kWaves - 1) / kWaves);
     const u32 row_blocks = (u32)((u64(rows) * k + kThreads - 1) / kThreads);
     SPECK_LAUNCH(spmm_finish_kernel, dim3(chain_blocks + row_blocks + 1u), dim3(kThreads), 0, s, A->row_offsets, rows, A->nnz, k,
-                 max_tiles, chain_blocks, row_blocks, sums, recs, alpha, beta, d_Y, ldy, st);
+                 w.max_tiles, chain_blocks, row_blocks, w.sums, w.recs, alpha, beta, d_Y, ldy, w.st);
     // the ONE read-back of the call: the two verdicts, the counters
-    rc = read_status(s, st, h);
+    rc = read_status(s, w.st, h);
     if (rc != SPECK_OK) return rc;
     return (h->invalid || h->bad_id) ? SPECK_ERR_INVALID : SPECK_OK;
 }
 
 const char* const kGuardNames[3] = {"spmm status", "spmm tile records and rows", "spmm row sums"};
-
-bool is_one_of(const void* v, const speck_dcsr* X) { return v == X->data || v == X->col_ids || v == X->row_offsets; }
 
 template <typename T>
 int spmm_impl(speck_config* cfg, double alpha, const speck_dcsr* A, const double* d_X, u64 ldx, u32 k, double beta, double* d_Y,
@@ -319,25 +251,12 @@ int spmm_impl(speck_config* cfg, double alpha, const speck_dcsr* A, const double
     if (info) *info = speck_spmm_info{};
     if (!cfg && !device_present()) return SPECK_ERR_NO_DEVICE;
     if (A->rows == 0 || k == 0) return SPECK_OK;  // no row or no column: nothing to write
-    SpmmScratch own;
-    SpmmScratch* sc = cfg ? spmm_scratch(cfg) : &own;
-    const hipStream_t s = cfg ? call_stream(cfg) : nullptr;
-    (void)take_launch_error();
-    SpmmStatus h{};
-    int rc = spmm_run<T>(sc, s, alpha, A, d_X, ldx, k, beta, d_Y, ldy, &h);
-    if (rc != SPECK_OK) (void)hipStreamSynchronize(s);
-    const void* whole[] = {sc->fixed.p, sc->var.p, sc->sums.p};
-    rc = guard_check_buffers(whole, kGuardNames, 3, s, " by the product with several right-hand sides", rc);
-    if (!cfg) {
-        (void)hipStreamSynchronize(s);
-        own.release();
-    }
+    ProductStatus h{};
+    const int rc = run_tile_call(cfg, spmm_scratch, kGuardNames, 3, " by the product with several right-hand sides",
+                                 [&](TileScratch* sc, hipStream_t s) { return spmm_run<T>(sc, s, alpha, A, d_X, ldx, k, beta, d_Y, ldy, &h); });
     if (rc != SPECK_OK) return rc;
     if (info) {
-        info->rows_empty = h.rows_empty;
-        info->rows_split = h.rows_split;
-        info->tiles = A->nnz ? (u64(h.base) + A->nnz - 1) / kTile - u64(h.base) / kTile + 1 : 0;
-        info->entries = A->nnz;
+        fill_tile_info(info, h, A);
         info->terms = A->nnz * k;
     }
     return SPECK_OK;

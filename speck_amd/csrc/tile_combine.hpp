@@ -5,7 +5,11 @@
 // such a row together from the records in a fixed tree over the tile numbers.  Where the 16 terms of a thread come from
 // (g(a) in the reduction, a x[j] in the matrix-vector product) and what happens to a finished row is the caller's; the
 // tree is one: it depends on the absolute positions of the entries alone.  The check of the offsets, which also tells
-// every tile the rows of its first and last entry, is entry_tiles.hpp's behind one kernel for both.
+// every tile the rows of its first and last entry, is entry_tiles.hpp's behind one kernel for all three.
+// Around the combine, what a tile's workgroup does first and a finish kernel does last is here as well: which entries
+// the tile holds (tile_frame), the load of a thread's 16 values and column ids (load_entries), the check of an id
+// (clamp_id), the status block of the two products (ProductStatus) and the one write of a y (write_y).  The host side of
+// the three calls is tile_call.hpp.
 #pragma once
 #include <algorithm>
 
@@ -97,6 +101,14 @@ __device__ __forceinline__ double wave_combine(double x)
 }
 
 // ------------------------------------------------------------------------------------------------ check
+// the status block of spmv.hip and spmm.hip (reduce.hip's carries a total instead of bad_id)
+struct ProductStatus {
+    u32 invalid;  // the offsets (tile_check_kernel)
+    u32 base;     // row_offsets[0]
+    unsigned long long rows_empty, rows_split;
+    u32 bad_id;   // a column id >= cols (the tile kernel)
+};
+
 // A thread per row (entry_tiles.hpp); Status begins with { u32 invalid, base; unsigned long long rows_empty; }.
 // tile_rows[2 i], [2 i + 1]: the rows of the first and of the last entry of the i-th tile the matrix touches
 template <typename Status>
@@ -116,6 +128,81 @@ __global__ __launch_bounds__(kThreads) void tile_check_kernel(const u32* __restr
 }
 
 // ------------------------------------------------------------------------------------------------ tiles
+// The tile of workgroup i: the absolute entries [tile0, tile0 + kTile), of which [lo, hi) belong to the matrix -- all of
+// them where `whole`
+struct TileFrame {
+    u64 tile0, lo, hi;
+    bool whole;
+};
+
+// The i-th tile a matrix of nnz entries from `base` on touches; false where it touches fewer: this workgroup has no tile
+// (the grid is sized without knowing the base).  The forms of this function, of entry_in and of clamp_id are the ones that
+// leave the tile kernels their registers: DESIGN.md 4.18.
+__device__ __forceinline__ bool tile_frame(u64 base, u64 nnz, u32 i, TileFrame* f)
+{
+    const u64 end = base + nnz, tile0 = (base / kTile + i) * kTile;
+    const u64 lo = std::max(tile0, base), hi = std::min(tile0 + kTile, end);
+    *f = TileFrame{tile0, lo, hi, lo == tile0 && hi == tile0 + kTile};
+    return tile0 < end;
+}
+
+template <typename V, u32 N>
+struct alignas(16) Vec {
+    V v[N];
+};
+
+// The thread's kPer entries of the tile, the absolute entries from f.tile0 + kPer threadIdx.x on: their values in a and,
+// with IDS, their column ids in c (without: c is not touched and may be null).  wide: 16-byte loads -- the caller says
+// that the tile is whole and that the arrays lie on 16-byte boundaries; entry by entry elsewhere, and where the matrix
+// does not reach the value is T(0) and the id 0.
+template <bool IDS, typename T>
+__device__ __forceinline__ void load_entries(const TileFrame& f, bool wide, const T* __restrict__ data, const u32* __restrict__ col,
+                                             T* a, u32* c)
+{
+    const u64 q0 = f.tile0 + u64(threadIdx.x) * kPer;
+    if (wide) {
+        constexpr u32 N = 16 / sizeof(T);
+        const Vec<T, N>* src = reinterpret_cast<const Vec<T, N>*>(data + q0);
+        Vec<T, N> av[kPer / N];
+#pragma unroll
+        for (u32 k = 0; k < kPer / N; ++k) av[k] = src[k];
+        if constexpr (IDS) {
+            const Vec<u32, 4>* cs = reinterpret_cast<const Vec<u32, 4>*>(col + q0);
+            Vec<u32, 4> cv[kPer / 4];
+#pragma unroll
+            for (u32 k = 0; k < kPer / 4; ++k) cv[k] = cs[k];
+#pragma unroll
+            for (u32 k = 0; k < kPer; ++k) c[k] = cv[k / 4].v[k % 4];
+        }
+#pragma unroll
+        for (u32 k = 0; k < kPer; ++k) a[k] = av[k / N].v[k % N];
+    } else {
+#pragma unroll
+        for (u32 k = 0; k < kPer; ++k) {
+            const u64 p = q0 + k;
+            const bool in = p >= f.lo && p < f.hi;
+            a[k] = in ? data[p] : T(0);
+            if constexpr (IDS) c[k] = in ? col[p] : 0u;
+        }
+    }
+}
+
+// whether entry k of the thread (load_entries) lies in [lo, hi) -- in a tile that is not whole, the entries the matrix
+// reaches: the term of any other is the identity
+__device__ __forceinline__ bool entry_in(const TileFrame& f, u32 k)
+{
+    const u64 p = f.tile0 + u64(threadIdx.x) * kPer + k;
+    return p >= f.lo && p < f.hi;
+}
+
+// An id the matrix has no column for is reported and not followed: the id a gather may use, with `bad` raised where c
+// lies behind `last`, the matrix's last column
+__device__ __forceinline__ u32 clamp_id(u32 c, u32 last, bool* bad)
+{
+    *bad |= c > last;
+    return std::min(c, last);
+}
+
 // the LDS of a tile's workgroup (about 36 KB)
 struct TileLds {
     double val[kTile + kTile / 16];
@@ -228,7 +315,7 @@ __device__ __forceinline__ void combine_tile(TileLds& s, const double (&v)[kPer]
 
 // ------------------------------------------------------------------------------------------------ finish
 // the tiles a matrix of nnz entries from `base` on touches
-__device__ __forceinline__ u32 tiles_touched(u64 base, u64 nnz)
+__host__ __device__ __forceinline__ u32 tiles_touched(u64 base, u64 nnz)
 {
     return nnz ? (u32)((base + nnz - 1) / kTile - base / kTile + 1) : 0u;
 }
@@ -271,6 +358,18 @@ __device__ __forceinline__ bool totals_finish(const TileRec* __restrict__ recs, 
     *total = sum;
     *split_rows = split;
     return true;
+}
+
+// y[at] = alpha s + beta y[at], each product and the sum rounded on its own; the one write of a result of spmv.hip and spmm.hip
+__device__ __forceinline__ void write_y(double* __restrict__ y, u64 at, double s, double alpha, double beta)
+{
+#pragma clang fp contract(off)
+    const double as = alpha * s;
+    if (beta == 0.0) y[at] = as;  // (y is not read: what it held does not survive)
+    else {
+        const double by = beta * y[at];
+        y[at] = as + by;
+    }
 }
 #endif  // __HIPCC__
 
