@@ -575,7 +575,10 @@ __global__ __launch_bounds__(NW * 64) void analysis_kernel(
 // kChainMaxBlocks workgroups).  Per tile: nnz sum + class histogram -> the chain -> row_offsets = (nnz before my tile)
 // + local scan, RowRec.base / nnz of every row, the row's id in its numeric class list at (rows of the class before my
 // tile) + rank (ascending rows inside a class).  The last tile writes the statistics the host and the numeric kernels read.
-// Traffic: 8(m+1) B for the scan itself + 16 m read for the classification + 36 m for records and lists.
+// Traffic: 8(m+1) B for the scan itself + 16 m read for the classification + 36 m for records and lists
+// (+ 16 m from the L2 with 8 / 32 rows per thread, where the records read the classification's inputs again).
+// Trips of a tile: ONE round of loads (every row of a thread, up to four; groups of four beyond), the aggregate out, the
+// look-back, the scans inside the tile, stores.
 // --------------------------------------------------------------------------------
 constexpr int kScanThreads = 256;
 // rows per thread: small inputs still get >= ~300 tiles, big ones at most kChainMaxBlocks.  32 rows per thread are a
@@ -635,27 +638,61 @@ __global__ __launch_bounds__(kScanThreads) void scan_kernel(
     __shared__ u32 s_run[kMaxClasses];  // rows of each class before the current sub-tile
     __shared__ u64 s_off_run;           // nnz before the current sub-tile
     const u32 lane = lane_id(), wid = threadIdx.x >> 6, t = threadIdx.x;
+    if constexpr (!WIDE) sub = 1;  // (launch_scan: several sub-tiles only in the WIDE form)
     const u64 tile0 = u64(blockIdx.x) * kSubRows * sub;
+    // through call: the last tile asks for the input check's ticket NOW, beside its first loads, and for the verdict as soon
+    // as this call's ticket is there (below) -- behind the look-back each of the two was a trip to host memory of its own.
+    // The early look can only find the check DONE: a ticket that is not this call's yet is read again where it is used.
+    const bool gate_lane = gate && blockIdx.x == gridDim.x - 1 && t == 0;
+    u32 early_ticket = 0, early_verdict = 0;
+    bool gate_early = false;
+    if (gate_lane && gate_ticket) early_ticket = __hip_atomic_load(gate + 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     u32 c[ITEMS];
     u8 cls[ITEMS];
+    // what a group of <= 4 consecutive rows is classified from: REQUESTED together, used behind that (one round of loads per
+    // group where a row at a time took two dependent ones).  Up to 4 rows per thread that is the whole tile and the records
+    // are written from these registers; with 8 / 32 rows the records read them again, from the L2, group by group.
+    constexpr int G = ITEMS < 4 ? ITEMS : 4;
+    constexpr bool kKept = ITEMS <= 4 && !WIDE;
+    static_assert(ITEMS % G == 0, "whole groups");
+    u32 g_ro[G + 1], g_rops[G], g_cmin[G], g_cmax[G];
     if (t < kMaxClasses) s_bytes[t] = 0;
     u64 g_ops = 0;
-    // one sub-tile's rows into registers (+ their classes; what the classification reads is read again, from the L2,
-    // when the records are written: 32 rows per thread would not fit the register file otherwise)
+    // rows [row0, row0 + G) of a thread; a row >= m reads nothing (the arrays end there, a row view has live rows behind it)
+    auto request = [&](u64 row0) {
+#pragma unroll
+        for (int j = 0; j <= G; ++j) {
+            const u64 row = row0 + j;
+            // a_ro[row] ends row - 1 and starts row
+            g_ro[j] = (j == 0 ? row < m : row <= m) ? a_ro[row] : 0u;
+        }
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+            const bool in = row0 + j < m;
+            g_rops[j] = in ? row_ops[row0 + j] : 0u;
+            g_cmin[j] = in ? row_col_min[row0 + j] : 0u;
+            g_cmax[j] = in ? row_col_max[row0 + j] : 0u;
+        }
+    };
+    // one sub-tile's rows into registers (+ their classes)
     auto load = [&](u32 s, bool count_g) {
         const u64 base = tile0 + u64(s) * kSubRows + u64(t) * ITEMS;
 #pragma unroll
-        for (int i = 0; i < ITEMS; ++i) {
-            const u64 row = base + i;
-            const bool in = row < m;
-            c[i] = in ? counts[row] : 0u;
-            cls[i] = NUM_NONE;
-            if (recs && in) {
-                const u32 len_a = a_ro[row + 1] - a_ro[row], ops = row_ops[row];
-                cls[i] = classify_numeric(len_a, ops, c[i], row_col_min[row], row_col_max[row], cp);
-                if (count_g && cls[i] == NUM_G) g_ops += ops;
-                if (count_g && cp.want_bytes && cls[i] != NUM_NONE)
-                    atomicAdd((unsigned long long*)&s_bytes[cls[i]], (unsigned long long)numeric_row_bytes(len_a, ops, c[i], vsize));
+        for (int g0 = 0; g0 < ITEMS; g0 += G) {
+#pragma unroll
+            for (int j = 0; j < G; ++j) c[g0 + j] = base + g0 + j < m ? counts[base + g0 + j] : 0u;
+            if (recs) request(base + g0);
+#pragma unroll
+            for (int j = 0; j < G; ++j) {
+                const int i = g0 + j;
+                cls[i] = NUM_NONE;
+                if (recs && base + i < m) {
+                    const u32 len_a = g_ro[j + 1] - g_ro[j], ops = g_rops[j];
+                    cls[i] = classify_numeric(len_a, ops, c[i], g_cmin[j], g_cmax[j], cp);
+                    if (count_g && cls[i] == NUM_G) g_ops += ops;
+                    if (count_g && cp.want_bytes && cls[i] != NUM_NONE)
+                        atomicAdd((unsigned long long*)&s_bytes[cls[i]], (unsigned long long)numeric_row_bytes(len_a, ops, c[i], vsize));
+                }
             }
         }
     };
@@ -664,7 +701,7 @@ __global__ __launch_bounds__(kScanThreads) void scan_kernel(
     u32 my_max = 0;
     PackedCounts packed_all;   // (per thread <= 32 x sub rows of a class: fits 16 bits up to sub = 2048)
     u32 hist_wide[WIDE ? kMaxClasses : 1];
-    constexpr bool wide = WIDE;  // (sub > 1) counts of several sub-tiles: 32-bit accumulators
+    // (WIDE: counts of several sub-tiles, 32-bit accumulators)
     if constexpr (WIDE) {
 #pragma unroll
         for (int k = 0; k < kMaxClasses; ++k) hist_wide[k] = 0;
@@ -684,6 +721,13 @@ __global__ __launch_bounds__(kScanThreads) void scan_kernel(
             for (int k = 0; k < kMaxClasses; ++k) hist_wide[k] += packed.get(k);
         } else
             packed_all = packed;
+    }
+    // (the ticket came in with the tile's own loads.  gate_ticket == 0: the check's stream was joined, the verdict is final.
+    //  Ticket, acquire at system scope, verdict: the order and the scopes of the late look)
+    if (gate_lane && early_ticket == gate_ticket) {
+        if (gate_ticket) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+        early_verdict = __hip_atomic_load(gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        gate_early = true;
     }
     tsum = wave_reduce_add(tsum);
     g_ops = wave_reduce_add(g_ops);
@@ -763,9 +807,13 @@ __global__ __launch_bounds__(kScanThreads) void scan_kernel(
             // input check of B has finished (the stream waited for it) -- a violation voids them, C stays as it is
             // (gate_ticket: the check's stream was NOT joined -- a cross-queue wait costs ~6 us even on a finished branch --
             //  the check counts as done only if its ticket kernel has stored this call's ticket; else: void, the call re-runs)
+            // (the tile asked for both when it started; a check that was not through by then is looked at again, here)
             if (gate) {
-                const u32 ticket = gate_ticket ? __hip_atomic_load(gate + 16, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) : 0u;
-                const u32 verdict = __hip_atomic_load(gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                u32 ticket = early_ticket, verdict = early_verdict;
+                if (!gate_early) {
+                    ticket = gate_ticket ? __hip_atomic_load(gate + 16, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) : 0u;
+                    verdict = __hip_atomic_load(gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                }
                 if ((verdict & 4u) || ticket != gate_ticket) st->capacity_miss = 1;
             }
             if (!chain_ok || chain_error(chain)) {
@@ -795,82 +843,92 @@ __global__ __launch_bounds__(kScanThreads) void scan_kernel(
     }
     // ---- pass 2: offsets, records, class lists (nothing from a truncated prefix: chain.hpp)
     if (!chain_ok) return;
+    // what places a row INSIDE its sub-tile: nnz of the threads before mine, rows of each class in the threads before mine
+    // (s_wave keeps the waves' class totals).  (Run between the publish and the look-back, where it needs no prefix, it
+    // did not shorten the call: HISTORY.md, scan_one_round)
+    u32 excl = 0, total = 0;
+    PackedCounts before;
+    auto local_scans = [&]() {
+        u32 tsum32 = 0;
+#pragma unroll
+        for (int i = 0; i < ITEMS; ++i) tsum32 += c[i];
+        excl = block_exclusive_scan<kScanThreads>(tsum32, s_scan, &total);
+        if (!recs) return;
+        PackedCounts mine;
+#pragma unroll
+        for (int i = 0; i < ITEMS; ++i)
+            if (cls[i] != NUM_NONE) mine.add(cls[i]);
+        PackedCounts incl = mine;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const u64 ta = __shfl_up(incl.a, o, 64), tb = __shfl_up(incl.b, o, 64), tc = __shfl_up(incl.c, o, 64),
+                      td = __shfl_up(incl.d, o, 64);
+            if (lane >= (u32)o) {
+                incl.a += ta;
+                incl.b += tb;
+                incl.c += tc;
+                incl.d += td;
+            }
+        }
+        if (lane == 63) {
+            s_wave[wid][0] = incl.a;
+            s_wave[wid][1] = incl.b;
+            s_wave[wid][2] = incl.c;
+            s_wave[wid][3] = incl.d;
+        }
+        __syncthreads();
+        before.a = incl.a - mine.a;
+        before.b = incl.b - mine.b;
+        before.c = incl.c - mine.c;
+        before.d = incl.d - mine.d;
+        for (u32 w = 0; w < wid; ++w) {
+            before.a += s_wave[w][0];
+            before.b += s_wave[w][1];
+            before.c += s_wave[w][2];
+            before.d += s_wave[w][3];
+        }
+    };
     if (t < kMaxClasses) s_run[t] = (u32)s_pref[kCwClass + t];
     if (t == 0) s_off_run = nnz_before;
     __syncthreads();
     for (u32 s = 0; s < sub; ++s) {
-        if (wide) load(s, false);
+        if constexpr (WIDE) load(s, false);
+        local_scans();
         const u64 base = tile0 + u64(s) * kSubRows + u64(t) * ITEMS;
-        u32 tsum32 = 0;
-#pragma unroll
-        for (int i = 0; i < ITEMS; ++i) tsum32 += c[i];
-        u32 total;
-        const u32 excl = block_exclusive_scan<kScanThreads>(tsum32, s_scan, &total);
         u32 run = (u32)s_off_run + excl;
-        u32 off[ITEMS];
         bool moved = false;
+        PackedCounts used;
 #pragma unroll
-        for (int i = 0; i < ITEMS; ++i) {
-            off[i] = run;
-            if (base + i < m) {
-                offsets_out[base + i] = run;
-                if (pred_off_out) pred_off_out[base + i] = run;  // the config's own copy: C.row_offsets is the caller's
-                // rows a replayed sequence has already placed by the previous call's offsets: the fresh ones must agree
-                // (checked for EVERY row: a shift anywhere before such a row moves it)
-                if (pred_off && pred_off[base + i] != run) moved = true;
-            }
-            run += c[i];
-        }
-        if (pred_off && __ballot(moved) != 0 && lane == 0) st->capacity_miss = 1;  // (only ever set, by whoever objects)
-        if (recs) {
-            // class of my rows, packed per-thread histogram, exclusive scan over the threads
-            PackedCounts mine;
+        for (int g0 = 0; g0 < ITEMS; g0 += G) {
+            if constexpr (!kKept)
+                if (recs) request(base + g0);  // (a group's loads first, its records behind them)
+            u32 off[G];
 #pragma unroll
-            for (int i = 0; i < ITEMS; ++i)
-                if (cls[i] != NUM_NONE) mine.add(cls[i]);
-            PackedCounts incl = mine;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const u64 ta = __shfl_up(incl.a, o, 64), tb = __shfl_up(incl.b, o, 64), tc = __shfl_up(incl.c, o, 64),
-                          td = __shfl_up(incl.d, o, 64);
-                if (lane >= (u32)o) {
-                    incl.a += ta;
-                    incl.b += tb;
-                    incl.c += tc;
-                    incl.d += td;
+            for (int j = 0; j < G; ++j) {
+                const int i = g0 + j;
+                off[j] = run;
+                run += c[i];
+                if (base + i < m) {
+                    offsets_out[base + i] = off[j];
+                    if (pred_off_out) pred_off_out[base + i] = off[j];  // the config's own copy: C.row_offsets is the caller's
+                    // rows a replayed sequence has already placed by the previous call's offsets: the fresh ones must agree
+                    // (checked for EVERY row: a shift anywhere before such a row moves it)
+                    if (pred_off && pred_off[base + i] != off[j]) moved = true;
                 }
             }
-            if (lane == 63) {
-                s_wave[wid][0] = incl.a;
-                s_wave[wid][1] = incl.b;
-                s_wave[wid][2] = incl.c;
-                s_wave[wid][3] = incl.d;
-            }
-            __syncthreads();
-            PackedCounts before;  // rows of each class in the threads before mine (exclusive)
-            before.a = incl.a - mine.a;
-            before.b = incl.b - mine.b;
-            before.c = incl.c - mine.c;
-            before.d = incl.d - mine.d;
-            for (u32 w = 0; w < wid; ++w) {
-                before.a += s_wave[w][0];
-                before.b += s_wave[w][1];
-                before.c += s_wave[w][2];
-                before.d += s_wave[w][3];
-            }
-            PackedCounts used;
+            // (a loop of their own: behind the load above a record would wait for the stores before it)
 #pragma unroll
-            for (int i = 0; i < ITEMS; ++i) {
-                const u64 row = base + i;
-                if (cls[i] == NUM_NONE) continue;
+            for (int j = 0; j < G; ++j) {
+                const int i = g0 + j;
+                if (cls[i] == NUM_NONE) continue;  // (every row when there are no records to write)
                 RowRec r;
-                r.row = (u32)row;
-                r.a0 = a_ro[row];
-                r.a1 = a_ro[row + 1];
-                r.base = off[i];
-                r.cmin = row_col_min[row];
-                r.cmax = row_col_max[row];
-                r.ops = row_ops[row];
+                r.row = (u32)(base + i);
+                r.a0 = g_ro[j];
+                r.a1 = g_ro[j + 1];
+                r.base = off[j];
+                r.cmin = g_cmin[j];
+                r.cmax = g_cmax[j];
+                r.ops = g_rops[j];
                 r.nnz = c[i];
                 const u32 k = cls[i];
                 const u32 pos = s_run[k] + before.get(k) + used.get(k);
@@ -878,8 +936,11 @@ __global__ __launch_bounds__(kScanThreads) void scan_kernel(
                 if (k == NUM_NFCOPY && pred_off) continue;  // already in place: no launch reads that list
                 if (pos < m) *class_rec_at(recs, m, k, pos) = r;
             }
+        }
+        if (pred_off && __ballot(moved) != 0 && lane == 0) st->capacity_miss = 1;  // (only ever set, by whoever objects)
+        if constexpr (WIDE) {  // the next sub-tile starts behind this one
             __syncthreads();
-            if (t < kMaxClasses) {
+            if (recs && t < kMaxClasses) {
                 PackedCounts all;
                 for (int w = 0; w < NW; ++w) {
                     all.a += s_wave[w][0];
@@ -889,9 +950,9 @@ __global__ __launch_bounds__(kScanThreads) void scan_kernel(
                 }
                 s_run[t] += all.get(t);
             }
+            if (t == 0) s_off_run += total;
+            __syncthreads();
         }
-        if (t == 0) s_off_run += total;
-        __syncthreads();
     }
 }
 
