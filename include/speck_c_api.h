@@ -632,6 +632,89 @@ int speck_spmm_f64(speck_config *cfg, double alpha, const speck_dcsr *A, const d
 int speck_spmm_f32(speck_config *cfg, double alpha, const speck_dcsr *A, const double *d_X, uint64_t ldx, uint32_t k,
                    double beta, double *d_Y, uint64_t ldy, speck_spmm_info *info);
 
+/* ---- sampled dense-dense product (new: the reference has no counterpart): C = alpha (U V^T) on A's pattern + beta A, the
+ *      one map (block, block) -> matrix beside speck_spmm_* ((matrix, block) -> block): d(i,j) = sum_c U(i,c) V(j,c) is
+ *      computed ONLY where A holds an entry.  The gradient of speck_spmm_* with respect to A's values (dA = dY X^T on A's
+ *      pattern), the edge scores of an attention layer, cosine or Gram similarities on the edges of a graph (U == V), the
+ *      residual R - U V^T of a factorisation on the observed entries (alpha = -1, beta = 1).  The structure does not
+ *      change, so C == NULL works IN PLACE, as speck_scale_*; k == 1 is speck_scale_* with a row and a column vector.
+ *  U is rows x k and V is cols x k, both ROW-MAJOR DEVICE arrays of doubles for both value types: U(i,c) = d_U[i ldu + c],
+ *      V(j,c) = d_V[j ldv + c] with ldu >= k, ldv >= k -- a contiguous torch tensor or a column slice of one.  U is
+ *      indexed by the row INSIDE A (for a row-range view the caller offsets d_U by r0 ldu), V by the column id.  The
+ *      padding [k, ld) of a row of U or V is never read.  All index arithmetic i ld + c is 64-bit.  U and V are only read:
+ *      they may overlap each other in any way, or be one block.
+ *  Values: every step in double for both value types, each rounded on its own, nothing fused.  t_c = U(i,c) * V(j,c),
+ *      rounded once.  d(i,j) is the sum of the t_c in a tree that is a function of k ALONE: a group of L(k) lanes (a
+ *      power of two <= 64) serves one entry; the columns are taken in pairs q = c >> 1; lane l owns the pairs q = l (mod L) and adds their terms one
+ *      after the other in ascending c, starting from its first term (no zero seed); a lane that owns no column holds +0.0;
+ *      the L partial sums are combined by the butterfly p = p + p[l ^ s] for s = L/2, ..., 1 (IEEE addition commutes: every
+ *      lane ends with the same bits).  Then
+ *        SPECK_SDDMM_AXPBY     x = alpha * d; where beta != 0.0 only: x = x + beta * (double)a, the product rounded, then
+ *                              the sum.  beta == 0.0 means A->data is NOT READ: a NaN there does not survive, and out of
+ *                              place A->data may be NULL (the BLAS convention, as speck_spmv_*).
+ *        SPECK_SDDMM_HADAMARD  x = alpha * d; x = x * (double)a.  beta must be 0.0 (SPECK_ERR_INVALID otherwise).
+ *      alpha is always applied.  ONE rounding to T.  info->nonfinite counts the results that are inf or NaN AFTER that
+ *      rounding; they do not make the call fail.  k == 0 is valid: d = +0.0, and d_U, d_V may be NULL.  The sign of a
+ *      zero d is unspecified, as for the reduction's s_i.
+ *  L(k) = min(8, max(1, pow2ceil(ceil(k / 4)))): 1 for k <= 4, 2 for k <= 8, 4 for k <= 16, 8 beyond -- two pairs of
+ *      columns per lane up to k = 32, ceil(k / 16) of them beyond.  Set from measurement (one lane per pair of columns,
+ *      L up to 64, was 1.3 to 2.4 times slower from k = 8 on: DESIGN.md 4.19) and fixed: it is part of the numeric
+ *      contract; info->lanes reports it.
+ *  What follows: the same bits from run to run.  The bits of an entry do not depend on where the entry lies in data, on
+ *      ldu or ldv, on the alignment of d_U / d_V (16-byte loads where the pointer lies on 16 bytes and ld is even, 8-byte
+ *      loads elsewhere, with the same results), or on whether the call is in place.  A row-range view gives bit for bit
+ *      the entries of the whole matrix's result.  For k = 1, alpha = 1, beta = 0, fp64 the result is bit for bit
+ *      speck_scale_f64(A, map ONE, row = U(:,0), col = V(:,0)).  |d - exact| <= g_k sum_c |U(i,c) V(j,c)|.  A NaN or
+ *      0 * inf of U(i,c) lands in exactly the entries of row i, one of V(j,c) in exactly the entries with column id j.
+ *      No floating-point atomic anywhere.
+ *  Structure: rows need not be sorted; duplicates each get the same value.  No entry is dropped, a result of 0.0 stays.
+ *      In place (C == NULL) only A->data[row_offsets[0] .. row_offsets[0] + nnz) is written: on a row-range view the
+ *      owner's entries in front of and behind the view's keep their bytes.  Out of place C receives A's pattern -- the
+ *      offsets rebased to 0, col_ids copied bit for bit -- under the ownership rule of speck_scale_* / speck_select_*.
+ *  Refused before anything runs, SPECK_ERR_INVALID: NULL A or p; NULL row_offsets with rows > 0; NULL d_U or d_V with
+ *      nnz > 0 and k > 0; NULL col_ids with nnz > 0 and (k > 0 or C != NULL); NULL data with nnz > 0 unless the call is
+ *      out of place, AXPBY and beta == 0; an unknown mode; alpha or beta NaN; ldu < k or ldv < k; nnz > 0 with rows == 0
+ *      or cols == 0; the span [d_U, d_U + (rows - 1) ldu + k) or [d_V, d_V + (cols - 1) ldv + k), padding inside
+ *      included, containing one of A's or C's three pointers (a span that ENDS at such a pointer is served); C sharing a
+ *      buffer with A.  SPECK_ERR_DIM_LIMIT: k > SPECK_SDDMM_MAX_K; ldu or ldv > 2^32; rows or cols > 2^27.
+ *      SPECK_ERR_NNZ_OVERFLOW: nnz >= 2^32.  rows == 0 or nnz == 0 is valid.
+ *  Refused on the device, SPECK_ERR_INVALID: offsets descending, leaving [row_offsets[0], row_offsets[0] + nnz], or a last
+ *      offset that is not row_offsets[0] + nnz; a column id >= cols.
+ *  On any error NOTHING is written: not A->data, not C's buffers, not C's struct (*info is zero once the arguments have
+ *      passed).  No offset or id is used as an address before it was checked: in-place output cannot wait in a temporary,
+ *      so a checking pass over the offsets and ALL the ids raises its verdict in a status block, the kernels that write are
+ *      queued behind it and do nothing where it is raised, and the host reads the status ONCE, at the end.
+ *  Config stream, cfg == NULL, grow-only temporaries of the config's own (not the multiply's arena) and the guard_bytes
+ *      canary zones: all as speck_scale_*.
+ *  The entries are walked in tiles of SPECK_SDDMM_TILE_ENTRIES, aligned to absolute positions as the reduction's; one path
+ *      for every row length.  The ids are loaded 16 bytes at a time where col_ids (and C's) lie on 16-byte boundaries,
+ *      one by one elsewhere, with the same results.
+ *  Not built: U^T / column-major or float blocks; a softmax or another map fused behind the dot; the product fused into
+ *      speck_multiply_masked_*. ---- */
+#define SPECK_SDDMM_MAX_K 1024            /* = SPECK_SPMM_MAX_RHS */
+#define SPECK_SDDMM_TILE_ENTRIES 4096
+enum { SPECK_SDDMM_AXPBY = 0, SPECK_SDDMM_HADAMARD = 1 };
+typedef struct speck_sddmm_params {
+    uint32_t mode;                /* SPECK_SDDMM_* */
+    uint32_t k;
+    double alpha, beta;
+    const double *d_U;            /* DEVICE, rows x k row-major, indexed by the row INSIDE A (a view offsets the pointer) */
+    uint64_t ldu;
+    const double *d_V;            /* DEVICE, cols x k row-major, indexed by the column id */
+    uint64_t ldv;
+} speck_sddmm_params;
+typedef struct speck_sddmm_info {
+    uint64_t entries;             /* entries written = nnz */
+    uint64_t terms;               /* products formed = entries * k */
+    uint64_t nonfinite;           /* results that, after rounding to T, are inf or NaN */
+    uint64_t tiles;               /* entry tiles walked */
+    uint64_t lanes;               /* L(k) */
+} speck_sddmm_info;
+int speck_sddmm_f64(speck_config *cfg, const speck_dcsr *A, const speck_sddmm_params *p, speck_dcsr *C /* NULL: in place */,
+                    speck_sddmm_info *info /* may be NULL */);
+int speck_sddmm_f32(speck_config *cfg, const speck_dcsr *A, const speck_sddmm_params *p, speck_dcsr *C,
+                    speck_sddmm_info *info);
+
 /* ---- row-sharded multi-GPU (new: the reference is single-GPU, source/Executor.cpp:25).  One process per GPU;
  *      rank p multiplies the row range [b_p, b_{p+1}) of A (a view with absolute offsets, boundaries from
  *      speck_partition_rows) with a replicated B, then ONE exchange concatenates the shards on a root rank:

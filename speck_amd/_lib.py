@@ -97,6 +97,18 @@ class CSpmmInfo(C.Structure):
                 ("terms", C.c_uint64)]
 
 
+class CSddmmParams(C.Structure):
+    # include/speck_c_api.h: speck_sddmm_params
+    _fields_ = [("mode", C.c_uint32), ("k", C.c_uint32), ("alpha", C.c_double), ("beta", C.c_double),
+                ("d_U", C.c_void_p), ("ldu", C.c_uint64), ("d_V", C.c_void_p), ("ldv", C.c_uint64)]
+
+
+class CSddmmInfo(C.Structure):
+    # include/speck_c_api.h: speck_sddmm_info
+    _fields_ = [("entries", C.c_uint64), ("terms", C.c_uint64), ("nonfinite", C.c_uint64), ("tiles", C.c_uint64),
+                ("lanes", C.c_uint64)]
+
+
 # every symbol include/speck_c_api.h declares, with its ctypes signature
 _P = C.POINTER
 _SIGS = {
@@ -144,6 +156,8 @@ _SIGS = {
                                  C.c_uint64, _P(CSpmmInfo)]),
     "speck_spmm_f32": (C.c_int, [C.c_void_p, C.c_double, _P(DCsr), C.c_void_p, C.c_uint64, C.c_uint32, C.c_double, C.c_void_p,
                                  C.c_uint64, _P(CSpmmInfo)]),
+    "speck_sddmm_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(CSddmmParams), _P(DCsr), _P(CSddmmInfo)]),
+    "speck_sddmm_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(CSddmmParams), _P(DCsr), _P(CSddmmInfo)]),
     "speck_compare_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), C.c_int, C.c_double, _P(C.c_uint64)]),
     "speck_compare_bounded_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), _P(DCsr), C.c_double, _P(C.c_uint64),
                                             _P(C.c_uint64)]),

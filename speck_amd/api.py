@@ -794,10 +794,10 @@ class SpmmInfo(_Info):
     _fields = ("rows_empty", "rows_split", "tiles", "entries", "terms")
 
 
-def _device_block(v, n, k, ld, what):
+def _device_block(v, n, k, ld, what, op="spmm"):
     """(address, k, ld) of a row-major n x k block of float64: a device address with k and ld given, or a 2-D object with
     data_ptr(), shape, stride() and dtype (a torch tensor, a column slice of one) checked"""
-    who = f"spmm: {what}"
+    who = f"{op}: {what}"
     if hasattr(v, "data_ptr"):
         if not all(hasattr(v, a) for a in ("shape", "stride", "dtype")):
             raise ValueError(f"{who} must have shape, stride() and dtype beside data_ptr()")
@@ -849,3 +849,70 @@ def spmm(A, X, config, alpha=1.0, beta=0.0, Y=None, k=None, ldx=None, ldy=None):
     _check(fn(config._h if config is not None else None, float(alpha), C.byref(A._c), x_ptr, ldx, k, float(beta), y_ptr, ldy,
               C.byref(info)), "spmm")
     return (_download_f64(buf, A.rows * k, "spmm").reshape(A.rows, k) if buf is not None else None), SpmmInfo(info)
+
+
+# include/speck_c_api.h: SPECK_SDDMM_*; the most columns U and V may have, and the entries of a tile of the pass
+SDDMM_AXPBY, SDDMM_HADAMARD = range(2)
+SDDMM_MODES = {"axpby": SDDMM_AXPBY, "hadamard": SDDMM_HADAMARD}
+SDDMM_MAX_K = 1024
+SDDMM_TILE_ENTRIES = 4096
+
+
+def sddmm_lanes(k):
+    """L(k) of speck_sddmm_*: the lanes that serve one entry -- min(8, max(1, pow2ceil(ceil(k / 4))))"""
+    lanes = 1
+    while lanes < 8 and 4 * lanes < k:
+        lanes *= 2
+    return lanes
+
+
+class SddmmInfo(_Info):
+    """speck_sddmm_info: what the sampled product wrote (terms = entries * k, lanes = L(k))."""
+    _fields = ("entries", "terms", "nonfinite", "tiles", "lanes")
+
+
+def sddmm(A, U, V, config, alpha=1.0, beta=0.0, mode="axpby", matOut=None, inplace=False, k=None, ldu=None, ldv=None):
+    """C = alpha (U V^T) on A's pattern + beta A (speck_sddmm_f64 / _f32): d(i,j) = sum_c U(i,c) V(j,c) only where A holds
+    an entry.  mode "hadamard" gives alpha d(i,j) A(i,j) instead (beta must be 0).  U (A.rows x k, indexed by the row inside
+    A: for a row_view pass the slice) and V (A.cols x k) are row-major device blocks of float64 for both value types, as
+    spmm takes them: a 2-D object with data_ptr(), shape, stride() and dtype, or a device address with k (and ldu / ldv,
+    default k) given.  They are only read and may be one block.  Every step in double, the sum over k in a tree that is a
+    function of k alone (sddmm_lanes), one rounding to A's value type: the same bits from run to run, in place or not,
+    whatever the leading dimensions.  beta == 0 does not read A's values (a NaN there does not survive); a NaN or 0 * inf
+    of U or V lands in exactly the entries that reference it and is counted in info.nonfinite.  The gradient of spmm
+    with respect to A's values is sddmm(A, dY, X).  inplace=True overwrites A's values (on a row_view: the view's
+    entries only); otherwise the result goes to matOut (a new matrix when None) with A's pattern, offsets rebased to 0.
+    config may be None.  Returns (matOut or A, SddmmInfo)."""
+    if isinstance(mode, str):
+        if mode not in SDDMM_MODES:
+            raise ValueError(f"sddmm: unknown mode {mode!r} (one of {', '.join(SDDMM_MODES)})")
+        mode = SDDMM_MODES[mode]
+    elif mode not in SDDMM_MODES.values():
+        raise ValueError(f"sddmm: unknown mode {mode!r}")
+    if mode == SDDMM_HADAMARD and float(beta) != 0.0:
+        raise ValueError("sddmm: beta must be 0 with mode 'hadamard'")
+    if inplace and matOut is not None:
+        raise ValueError("sddmm: inplace=True and matOut exclude each other")
+    p = _lib.CSddmmParams()
+    p.mode, p.alpha, p.beta = int(mode), float(alpha), float(beta)
+    p.d_U, k, p.ldu = _device_block(U, A.rows, k, ldu, "U", "sddmm")
+    p.d_V, k, p.ldv = _device_block(V, A.cols, k, ldv, "V", "sddmm")
+    if k < 0 or p.ldu < k or p.ldv < k:
+        raise ValueError(f"sddmm: k = {k} with ldu = {p.ldu}, ldv = {p.ldv}: a leading dimension is at least k >= 0")
+    p.k = k
+    L = _lib.load()
+    fn = L.speck_sddmm_f32 if A.dtype == np.float32 else L.speck_sddmm_f64
+    info = _lib.CSddmmInfo()
+    h = config._h if config is not None else None
+    if inplace:
+        _check(fn(h, C.byref(A._c), C.byref(p), None, C.byref(info)), "sddmm")
+        return A, SddmmInfo(info)
+    if matOut is None:
+        matOut = dCSR(A.dtype)
+    if matOut.dtype != A.dtype:
+        matOut.reset()
+        matOut.dtype = A.dtype
+    _check(fn(h, C.byref(A._c), C.byref(p), C.byref(matOut._c), C.byref(info)), "sddmm")
+    ro = A._host_row_offsets   # (C's offsets are A's, from 0: the host copy is shared where A's start there)
+    matOut._host_row_offsets = ro if ro is None or ro[0] == 0 else (ro - ro[0]).astype(np.uint32)
+    return matOut, SddmmInfo(info)

@@ -227,6 +227,7 @@ struct speck_config {
     ScaleScratch scale;  // ... and of speck_scale_* (scale.hip)
     TileScratch spmv;  // ... and of speck_spmv_* (spmv.hip)
     TileScratch spmm;  // ... and of speck_spmm_* (spmm.hip): its own, a spmv after a wide spmm keeps its small buffers
+    ScaleScratch sddmm;  // ... and of speck_sddmm_* (sddmm.hip): scale's pair of buffers, its own
     const void* zones_arena = nullptr;
     u64 zones_m = 0, zones_nnz = 0, zones_gap = 0;
     bool gpool_zones_filled = false;
@@ -1921,6 +1922,7 @@ TileScratch* reduce_scratch(speck_config* c) { return &c->reduce; }
 ScaleScratch* scale_scratch(speck_config* c) { return &c->scale; }
 TileScratch* spmv_scratch(speck_config* c) { return &c->spmv; }
 TileScratch* spmm_scratch(speck_config* c) { return &c->spmm; }
+ScaleScratch* sddmm_scratch(speck_config* c) { return &c->sddmm; }
 }  // namespace speck
 
 extern "C" {
@@ -2041,6 +2043,7 @@ int speck_config_destroy(speck_config* c)
     c->scale.release();
     c->spmv.release();
     c->spmm.release();
+    c->sddmm.release();
     if (c->pred.off) (void)guarded_free(c->pred.off);
     if (c->gpred.off) (void)guarded_free(c->gpred.off);
     if (c->d_stats) (void)hipFree(c->d_stats);
@@ -2129,6 +2132,7 @@ int speck_config_set_option(speck_config* c, const char* name, int64_t value)
         c->scale.release();
         c->spmv.release();
         c->spmm.release();
+        c->sddmm.release();
     }
     else if (n == "sort_reg_max") c->sort.reg_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_REG_MAX);
     else if (n == "sort_lds_max") c->sort.lds_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_LDS_MAX);

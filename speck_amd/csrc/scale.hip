@@ -2,7 +2,7 @@
 // place or into a new C; g is the identity, |v|, v v or 1.  Every step in double, one rounding to T.  The one map from a
 // device vector back into a matrix (reduce.hip is the way out).  The reference has no counterpart.
 //
-//   scale_check_kernel    two kinds of workgroups in one launch.  A thread per row: the offsets ascend, stay inside
+//   scale_check_kernel    (scale.hpp: sddmm.hip queues it too) two kinds of workgroups in one launch.  A thread per row: the offsets ascend, stay inside
 //                         [row_offsets[0], row_offsets[0] + nnz] and the last one spans nnz (entry_tiles.hpp, the check the
 //                         reduction makes); with a row vector a row also tells every entry tile the rows of its first and
 //                         last entry.  Where col_ids is read at all (a column vector, or a new C): a stream over the ids,
@@ -20,7 +20,7 @@
 //                         so thousands of them between two tiles, a tile inside one row and a tile of 4096 rows are one
 //                         case.  l[i] is loaded where the row changes, not per entry.  Two forms: with the column ids
 //                         (a column vector, a new C) and without (none held in registers: one more wave per SIMD).
-//   scale_offsets_kernel  a new C only: its row offsets, rebased to 0.
+//   scale_offsets_kernel  (scale.hpp) a new C only: its row offsets, rebased to 0.
 // Every entry is written once by one thread; `nonfinite` is an integer counter (one atomic per workgroup).  No kernel
 // uses scratch.  The host side is the side operations' own (side_call.hpp, compact.hpp: C by the multiply's rule).
 #include <hip/hip_runtime.h>
@@ -44,15 +44,9 @@ namespace {
 
 constexpr u32 kTile = SPECK_SCALE_TILE_ENTRIES, kThreads = 256, kPer = kTile / kThreads;
 static_assert(kPer == 16, "a thread's row-start bits are half a word of the bitmap");
+static_assert(kTile == kScaleTile && kThreads == kScaleThreads, "the checking pass of scale.hpp");
 constexpr u32 kSteps = 4;            // 16-byte chunks a lane of the stream has in flight
 constexpr u32 kStreamBlocks = 2048;  // ... and its grid at most (8 workgroups per CU; it strides over the rest)
-constexpr u32 kColBlocks = 1024, kColUnroll = 4;
-
-struct ScaleStatus {
-    u32 invalid;  // the offsets, a column id
-    u32 base;     // row_offsets[0]
-    unsigned long long nonfinite;
-};
 
 template <typename T>
 struct ScaleArgs {
@@ -92,36 +86,6 @@ __device__ __forceinline__ T scaled_entry(const ScaleArgs<T>& g, T a, double l, 
     const T y = (T)x;
     nonfinite += !__builtin_isfinite(y);
     return y;
-}
-
-// ------------------------------------------------------------------------------------------------ check
-__global__ __launch_bounds__(kThreads) void scale_check_kernel(const u32* __restrict__ ro, const u32* __restrict__ col, u32 rows,
-                                                               u32 cols, u64 nnz, u32 row_blocks, u32 max_tiles,
-                                                               u32* __restrict__ tile_rows, ScaleStatus* st)
-{
-    SPECK_POISON();
-    const u32 base = ro[0];
-    if (blockIdx.x < row_blocks) {
-        const u32 r = blockIdx.x * kThreads + threadIdx.x;
-        if (r == 0) st->base = base;
-        bool empty;
-        if (r < rows && !row_offsets_sound<kTile>(ro, r, rows, base, nnz, max_tiles, tile_rows, &empty)) st->invalid = 1;
-    } else {
-        // the ids of the entries [base, base + nnz), a batch of loads per trip (compared, never followed)
-        const u64 stride = u64(gridDim.x - row_blocks) * kThreads * kColUnroll;
-        bool bad = false;
-        for (u64 b = u64(blockIdx.x - row_blocks) * kThreads * kColUnroll; b < nnz; b += stride) {
-            u32 c[kColUnroll];
-#pragma unroll
-            for (u32 k = 0; k < kColUnroll; ++k) {
-                const u64 i = b + k * kThreads + threadIdx.x;
-                c[k] = i < nnz ? col[u64(base) + i] : 0u;
-            }
-#pragma unroll
-            for (u32 k = 0; k < kColUnroll; ++k) bad |= b + k * kThreads + threadIdx.x < nnz && c[k] >= cols;
-        }
-        if (bad) st->invalid = 1;
-    }
 }
 
 // ------------------------------------------------------------------------------------------------ no row vector
@@ -305,16 +269,6 @@ __global__ __launch_bounds__(kThreads) void scale_tile_kernel(const ScaleArgs<T>
     block_counter_to(&g.st->nonfinite, bad, &s_count);
 }
 
-// ------------------------------------------------------------------------------------------------ C's offsets
-__global__ __launch_bounds__(kThreads) void scale_offsets_kernel(const u32* __restrict__ ro, u32 rows, u32* __restrict__ c_ro,
-                                                                 const ScaleStatus* st)
-{
-    SPECK_POISON();
-    if (st->invalid) return;
-    const u32 r = blockIdx.x * kThreads + threadIdx.x;
-    if (r <= rows) c_ro[r] = ro[r] - st->base;
-}
-
 // ------------------------------------------------------------------------------------------------ host
 template <typename T>
 int scale_run(ScaleScratch* sc, hipStream_t s, const speck_dcsr* A, const speck_scale_params* p, speck_dcsr* C,
@@ -341,10 +295,7 @@ int scale_run(ScaleScratch* sc, hipStream_t s, const speck_dcsr* A, const speck_
     u32* tile_rows = max_tiles ? static_cast<u32*>(sc->var.p) : nullptr;
 
     HIP_TRY(hipMemsetAsync(st, 0, sizeof(ScaleStatus), s));
-    const u32 row_blocks = (rows + kThreads - 1) / kThreads;
-    const u32 col_blocks = need_col && nnz ? grid_of((nnz + kThreads * kColUnroll - 1) / (kThreads * kColUnroll), kColBlocks) : 0u;
-    SPECK_LAUNCH(scale_check_kernel, dim3(row_blocks + col_blocks), dim3(kThreads), 0, s, A->row_offsets, A->col_ids, rows,
-                 (u32)A->cols, nnz, row_blocks, max_tiles, tile_rows, st);
+    launch_scale_check(s, A, need_col, max_tiles, tile_rows, st);
     if (nnz) {
         T* dst = C ? static_cast<T*>(out->val) : static_cast<T*>(A->data);
         const bool aligned = on_16_bytes(A->data) && (!need_col || on_16_bytes(A->col_ids)) && on_16_bytes(dst) &&
@@ -360,7 +311,7 @@ int scale_run(ScaleScratch* sc, hipStream_t s, const speck_dcsr* A, const speck_
                          dim3(kThreads), 0, s, g);
         }
     }
-    if (C) SPECK_LAUNCH(scale_offsets_kernel, dim3(rows / kThreads + 1), dim3(kThreads), 0, s, A->row_offsets, rows, out->ro, st);
+    if (C) launch_scale_offsets(s, A, out->ro, st);
     // the ONE read-back of the call: the verdict, the base, the counter
     ScaleStatus h{};
     rc = read_status(s, st, &h);
