@@ -106,6 +106,22 @@ struct ReplayPlan {
     u32 nf_wcols;
 };
 
+// What the last COMPLETE call on a config left for the next call to be sized from and for a reuse sequence to be planned
+// from.  Written by Call::remember_call (a hash one-walk or through call that held refreshes the figures it was chosen by).
+struct LastCall {
+    bool valid = false;          // such a call has completed ...
+    u64 rows_a = 0, rows_b = 0;  // ... on inputs of these shapes
+    u32 sym_counts[kMaxClasses] = {}, num_counts[kMaxClasses] = {};  // rows per class
+    u32 sym_mask = 0, num_mask = 0;                                  // ... and the classes with rows
+    u32 max_row_nnz = 0, max_row_ops = 0;  // its longest row of C, its longest row in products
+    u64 g_products = 0;          // what the spill pools were sized for
+    u64 nf_entries = 0;          // scratch-pool entries its analysis counted
+    bool was_walk = false;       // it was a one-walk call (its nf_entries count the register-class slots too)
+    DeviceStats eager_stats{};   // its final statistics block (what `pred` goes with)
+    // a complete call of these shapes has run on the config
+    bool ran_on(const speck_dcsr* A, const speck_dcsr* B) const { return valid && rows_a == A->rows && rows_b == B->rows; }
+};
+
 struct speck_config {
     int device = 0;
     int sm = 0;                 // compute units
@@ -145,15 +161,13 @@ struct speck_config {
                                   //   its symbolic phase (grids, launched classes, scratch pool, numeric-first window) from
                                   //   THAT call and runs analysis .. scan as one batch -- one read-back instead of two; the
                                   //   device checks every assumption (capacity_miss: the two-read-back sequence re-runs)
-    bool spec_valid = false;      // such a call has completed (last_sym_* describe it)
     // option eager_through: ... and when matOut already holds buffers of the size that call produced, the numeric launches are
     // queued right behind the scan -- no read-back in the middle of the call.  The scan checks on the device what the host
     // would have (nnz(C) = what the buffers hold, the classes with rows, the spill pool, the verdict of the input check: its
     // stream is joined in front of the scan); on a miss nothing of C is written and the call re-runs with its read-back.
     bool eager_through = true;
     hipEvent_t vdone = nullptr;         // the input check's stream, joined in front of that scan
-    u64 through_hits = 0, through_misses = 0;
-    u64 spec_rows_a = 0, spec_rows_b = 0;
+    int through_hits = 0, through_misses = 0;
     int eager_spec_hits = 0, eager_spec_misses = 0;
     bool validate_inputs = true;  // complete call: B's rows strictly ascending and in range
     bool concurrent_classes = true;
@@ -165,15 +179,13 @@ struct speck_config {
                               //   the small-row launch on the mac_econ stand-in for bit 3 -- that launch is bound by
                               //   its gathers of B rows since it sorts in registers; bits 0 and 2 lose to load
                               //   imbalance)
-    u32 last_sym_counts[kMaxClasses] = {}, last_num_counts[kMaxClasses] = {};
+    LastCall prev;  // what the last complete call left (above)
 
     // the reuse sequence of the last repeated call (option "reuse")
     bool reuse = true;
     bool plan_valid = false;
     CallKey plan_key;
-    u32 last_sym_mask = 0, last_num_mask = 0;  // non-empty classes of the last complete call
-    u32 last_max_row_nnz = 0;                  // ... and its longest C row
-    CallKey last_key;                         // ... and what it ran on
+    CallKey last_key;                         // what the last complete call ran on
     bool last_key_valid = false;
     int replays = 0, plans_made = 0, replay_misses = 0;
     void* gpool = nullptr;    // global-memory buffers of the NUM_G spill path, carved into `spill`
@@ -184,7 +196,6 @@ struct speck_config {
     size_t nf_pool_max_bytes = 0;  // 0: half of the free device memory at allocation time
     int pool_fallbacks = 0;        // times a scratch-pool class was switched off because the pool did not fit
     Prediction pred, gpred;
-    DeviceStats last_eager_stats{};  // final statistics block of the last complete call (what `pred` goes with)
     bool pred_valid = false;         // pred.off holds the offsets of the last complete call
     bool nf_direct = true;           // option nf_direct: a reuse sequence places its numeric-first rows directly
     bool esc_fused = true;           // option esc_fused: such a sequence finishes the rows of the register classes in
@@ -215,7 +226,6 @@ struct speck_config {
     bool arena_key_valid = false;    //   class table) was last written for -- by a multiply that COMPLETED
     u32 nf_wcols = kNumD1Cols;  // LDS window of the numeric-first kernel: the widest such row of the last analysis
     SpillBuffers spill{};
-    u64 last_g_products = 0;  // what the spill pools of the reuse sequence were sized for
     // debug option guard_bytes (guards.hpp): the zones between the regions carved from the arena / the spill pool, and what
     // layout the arena's were last filled for
     std::vector<GuardZone> arena_zones, gpool_zones, nfpool_zones;
@@ -237,8 +247,6 @@ struct speck_config {
     // allocated (the caller's matOut of the previous call) and the class counts of the previous complete call for grids.
     int one_walk = 0;                // option: 0 never (default: measured and lost on every stand-in but cant),
                                      //   1 when the previous call says the walk kernel takes a good share of the rows, 2 whenever possible
-    bool last_was_walk = false;      // the last complete call was one (its nf_entries count the register-class slots too)
-    u64 last_nf_entries = 0;         // scratch-pool entries the last complete call's analysis counted
     int walks = 0, walk_misses = 0;
     // ... and of the HASH classes (numeric.hip, walk_hash_kernel; option one_walk_hash): inputs whose rows all fit the 256-entry
     // sub-wave table (the previous complete call says so) -- analysis -> walk_hash_kernel -> done
@@ -247,7 +255,6 @@ struct speck_config {
     void* chain3_buf = nullptr;      // three-level chain of that kernel (chain3.hpp): grow-only
     size_t chain3_cap_words = 0;
     u64 chain3_launches = 0;
-    u32 last_max_row_ops = 0;        // longest row (products) of the last complete call
 };
 
 namespace {
@@ -1024,11 +1031,11 @@ int snapshot_prediction(speck_config* c, hipStream_t s)
 ReplayPlan plan_replay(const speck_config* c, bool arena_mine, bool arena_replay_ok)
 {
     ReplayPlan p;
-    p.num_mask = c->last_num_mask;
-    std::memcpy(p.num_counts, c->last_num_counts, sizeof(p.num_counts));
-    p.sym_mask = c->last_sym_mask;
-    std::memcpy(p.sym_counts, c->last_sym_counts, sizeof(p.sym_counts));
-    p.g_products = c->last_g_products;
+    p.num_mask = c->prev.num_mask;
+    std::memcpy(p.num_counts, c->prev.num_counts, sizeof(p.num_counts));
+    p.sym_mask = c->prev.sym_mask;
+    std::memcpy(p.sym_counts, c->prev.sym_counts, sizeof(p.sym_counts));
+    p.g_products = c->prev.g_products;
     p.nf_cap_entries = c->nf_cap_entries;
     p.nf_wcols = c->nf_wcols;
     // Numeric-first rows: a complete call writes them to scratch slots and copies them after the scan (nothing else
@@ -1056,7 +1063,7 @@ ReplayPlan plan_replay(const speck_config* c, bool arena_mine, bool arena_replay
     // (on the library's own pipeline stream only: beside a CALLER's stream the verifier would not be ordered behind the
     //  work that produces the inputs there; rows that take a scratch slot keep the writing analysis)
     p.overlap = c->overlap_analysis && arena_mine && c->pred_valid && c->vstream != nullptr && !c->use_user_stream &&
-                !(c->last_sym_mask >> SYM_GH & 1u) && (!(c->last_sym_mask >> SYM_NF & 1u) || p.direct) &&
+                !(c->prev.sym_mask >> SYM_GH & 1u) && (!(c->prev.sym_mask >> SYM_NF & 1u) || p.direct) &&
                 (p.direct || !(p.num_mask >> NUM_NFCOPY & 1u));
     // ... and when the arena was last written by a replay of THIS sequence, its scan has nothing left to do either: the
     // offsets, classes, records and lists it would produce are a function of the rows' nnz and of the analysis' quantities
@@ -1081,10 +1088,10 @@ ReplayPlan plan_replay(const speck_config* c, bool arena_mine, bool arena_replay
     return p;
 }
 
-// front + back + ticket of a reuse sequence, straight onto the stream (with `tm`: HIP events around the launches)
+// front + back + ticket of a reuse sequence, straight onto the stream
 template <typename T>
 int enqueue_replay(speck_config* c, hipStream_t s, const speck_dcsr* A, const speck_dcsr* B, const speck_dcsr* C,
-                   const Scratch& sc, const ReplayPlan& p, Timing* tm, size_t* ev_num_end)
+                   const Scratch& sc, const ReplayPlan& p)
 {
     CallForm f;
     f.fused = p.fused, f.direct = p.direct, f.overlap = p.overlap, f.skip_scan = p.skip_scan;
@@ -1108,18 +1115,10 @@ int enqueue_replay(speck_config* c, hipStream_t s, const speck_dcsr* A, const sp
         for (int k = 0; k < kMaxClasses; ++k)
             if (!(kSymEscMask >> k & 1u)) sym_counts[k] = 0;
     }
-    int rc = enqueue_front(c, s, A, B, sc, (u32)sizeof(T), f, a, tm);
+    int rc = enqueue_front(c, s, A, B, sc, (u32)sizeof(T), f, a, nullptr);
     if (rc != SPECK_OK) return rc;
-    if (tm) {
-        tm->ev_num = tm->ev;
-        (void)hipEventRecord(kernel_event(c, tm->ev++), s);
-    }
-    rc = enqueue_back<T>(c, s, A, B, sc, f, C->col_ids, static_cast<T*>(C->data), p.launch_mask, p.num_counts, tm);
+    rc = enqueue_back<T>(c, s, A, B, sc, f, C->col_ids, static_cast<T*>(C->data), p.launch_mask, p.num_counts, nullptr);
     if (rc != SPECK_OK) return rc;
-    if (tm) {
-        *ev_num_end = tm->ev;
-        (void)hipEventRecord(kernel_event(c, tm->ev++), s);
-    }
     // the last kernel mirrors the (final) statistics block into pinned host memory, then stores the completion ticket
     launch_done(s, c->d_ticket, c->h_ticket_dev, c->d_stats, c->h_stats_dev);
     return SPECK_OK;
@@ -1281,35 +1280,117 @@ u32 speculated_hints(const speck_config* c, u32 (&hints)[kMaxClasses])
 {
     u32 mask = kSymLightMask;
     for (int k = 0; k < kMaxClasses; ++k) {
-        hints[k] = c->last_sym_counts[k];
+        hints[k] = c->prev.sym_counts[k];
         if (hints[k]) mask |= 1u << k;
         if ((kSymLightMask >> k & 1u) && !hints[k]) hints[k] = 256;
     }
     return mask;
 }
 
-template <typename T>
-int multiply_impl(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, speck_dcsr* C,
-                  speck_timings* t)
-{
-    if (!c || !C) return SPECK_ERR_INVALID;
-    int rc = check_inputs(A, B);
-    if (rc != SPECK_OK) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    speck_timings local_t{};
-    if (!t) t = &local_t;
-    c->last = speck_stats{};
+// How an attempt at one kind of call ended, beside its status code
+enum class Attempt {
+    not_tried,     // its conditions do not hold: nothing was enqueued
+    done,          // the call is complete
+    missed,        // the device objected and nothing of C was written: the next kind starts over
+    front_stands,  // through call only: the scan alone objected -- analysis .. scan stand, the call goes on behind them
+};
 
-    // reference: source/GPU/Multiply.cu:67-70
-    if (A->nnz == 0 || B->nnz == 0) {
-        C->nnz = 0;
+// One multiply in flight: what every kind of call needs.  Built on the stack by multiply_impl and gone with the call --
+// with it the row offsets the call allocated, unless C has taken them.  The kinds are tried in the order of the
+// declarations below (multiply_impl).
+template <typename T>
+struct Call {
+    speck_config* const c;
+    const speck_dcsr *const A, *const B;
+    speck_dcsr* const C;
+    speck_timings* const t;
+    const hipStream_t s;
+    const u32 m;
+    Scratch sc{};
+    // The input check -- B's rows strictly ascending and in range: one coalesced pass over B.col_ids -- runs BESIDE the
+    // call on the verifier's stream; its verdict is looked at with the statistics of the scan, before anything of C is
+    // written.  Until then the kernels stay inside their tables and windows whatever B holds (a requirement for every
+    // kernel body: DESIGN.md 1).  A's column ids are checked -- and clamped -- by the analysis.
+    // (launched BEHIND the analysis of the call, not in front of it: enqueue_front starts it)
+    InputCheck check;
+    Timing tm;
+    StageTimer st;
+    const bool c_ready;        // C holds buffers for a product of A's row count
+    // what this call leaves behind for a repeated identical call: its row offsets, written by the scan kernel next to its
+    // other outputs.  No room on the device: that call places nothing early.
+    bool keep_pred = false;
+    u32* pred_out = nullptr;
+    bool early_stats = false;  // the scan mirrors the statistics and stores the ticket itself: await_scan_stats
+    u32 num_mask = 0;          // numeric classes with rows, once the host knows them
+    size_t ev_num_end = 0;
+    u32* c_ro = nullptr;       // the row offsets of C ...
+    bool own_ro = false;       // ... allocated by this call and not yet C's
+
+    Call(speck_config* c_, const speck_dcsr* A_, const speck_dcsr* B_, speck_dcsr* C_, speck_timings* t_, hipStream_t s_)
+        : c(c_), A(A_), B(B_), C(C_), t(t_), s(s_), m((u32)A_->rows), check{c_, B_, s_}, st(c_, t_->measureAll != 0, s_),
+          c_ready(C_->rows == A_->rows && C_->row_offsets && C_->col_ids && C_->data && C_->nnz > 0) {}
+    ~Call() { if (own_ro) (void)guarded_free(c_ro); }
+    // C holds usable buffers whose size fits 32 bits: an attempt may write the product into them
+    bool c_usable() const { return c_ready && C->nnz <= 0xFFFFFFFFull; }
+    // a form of this call: the config's numeric-first window as it is NOW, the input check behind the analysis
+    CallForm form()
+    {
+        CallForm f;
+        f.nf_wcols = c->nf_wcols, f.after_analysis = &check;
+        return f;
+    }
+    int front(const CallForm& f, const FrontArgs& a) { return enqueue_front(c, s, A, B, sc, (u32)sizeof(T), f, a, &tm); }
+    int back(const CallForm& f, u32* c_col, void* c_val, u32 mask, const u32* counts)
+    {
+        return enqueue_back<T>(c, s, A, B, sc, f, c_col, static_cast<T*>(c_val), mask, counts, &tm);
+    }
+    // parts of the front of a plain two-phase call (the offsets go to scratch: C.row_offsets -- possibly the caller's
+    // reused buffer -- is written only once nothing can fail any more)
+    int plain_front(u32 parts, const u32* sym_known)
+    {
+        FrontArgs a;
+        a.parts = parts, a.sym_hint = parts == 2u ? sym_known : nullptr;
+        a.host_mirror = early_stats ? c->h_stats_dev : nullptr, a.pred_off_out = pred_out;
+        return front(form(), a);
+    }
+    // the statistics of a front's scan on the host, then what the call says of its inputs
+    int await_front() { const int rc = early_stats ? await_scan_stats(c, s) : read_stats(c, s); return rc == SPECK_OK ? input_verdict(c) : rc; }
+    // the numeric launches of a call between their two profiling events
+    template <typename F>
+    int timed_numeric(F&& enqueue)
+    {
+        if (c->profile_kernels) {
+            tm.ev_num = tm.ev;
+            (void)hipEventRecord(kernel_event(c, tm.ev++), s);
+        }
+        const int rc = enqueue();
+        if (rc != SPECK_OK) return rc;
+        ev_num_end = tm.ev;
+        if (c->profile_kernels) (void)hipEventRecord(kernel_event(c, tm.ev++), s);
         return SPECK_OK;
     }
-    const u32 m = (u32)A->rows;
-    hipStream_t s = main_stream(c);
-
-    if (t->measureCompleteTime) HIP_TRY(hipEventRecord(c->completeStart, s));
-    auto finish_complete = [&]() -> int {
+    // The settle step of a batch that wrote into the caller's buffers on the strength of the previous complete call: the
+    // statistics (done_kernel + ticket: the one wait of the call), the verdict on the inputs (a B that fails the check:
+    // the device saw the verdict, nothing of C was written), whether the speculation held -- counted
+    int settle_batch(int& hits, int& misses, bool* held)
+    {
+        int rc = read_stats(c, s);
+        if (rc == SPECK_OK) rc = input_verdict(c);
+        if (rc != SPECK_OK) return rc;
+        *held = speculation_held(c->h_stats, C->nnz);
+        ++(*held ? hits : misses);
+        return SPECK_OK;
+    }
+    // this attempt missed: the next one checks B again (the verdict word of the check was consumed)
+    int miss(Attempt& how, bool forget_events)
+    {
+        check.started = false;
+        if (forget_events) tm = Timing{};
+        how = Attempt::missed;
+        return SPECK_OK;
+    }
+    int finish_complete()
+    {
         if (t->measureCompleteTime) {
             // reference: cudaDeviceSynchronize + complete event, Multiply.cu:1082-1085
             HIP_TRY(hipEventRecord(c->completeEnd, s));
@@ -1317,34 +1398,14 @@ int multiply_impl(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, spe
             HIP_TRY(hipEventElapsedTime(&t->complete, c->completeStart, c->completeEnd));
         }
         return SPECK_OK;
-    };
-    StageTimer st(c, t->measureAll != 0, s);
-    struct RestoreFlag {
-        int& flag;
-        int value;
-        ~RestoreFlag() { flag = value; }
-    } restore_profile{c->profile_kernels, c->profile_kernels};
-    if (t->measureAll) c->profile_kernels = 1;  // per-stage times come from per-launch events
-
-    rc = ensure_arena(c, scratch_bytes(m, A->nnz));
-    if (rc != SPECK_OK) return rc;
-    std::vector<GuardZone> carved;
-    Scratch sc = carve(c, m, A->nnz, guard_bytes() ? &carved : nullptr);
-    if (guard_bytes() && (c->zones_arena != c->arena || c->zones_m != m || c->zones_nnz != A->nnz || c->zones_gap != guard_bytes())) {
-        // (another layout of the arena than the one whose zones were filled last: canaries between ITS regions)
-        HIP_TRY(guard_fill(carved, s));
-        c->arena_zones = carved;
-        c->zones_arena = c->arena, c->zones_m = m, c->zones_nnz = A->nnz, c->zones_gap = guard_bytes();
     }
-    c->snap_pending = false;
-    if (c->verify_inputs && c->overlap_analysis && c->reuse) ensure_snap(c, A->nnz, B->rows);
-    VerifierGuard verifier_guard{c};
 
-    // ------------------------------------------------------------------ reuse path (option "reuse")
-    // Same buffers as the previous call, C already allocated for the expected nnz: the sequence that places rows where
-    // that call put them (plan_replay).  The device checks every assumption; on a miss the complete call below re-runs.
-    const bool c_ready = C->rows == A->rows && C->row_offsets && C->col_ids && C->data && C->nnz > 0;
-    if (c->reuse && c_ready && !c->profile_kernels && !t->measureAll) {
+    // ---- REUSE sequence (option "reuse").  Applies when C is allocated and nothing is being timed; runs when the call has the
+    // buffers of the previous call and C holds the expected nnz: the sequence that places rows where that call put them
+    // (plan_replay).  The device checks every assumption; on a miss the complete call re-runs.
+    int try_replay(Attempt& how)
+    {
+        if (!c->reuse || !c_ready || c->profile_kernels || t->measureAll) return SPECK_OK;
         const CallKey key = make_key<T>(c, A, B, C, s);
         const bool arena_mine = c->arena_key_valid && c->arena_key == key;
         const bool replay_layout = arena_mine && c->arena_from_replay;
@@ -1357,256 +1418,192 @@ int multiply_impl(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, spe
             c->plan_valid = have = true;
             ++c->plans_made;
         }
-        if (have) {
-            // A sequence whose analysis only VERIFIES reads the metadata the previous multiply of THIS problem left in the
-            // arena.  If something else has used the arena since (another problem on this config, a stage entry point) the
-            // same sequence runs with a writing analysis in front instead and leaves the arena as the next replay needs it.
-            ReplayPlan p = c->plan;
-            if ((p.overlap && !arena_mine) || (p.skip_scan && !replay_layout)) p.overlap = p.skip_scan = p.num_verify = false;
-            c->arena_key_valid = false;  // (until this call has completed)
-            // (a sequence with its own analysis: the input check of B alone, beside it from its first launch on; one whose
-            //  numeric launches are the plain forms: the check FIRST -- they must not see a B that fails it)
-            bool b_first_bad = false;
-            if (!p.safe_numeric && !p.num_verify && c->validate_inputs) {
-                rc = begin_validate(c, B);
-                if (rc == SPECK_OK) rc = finish_validate(c, &b_first_bad);
-                if (rc != SPECK_OK) return rc;
-            } else if (!p.overlap && c->validate_inputs) {
-                rc = begin_validate(c, B);
-                if (rc != SPECK_OK) return rc;
-            }
-            if (!b_first_bad) {
-            rc = enqueue_replay<T>(c, s, A, B, C, sc, p, nullptr, nullptr);
-            if (rc != SPECK_OK) return rc;
-            // (behind the sequence, while it runs: the host would only spin otherwise)
-            if (p.overlap) {
-                rc = launch_verifier(c, A, B, sc);
-                if (rc != SPECK_OK) return rc;
-            }
-            // the last kernel of the sequence stores a ticket into pinned memory
-            rc = wait_ticket(c, s);
-            if (rc != SPECK_OK) return rc;
-            bool changed = false;
-            if (p.overlap) rc = wait_verifier(c, &changed);
-            else rc = finish_validate(c, &changed);
-            if (rc != SPECK_OK) return rc;
-            if (c->h_stats->chain_error) return chain_failed(c, s);
-            if (!changed && !c->h_stats->capacity_miss && !c->h_stats->nnz_overflow && c->h_stats->nnz_c == C->nnz) {
-                c->arena_key = key;
-                c->arena_key_valid = true;
-                c->arena_from_replay = true;
-                if (c->snap_pending) c->snap_for_arena = true;  // (the copy of the inputs this call's verifier took)
-                ++c->replays;
-                publish_counts(c, s);
-                c->last.replayed = 1;
-                c->last.nf_direct = p.direct ? 1 : 0;
-                c->last.esc_fused = p.fused ? 1 : 0;
-                // bits 0-1: rows are placed by / compared with the previous call's offsets (the sequence's own copy); 2: the analysis only
-                // verifies, beside the sequence; 3: no scan kernel; 4: no symbolic pass for the hash / dense rows
-                c->last.pred_stages = (c->pred_valid ? 3 : 0) | (p.overlap ? 4 : 0) | (p.skip_scan ? 8 : 0) | (p.num_verify ? 16 : 0);
-                return finish_complete();
-            }
-            }  // !b_first_bad
-            ++c->replay_misses;  // inputs changed under the same pointers: fall through
+        if (!have) return SPECK_OK;
+        // A sequence whose analysis only VERIFIES reads the metadata the previous multiply of THIS problem left in the
+        // arena.  If something else has used the arena since (another problem on this config, a stage entry point) the
+        // same sequence runs with a writing analysis in front instead and leaves the arena as the next replay needs it.
+        ReplayPlan p = c->plan;
+        if ((p.overlap && !arena_mine) || (p.skip_scan && !replay_layout)) p.overlap = p.skip_scan = p.num_verify = false;
+        c->arena_key_valid = false;  // (until this call has completed)
+        auto missed = [&] {  // inputs changed under the same pointers: the complete call re-runs
+            ++c->replay_misses;
             drop_plan(c);
+            how = Attempt::missed;
+            return SPECK_OK;
+        };
+        // (a sequence with its own analysis: the input check of B alone, beside it from its first launch on; one whose
+        //  numeric launches are the plain forms: the check FIRST -- they must not see a B that fails it)
+        bool b_first_bad = false, changed = false;
+        int rc = SPECK_OK;
+        if (!p.safe_numeric && !p.num_verify && c->validate_inputs) {
+            rc = begin_validate(c, B);
+            if (rc == SPECK_OK) rc = finish_validate(c, &b_first_bad);
+        } else if (!p.overlap && c->validate_inputs) {
+            rc = begin_validate(c, B);
         }
+        if (rc != SPECK_OK) return rc;
+        if (b_first_bad) return missed();
+        rc = enqueue_replay<T>(c, s, A, B, C, sc, p);
+        // (the verifier behind the sequence, while it runs: the host would only spin otherwise)
+        if (rc == SPECK_OK && p.overlap) rc = launch_verifier(c, A, B, sc);
+        // the last kernel of the sequence stores a ticket into pinned memory
+        if (rc == SPECK_OK) rc = wait_ticket(c, s);
+        if (rc == SPECK_OK) rc = p.overlap ? wait_verifier(c, &changed) : finish_validate(c, &changed);
+        if (rc != SPECK_OK) return rc;
+        if (c->h_stats->chain_error) return chain_failed(c, s);
+        if (changed || c->h_stats->capacity_miss || c->h_stats->nnz_overflow || c->h_stats->nnz_c != C->nnz) return missed();
+        c->arena_key = key;
+        c->arena_key_valid = c->arena_from_replay = true;
+        if (c->snap_pending) c->snap_for_arena = true;  // (the copy of the inputs this call's verifier took)
+        ++c->replays;
+        publish_counts(c, s);
+        c->last.replayed = 1;
+        c->last.nf_direct = p.direct ? 1 : 0, c->last.esc_fused = p.fused ? 1 : 0;
+        // bits 0-1: rows are placed by / compared with the previous call's offsets (the sequence's own copy); 2: the analysis only
+        // verifies, beside the sequence; 3: no scan kernel; 4: no symbolic pass for the hash / dense rows
+        c->last.pred_stages = (c->pred_valid ? 3 : 0) | (p.overlap ? 4 : 0) | (p.skip_scan ? 8 : 0) | (p.num_verify ? 16 : 0);
+        how = Attempt::done;
+        return finish_complete();
     }
 
-    // ------------------------------------------------------------------ complete call
-    c->arena_key_valid = false;  // (the arena is rewritten: it is this problem's once the call has completed)
-    // INIT: C.row_offsets reuse rule (Multiply.cu:156-165)
-    u32* c_ro = nullptr;
-    bool own_ro = false;
-    if (C->rows == A->rows && C->row_offsets != nullptr) {
-        c_ro = C->row_offsets;
-    } else {
-        HIP_TRY(guarded_malloc(reinterpret_cast<void**>(&c_ro), (size_t(m) + 1) * sizeof(u32)));
-        own_ro = true;
-    }
-    auto fail = [&](int code) {
-        if (own_ro) (void)guarded_free(c_ro);
-        return code;
-    };
-    t->init = st.lap();
-
-    // ANALYSIS + binning + SYMBOLIC + SCAN (Multiply.cu:239-575) -- one read-back
-    Timing tm;
-    u32 sym_now[kMaxClasses];
-    const u32* sym_known = nullptr;  // rows per symbolic class, once a read-back of this call has them
-    // what this call leaves behind for a repeated identical call: its row offsets, written by the scan kernel next to its
-    // other outputs.  No room on the device: that call places nothing early.
-    c->pred_valid = false;
-    const bool keep_pred = c->nf_direct && c->reuse && ensure_pred(c->pred, m);
-    // (the scan mirrors the statistics and stores the ticket itself: await_scan_stats)
-    const bool early_stats = c->spin_wait && !c->profile_kernels;
-    u32* const pred_out = keep_pred ? c->pred.off : nullptr;
-    // ONE batch, sized from the previous complete call on this config (same shapes): the classes that call had rows in
-    // (a row in any other class raises capacity_miss), grids from its counts, its scratch pool and numeric-first window
-    // (checked by the analysis / numeric-first kernels).  Saves the first of the two read-backs.
-    // The input check -- B's rows strictly ascending and in range: one coalesced pass over B.col_ids -- runs BESIDE the
-    // call on the verifier's stream; its verdict is looked at with the statistics of the scan, before anything of C is
-    // written.  Until then the kernels stay inside their tables and windows whatever B holds (a requirement for every
-    // kernel body: DESIGN.md 1).  A's column ids are checked -- and clamped -- by the analysis.
-    // (launched BEHIND the analysis of the call, not in front of it: enqueue_front starts it)
-    InputCheck check{c, B, s};
-    // a form of this call: the config's numeric-first window as it is NOW, the input check behind the analysis
-    auto form = [&] {
-        CallForm f;
-        f.nf_wcols = c->nf_wcols, f.after_analysis = &check;
-        return f;
-    };
-    auto front = [&](u32 parts) {
-        // (the offsets go to scratch: C.row_offsets -- possibly the caller's reused buffer -- is written only once
-        //  nothing can fail any more)
-        FrontArgs a;
-        a.parts = parts, a.sym_hint = parts == 2u ? sym_known : nullptr;
-        a.host_mirror = early_stats ? c->h_stats_dev : nullptr, a.pred_off_out = pred_out;
-        return enqueue_front(c, s, A, B, sc, (u32)sizeof(T), form(), a, &tm);
-    };
-    // ---- ONE-WALK call (walk.hip): when matOut is allocated and a complete call of the same shapes has run on the config,
-    // the rows of the register classes are finished in ONE walk inside the kernel that places the rows -- no symbolic
-    // pass for them, no scan kernel, no read-back before the numeric launches.  Everything the sequence assumes (classes
-    // with rows, pool and buffer sizes, nnz(C) = what the caller's buffers hold) is checked on the device; on a miss the
-    // two-phase call below re-runs (and re-allocates C as the reference does when nnz changes, Multiply.cu:589-592).
-    u32 num_mask = 0;
-    size_t ev_num_end = 0;
-    bool walked = false;
-    // ... first its form for inputs whose rows all fit the sub-wave hash table (walk_hash_kernel, numeric.hip): chosen from
-    // the previous complete call's figures -- longest row of C within the 256-entry class, most rows hash rows -- and
-    // checked row by row on the device
+    // ---- COMPLETE call: the arena is rewritten (it is this problem's once the call has completed), the row offsets of C by
+    // the reuse rule of the reference (INIT, Multiply.cu:156-165), what the call will leave for a repeated identical one
+    int begin_complete()
     {
-        const u32* sl = c->last_sym_counts;
+        c->arena_key_valid = false;
+        if (C->rows == A->rows && C->row_offsets != nullptr) {
+            c_ro = C->row_offsets;
+        } else {
+            HIP_TRY(guarded_malloc(reinterpret_cast<void**>(&c_ro), (size_t(m) + 1) * sizeof(u32)));
+            own_ro = true;
+        }
+        t->init = st.lap();
+        c->pred_valid = false;
+        keep_pred = c->nf_direct && c->reuse && ensure_pred(c->pred, m);
+        early_stats = c->spin_wait && !c->profile_kernels;
+        pred_out = keep_pred ? c->pred.off : nullptr;
+        return SPECK_OK;
+    }
+
+    // ---- HASH ONE-WALK call (walk_hash_kernel, numeric.hip; option one_walk_hash): analysis -> walk_hash_kernel -> done.
+    // Applies when C is allocated and the previous complete call, of the same shapes, says that every row fits the sub-wave
+    // hash table -- longest row of C within the 256-entry class, most rows hash rows; checked row by row on the device.
+    int try_walk_hash(Attempt& how)
+    {
+        const LastCall& prev = c->prev;
+        const u32* sl = prev.sym_counts;
         const u64 hash_rows = u64(sl[SYM_W128]) + sl[SYM_W256] + sl[SYM_W1K];
         const u64 groups = (u64(m) + kWalkHashRows - 1) / kWalkHashRows;
         const bool pays = c->one_walk_hash >= 2 || 2 * hash_rows >= m;
-        if (c->one_walk_hash && pays && c_ready && C->nnz <= 0xFFFFFFFFull && c->spec_valid && c->spec_rows_a == A->rows &&
-            c->spec_rows_b == B->rows && !c->use_user_stream && c->last_max_row_nnz != 0 &&
-            c->last_max_row_nnz <= kNumW256MaxNnz && c->last_max_row_ops <= 4096 && groups <= kChain3MaxGroups) {
-            Chain3 ch3;
-            rc = next_chain3(c, s, groups, &ch3);
-            if (rc != SPECK_OK) return rc;
-            FrontArgs fa;
-            fa.parts = 1u;
-            rc = enqueue_front(c, s, A, B, sc, (u32)sizeof(T), form(), fa, &tm);
-            if (rc != SPECK_OK) return rc;
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (c->profile_kernels) {
-                tm.ev_scan = tm.ev;
-                e0 = kernel_event(c, tm.ev++);
-                e1 = kernel_event(c, tm.ev++);
-            }
-            WalkHashArgs wa{};
-            wa.a_ro = A->row_offsets;
-            wa.row_ops = sc.row_ops, wa.row_col_min = sc.row_col_min, wa.row_col_max = sc.row_col_max;
-            wa.offsets_out = sc.offsets;
-            wa.pred_off_out = nullptr;
-            wa.st = c->d_stats;
-            wa.c_col = C->col_ids;
-            wa.c_val = C->data;
-            wa.c_cap = C->nnz;
-            wa.m = m;
-            wa.max_ops = 4096;
-            wa.want_bytes = c->cp.want_bytes;
-            wa.vsize = (u32)sizeof(T);
-            wa.bytes_acc = c->cp.want_bytes ? c->d_bytes : nullptr;
-            wa.debug = c->walk_hash_debug;
-            const ProductSrc<T> src{sc.b_sl, static_cast<const T*>(A->data), B->col_ids, static_cast<const T*>(B->data), sc.w_sl};
-            launch_walk_hash<T>(s, wa, src, ch3, e0, e1);
-            if (c->profile_kernels) {
-                tm.ev_num = tm.ev;
-                (void)hipEventRecord(kernel_event(c, tm.ev++), s);
-            }
+        if (!c->one_walk_hash || !pays || !c_usable() || !prev.ran_on(A, B) || c->use_user_stream || prev.max_row_nnz == 0 ||
+            prev.max_row_nnz > kNumW256MaxNnz || prev.max_row_ops > 4096 || groups > kChain3MaxGroups)
+            return SPECK_OK;
+        Chain3 ch3;
+        int rc = next_chain3(c, s, groups, &ch3);
+        if (rc != SPECK_OK) return rc;
+        FrontArgs fa;
+        fa.parts = 1u;
+        rc = front(form(), fa);
+        if (rc != SPECK_OK) return rc;
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        if (c->profile_kernels) {
+            tm.ev_scan = tm.ev;
+            e0 = kernel_event(c, tm.ev++);
+            e1 = kernel_event(c, tm.ev++);
+        }
+        WalkHashArgs wa{};
+        wa.a_ro = A->row_offsets, wa.m = m, wa.max_ops = 4096, wa.vsize = (u32)sizeof(T);
+        wa.row_ops = sc.row_ops, wa.row_col_min = sc.row_col_min, wa.row_col_max = sc.row_col_max;
+        wa.offsets_out = sc.offsets, wa.pred_off_out = nullptr, wa.st = c->d_stats;
+        wa.c_col = C->col_ids, wa.c_val = C->data, wa.c_cap = C->nnz;
+        wa.want_bytes = c->cp.want_bytes, wa.bytes_acc = c->cp.want_bytes ? c->d_bytes : nullptr;
+        wa.debug = c->walk_hash_debug;
+        const ProductSrc<T> src{sc.b_sl, static_cast<const T*>(A->data), B->col_ids, static_cast<const T*>(B->data), sc.w_sl};
+        launch_walk_hash<T>(s, wa, src, ch3, e0, e1);
+        (void)timed_numeric([&] {
             launch_copy_offsets(s, sc.offsets, C->row_offsets, m + 1, c->d_stats);
-            ev_num_end = tm.ev;
-            if (c->profile_kernels) (void)hipEventRecord(kernel_event(c, tm.ev++), s);
-            LAUNCHES_OK();
-            rc = read_stats(c, s);
-            if (rc != SPECK_OK) return rc;
-            rc = input_verdict(c);
-            if (rc != SPECK_OK) return rc;
-            const bool ok = speculation_held(c->h_stats, C->nnz);
-            ++(ok ? c->walks : c->walk_misses);
-            if (ok) {
-                publish_counts(c, s);
-                c->last.one_walk = 2;
-                c->last.num_bin_rows[NUM_W256] = m;  // (every row went through the 256-entry sub-wave body)
-                t->spGEMMCounting = 0.f;
-                t->spGEMMNumeric = st.lap();
-                // the arena holds no numeric records / lists of this call: a reuse sequence is planned from a two-phase
-                // call only; the figures this path was chosen by are refreshed
-                c->last_max_row_nnz = c->h_stats->max_row_nnz_c;
-                c->last_max_row_ops = c->h_stats->max_row_ops;
-                c->last_key_valid = false;
-                c->arena_key_valid = false;
-                c->pred_valid = false;
-                drop_plan(c);
-                rc = finish_complete();
-                if (rc != SPECK_OK) return rc;
-                if (c->profile_kernels) {
-                    HIP_TRY(hipStreamSynchronize(s));
-                    publish_kernel_times(c, tm, ev_num_end);
-                }
-                return SPECK_OK;
-            }
-            check.started = false;  // (the two-phase call checks B again)
-            tm = Timing{};
+            return SPECK_OK;
+        });
+        LAUNCHES_OK();
+        bool held = false;
+        rc = settle_batch(c->walks, c->walk_misses, &held);
+        if (rc != SPECK_OK) return rc;
+        if (!held) return miss(how, true);
+        publish_counts(c, s);
+        c->last.one_walk = 2;
+        c->last.num_bin_rows[NUM_W256] = m;  // (every row went through the 256-entry sub-wave body)
+        t->spGEMMCounting = 0.f;
+        t->spGEMMNumeric = st.lap();
+        // the arena holds no numeric records / lists of this call: a reuse sequence is planned from a two-phase
+        // call only; the figures this path was chosen by are refreshed
+        c->prev.max_row_nnz = c->h_stats->max_row_nnz_c, c->prev.max_row_ops = c->h_stats->max_row_ops;
+        c->last_key_valid = c->arena_key_valid = c->pred_valid = false;
+        drop_plan(c);
+        how = Attempt::done;
+        rc = finish_complete();
+        if (rc != SPECK_OK) return rc;
+        if (c->profile_kernels) {
+            HIP_TRY(hipStreamSynchronize(s));
+            publish_kernel_times(c, tm, ev_num_end);
         }
+        return SPECK_OK;
     }
-    if (c->one_walk && c_ready && C->nnz <= 0xFFFFFFFFull && c->spec_valid && c->spec_rows_a == A->rows &&
-        c->spec_rows_b == B->rows && m <= walk_max_rows() && !c->use_user_stream) {
-        const u32* sc_last = c->last_sym_counts;
-        const u64 esc_rows = u64(sc_last[SYM_G8]) + sc_last[SYM_G16] + sc_last[SYM_R32] + sc_last[SYM_R64];
-        const u64 esc_bound = 32ull * sc_last[SYM_G8] + 64ull * sc_last[SYM_G16] + 128ull * sc_last[SYM_R32] + 256ull * sc_last[SYM_R64];
+
+    // ---- ONE-WALK call (walk.hip; option one_walk).  Applies when C is allocated and a complete call of the same shapes has
+    // run on the config: the rows of the register classes are finished in ONE walk inside the kernel that places the rows --
+    // no symbolic pass for them, no scan kernel, no read-back before the numeric launches.  Everything the sequence assumes
+    // (classes with rows, pool and buffer sizes, nnz(C) = what the caller's buffers hold) is checked on the device; on a miss
+    // the two-phase call re-runs (and re-allocates C as the reference does when nnz changes, Multiply.cu:589-592).
+    int try_one_walk(Attempt& how)
+    {
+        const LastCall& prev = c->prev;
+        if (!c->one_walk || !c_usable() || !prev.ran_on(A, B) || m > walk_max_rows() || c->use_user_stream) return SPECK_OK;
+        const u32* sl = prev.sym_counts;
+        const u64 esc_rows = u64(sl[SYM_G8]) + sl[SYM_G16] + sl[SYM_R32] + sl[SYM_R64];
+        const u64 esc_bound = 32ull * sl[SYM_G8] + 64ull * sl[SYM_G16] + 128ull * sl[SYM_R32] + 256ull * sl[SYM_R64];
         // it pays when the rows the walk kernel finishes (or moves) are a good share of all rows
-        const bool pays = c->one_walk >= 2 || 8 * (esc_rows + sc_last[SYM_NF]) >= m;
-        const u64 want = c->last_was_walk ? c->last_nf_entries + c->last_nf_entries / 32 + 4096 : c->last_nf_entries + esc_bound + 4096;
-        if (pays && want < (1ull << 40) && ensure_nfpool(c, want, sizeof(T)) == SPECK_OK) {
-            u32 hints[kMaxClasses];
-            const u32 launch_mask = c->last_num_mask & ~(kNumEscMask | (1u << NUM_NFCOPY));
-            CallForm f = form();
-            f.one_walk = true;
-            f.c_col = C->col_ids, f.c_val = C->data, f.c_cap = C->nnz;
-            f.off_src = sc.offsets, f.off_dst = C->row_offsets, f.off_n = m + 1;
-            FrontArgs fa;
-            fa.sym_mask = speculated_hints(c, hints) & ~kSymEscMask, fa.num_mask = launch_mask;
-            fa.sym_hint = hints, fa.hint_exact = false;
-            fa.expect_g = c->last_g_products, fa.expect_g_rows = c->last_num_counts[NUM_G], fa.expect_nf = c->nf_cap_entries;
-            fa.pred_off_out = pred_out;
-            rc = enqueue_front(c, s, A, B, sc, (u32)sizeof(T), f, fa, &tm);
-            if (rc != SPECK_OK) return rc;
-            if (c->profile_kernels) {
-                tm.ev_num = tm.ev;
-                (void)hipEventRecord(kernel_event(c, tm.ev++), s);
-            }
-            rc = enqueue_back<T>(c, s, A, B, sc, f, C->col_ids, static_cast<T*>(C->data), launch_mask, c->last_num_counts, &tm);
-            if (rc != SPECK_OK) return rc;
-            ev_num_end = tm.ev;
-            if (c->profile_kernels) (void)hipEventRecord(kernel_event(c, tm.ev++), s);
-            rc = read_stats(c, s);  // (done_kernel + ticket; the one wait of the call)
-            if (rc != SPECK_OK) return rc;
-            rc = input_verdict(c);
-            if (rc != SPECK_OK) return rc;
-            walked = speculation_held(c->h_stats, C->nnz);
-            ++(walked ? c->walks : c->walk_misses);
-            if (walked) {
-                publish_counts(c, s);
-                num_mask = mask_of(c->h_stats->num.count, NUM_CLASSES);
-                c->last.one_walk = 1;
-                t->spGEMMCounting = 0.f;
-                t->spGEMMNumeric = st.lap();
-            } else {
-                check.started = false;  // (the two-phase call checks B again: its verdict word was consumed)
-            }
-        }
+        const bool pays = c->one_walk >= 2 || 8 * (esc_rows + sl[SYM_NF]) >= m;
+        const u64 want = prev.was_walk ? prev.nf_entries + prev.nf_entries / 32 + 4096 : prev.nf_entries + esc_bound + 4096;
+        if (!pays || want >= (1ull << 40) || ensure_nfpool(c, want, sizeof(T)) != SPECK_OK) return SPECK_OK;
+        u32 hints[kMaxClasses];
+        const u32 launch_mask = prev.num_mask & ~(kNumEscMask | (1u << NUM_NFCOPY));
+        CallForm f = form();
+        f.one_walk = true;
+        f.c_col = C->col_ids, f.c_val = C->data, f.c_cap = C->nnz;
+        f.off_src = sc.offsets, f.off_dst = C->row_offsets, f.off_n = m + 1;
+        FrontArgs fa;
+        fa.sym_mask = speculated_hints(c, hints) & ~kSymEscMask, fa.num_mask = launch_mask;
+        fa.sym_hint = hints, fa.hint_exact = false;
+        fa.expect_g = prev.g_products, fa.expect_g_rows = prev.num_counts[NUM_G], fa.expect_nf = c->nf_cap_entries;
+        fa.pred_off_out = pred_out;
+        int rc = front(f, fa);
+        if (rc != SPECK_OK) return rc;
+        rc = timed_numeric([&] { return back(f, C->col_ids, C->data, launch_mask, prev.num_counts); });
+        if (rc != SPECK_OK) return rc;
+        bool held = false;
+        rc = settle_batch(c->walks, c->walk_misses, &held);
+        if (rc != SPECK_OK) return rc;
+        if (!held) return miss(how, false);  // (unlike the other two misses this one has never forgotten the attempt's events: kept)
+        publish_counts(c, s);
+        num_mask = mask_of(c->h_stats->num.count, NUM_CLASSES);
+        c->last.one_walk = 1;
+        t->spGEMMCounting = 0.f;
+        t->spGEMMNumeric = st.lap();
+        how = Attempt::done;
+        return SPECK_OK;
     }
-    // ---- THROUGH call: a complete two-phase call enqueued in ONE batch -- analysis, symbolic, scan AND the numeric launches,
-    // sized from the previous complete call on this config, into the buffers matOut already has.  What the host checks between
-    // the two phases of the call below is checked by the scan on the device; a miss leaves C untouched and falls through.
-    bool through_ok = false, through_missed = false, through_front = false;
-    if (!walked && c->eager_through && c->eager_speculate && c->spec_valid && c->spec_rows_a == A->rows && c->spec_rows_b == B->rows &&
-        c_ready && C->nnz <= 0xFFFFFFFFull && C->nnz == c->last_eager_stats.nnz_c && c->last_num_mask && !c->last_was_walk &&
-        !c->profile_kernels && !t->measureAll && c->spin_wait && !c->cp.want_bytes &&
-        (!(c->last_num_mask >> NUM_G & 1u) || c->spill.plan != nullptr)) {
+
+    // ---- THROUGH call (option eager_through): a complete two-phase call enqueued in ONE batch -- analysis, symbolic, scan AND
+    // the numeric launches, sized from the previous complete call on this config.  Applies when that call had the same shapes
+    // and was no walk, C holds buffers of the size it produced, and nothing is being timed or counted.  What the host checks
+    // between the two phases of a two-phase call the scan checks on the device; a miss leaves C untouched.
+    int try_through(Attempt& how)
+    {
+        const LastCall& prev = c->prev;
+        if (!c->eager_through || !c->eager_speculate || !prev.ran_on(A, B) || !c_usable() || C->nnz != prev.eager_stats.nnz_c ||
+            !prev.num_mask || prev.was_walk || c->profile_kernels || t->measureAll || !c->spin_wait || c->cp.want_bytes ||
+            ((prev.num_mask >> NUM_G & 1u) && c->spill.plan == nullptr))
+            return SPECK_OK;
         u32 hints[kMaxClasses];
         CallForm f = form();
         f.through_gate = c->validate_inputs ? c->h_verify_dev : nullptr;
@@ -1615,298 +1612,353 @@ int multiply_impl(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, spe
         f.off_src = sc.offsets, f.off_dst = C->row_offsets, f.off_n = m + 1;  // (c_ready: c_ro IS C's array)
         FrontArgs fa;
         fa.exact_nnz = C->nnz;
-        fa.sym_mask = speculated_hints(c, hints), fa.num_mask = c->last_num_mask, fa.sym_hint = hints;
-        if (c->last_num_mask >> NUM_G & 1u) fa.expect_g = c->last_g_products, fa.expect_g_rows = c->last_num_counts[NUM_G];
+        fa.sym_mask = speculated_hints(c, hints), fa.num_mask = prev.num_mask, fa.sym_hint = hints;
+        if (prev.num_mask >> NUM_G & 1u) fa.expect_g = prev.g_products, fa.expect_g_rows = prev.num_counts[NUM_G];
         fa.expect_nf = c->nf_cap_entries, fa.pred_off_out = pred_out;
-        rc = enqueue_front(c, s, A, B, sc, (u32)sizeof(T), f, fa, &tm);
-        if (rc != SPECK_OK) return fail(rc);
-        rc = enqueue_back<T>(c, s, A, B, sc, f, C->col_ids, static_cast<T*>(C->data), c->last_num_mask, c->last_num_counts, &tm);
-        if (rc != SPECK_OK) return fail(rc);
-        rc = read_stats(c, s);  // (done_kernel + ticket: the one wait of the call)
-        if (rc != SPECK_OK) return fail(rc);
-        rc = input_verdict(c);  // (a B that fails the check: the scan saw the verdict, nothing of C was written)
-        if (rc != SPECK_OK) return fail(rc);
-        through_ok = speculation_held(c->h_stats, C->nnz);
-        ++(through_ok ? c->through_hits : c->through_misses);
-        if (through_ok) {
+        int rc = front(f, fa);
+        if (rc == SPECK_OK) rc = back(f, C->col_ids, C->data, prev.num_mask, prev.num_counts);
+        bool held = false;
+        if (rc == SPECK_OK) rc = settle_batch(c->through_hits, c->through_misses, &held);
+        if (rc != SPECK_OK) return rc;
+        if (held) {
             publish_counts(c, s);
             num_mask = mask_of(c->h_stats->num.count, NUM_CLASSES);
-            c->last_g_products = c->h_stats->g_products;
-            c->last.eager_speculated = 1;
-            c->last.eager_through = 1;
+            c->prev.g_products = c->h_stats->g_products;
+            c->last.eager_speculated = c->last.eager_through = 1;
             t->countProducts = t->loadBalanceCounting = t->globalMapsCounting = t->globalMapsNumeric = t->allocC = t->loadBalanceNumeric = 0.f;
             t->spGEMMCounting = 0.f;
             t->spGEMMNumeric = st.lap();
+            how = Attempt::done;
         } else if (!c->h_stats->front_miss && !c->h_stats->nnz_overflow) {
             // only the scan objected (another nnz(C), a numeric class without a launch, the spill pool): its offsets, counts
             // and class lists stand -- the call goes on behind its ONE read-back like a speculated call whose checks held;
             // the numeric launches queued above found the flag and wrote nothing
             HIP_TRY(hipMemsetAsync(&c->d_stats->capacity_miss, 0, sizeof(u32), s));
             c->h_stats->capacity_miss = 0;
-            through_missed = through_front = true;
-        } else {
-            check.started = false;  // (the call below checks B again: the verdict word was consumed)
-            tm = Timing{};
-            through_missed = true;
-        }
+            how = Attempt::front_stands;
+        } else
+            return miss(how, true);
+        return SPECK_OK;
     }
-    if (!walked && !through_ok) {
-    bool speculated = through_front;
-    if (through_front) c->last.eager_speculated = 1;
-    u32 spec_counts[kMaxClasses];
-    if (c->eager_speculate && !through_missed && c->spec_valid && c->spec_rows_a == A->rows && c->spec_rows_b == B->rows) {
+
+    // ---- SPECULATED batch (option eager_speculate): analysis .. scan as ONE batch, sized from the previous complete call on
+    // this config when it had the same shapes: the classes that call had rows in (a row in any other class raises
+    // capacity_miss), grids from its counts, its scratch pool and numeric-first window (checked by the analysis /
+    // numeric-first kernels).  Saves the first of the two read-backs; *held: the front stands.
+    int front_speculated(bool* held)
+    {
+        if (!c->eager_speculate || !c->prev.ran_on(A, B)) return SPECK_OK;
+        u32 spec_counts[kMaxClasses];
         FrontArgs fa;
         fa.sym_mask = speculated_hints(c, spec_counts), fa.sym_hint = spec_counts;
         fa.host_mirror = early_stats ? c->h_stats_dev : nullptr;
         fa.expect_nf = c->nf_cap_entries, fa.pred_off_out = pred_out;
-        rc = enqueue_front(c, s, A, B, sc, (u32)sizeof(T), form(), fa, &tm);
-        if (rc == SPECK_OK) rc = early_stats ? await_scan_stats(c, s) : read_stats(c, s);
-        if (rc == SPECK_OK) rc = input_verdict(c);
-        if (rc != SPECK_OK) return fail(rc);
-        speculated = !c->h_stats->capacity_miss;
-        ++(speculated ? c->eager_spec_hits : c->eager_spec_misses);
-        c->last.eager_speculated = speculated ? 1 : -1;
+        int rc = front(form(), fa);
+        if (rc == SPECK_OK) rc = await_front();
+        if (rc != SPECK_OK) return rc;
+        *held = !c->h_stats->capacity_miss;
+        ++(*held ? c->eager_spec_hits : c->eager_spec_misses);
+        c->last.eager_speculated = *held ? 1 : -1;
+        return SPECK_OK;
     }
-    if (!speculated) {
-    // analysis + binning
-    rc = front(1u);
-    if (rc != SPECK_OK) return fail(rc);
-    if (c->cp.nf_min_ops || c->cp.gh_per_window) {
-        // numeric-first rows (and the global key sets of SYM_GH rows) need their scratch pool before the
-        // symbolic phase: one more read-back
-        rc = read_stats(c, s);
-        if (rc != SPECK_OK) return fail(rc);
-        if (c->h_stats->a_invalid) return fail(SPECK_ERR_INVALID);
-        // No room (or no budget) for the pool: first the global key sets go (those rows take the multi-window
-        // bitmap, which needs no memory), then the numeric-first rows (they take the two-phase path) -- for this
-        // config from now on; the rows are classified again.
-        while (c->h_stats->nf_entries) {
-            rc = ensure_nfpool(c, c->h_stats->nf_entries, sizeof(T));
-            if (rc != SPECK_ERR_OOM) break;
-            if (c->cp.gh_per_window && c->h_stats->sym.count[SYM_GH]) c->cp.gh_per_window = 0;
-            else if (c->cp.nf_min_ops && c->h_stats->sym.count[SYM_NF]) c->cp.nf_min_ops = 0;
-            else break;
-            ++c->pool_fallbacks;
-            rc = front(1u);
-            if (rc == SPECK_OK) rc = read_stats(c, s);
-            if (rc != SPECK_OK) break;
-        }
-        if (rc != SPECK_OK) return fail(rc);
-        c->nf_wcols = c->h_stats->nf_max_range ? c->h_stats->nf_max_range : kNumD1Cols;
-        // the read-back also buys right-sized grids, fork decisions and exact class counts for the symbolic launches
-        std::memcpy(sym_now, c->h_stats->sym.count, sizeof(sym_now));
-        sym_known = sym_now;
-    }
-    // (with both scratch-pool classes off the symbolic kernels run before the host has seen the verdict of the
-    //  check: they stay inside their tables and windows whatever B holds, and nothing of C is written before the
-    //  read-back below)
-    rc = front(2u);
-    if (rc != SPECK_OK) return fail(rc);
-    rc = early_stats ? await_scan_stats(c, s) : read_stats(c, s);
-    if (rc == SPECK_OK) rc = input_verdict(c);
-    if (rc != SPECK_OK) return fail(rc);
-    }  // !speculated
-    t->countProducts = 0.f;
-    t->loadBalanceCounting = 0.f;
-    t->globalMapsCounting = 0.f;
-    t->spGEMMCounting = st.lap();  // analysis + binning + symbolic + scan are one async batch
-    publish_counts(c, s);
-    if (c->h_stats->nnz_overflow) return fail(SPECK_ERR_NNZ_OVERFLOW);
-    const u64 nnz_c = c->h_stats->nnz_c;
 
-    if (c->h_stats->sum_products == 0) {
+    // ---- the front of the plain TWO-PHASE call: ANALYSIS + binning, SYMBOLIC + SCAN (Multiply.cu:239-575) -- one read-back,
+    // two when a scratch-pool class is on
+    int front_two_phase()
+    {
+        u32 sym_now[kMaxClasses];
+        const u32* sym_known = nullptr;  // rows per symbolic class, once a read-back of this call has them
+        int rc = plain_front(1u, nullptr);
+        if (rc != SPECK_OK) return rc;
+        if (c->cp.nf_min_ops || c->cp.gh_per_window) {
+            // numeric-first rows (and the global key sets of SYM_GH rows) need their scratch pool before the
+            // symbolic phase: one more read-back
+            rc = read_stats(c, s);
+            if (rc != SPECK_OK) return rc;
+            if (c->h_stats->a_invalid) return SPECK_ERR_INVALID;
+            // No room (or no budget) for the pool: first the global key sets go (those rows take the multi-window
+            // bitmap, which needs no memory), then the numeric-first rows (they take the two-phase path) -- for this
+            // config from now on; the rows are classified again.
+            while (c->h_stats->nf_entries) {
+                rc = ensure_nfpool(c, c->h_stats->nf_entries, sizeof(T));
+                if (rc != SPECK_ERR_OOM) break;
+                if (c->cp.gh_per_window && c->h_stats->sym.count[SYM_GH]) c->cp.gh_per_window = 0;
+                else if (c->cp.nf_min_ops && c->h_stats->sym.count[SYM_NF]) c->cp.nf_min_ops = 0;
+                else break;
+                ++c->pool_fallbacks;
+                rc = plain_front(1u, nullptr);
+                if (rc == SPECK_OK) rc = read_stats(c, s);
+                if (rc != SPECK_OK) break;
+            }
+            if (rc != SPECK_OK) return rc;
+            c->nf_wcols = c->h_stats->nf_max_range ? c->h_stats->nf_max_range : kNumD1Cols;
+            // the read-back also buys right-sized grids, fork decisions and exact class counts for the symbolic launches
+            std::memcpy(sym_now, c->h_stats->sym.count, sizeof(sym_now));
+            sym_known = sym_now;
+        }
+        // (with both scratch-pool classes off the symbolic kernels run before the host has seen the verdict of the
+        //  check: they stay inside their tables and windows whatever B holds, and nothing of C is written before the
+        //  read-back below)
+        rc = plain_front(2u, sym_known);
+        return rc == SPECK_OK ? await_front() : rc;
+    }
+
+    // ... whichever front stands, its statistics are on the host: the stage times, the counts, and the product without an
+    // entry (*empty: C is published with nnz 0 and the call is over)
+    int settle_front(bool* empty)
+    {
+        t->countProducts = t->loadBalanceCounting = t->globalMapsCounting = 0.f;
+        t->spGEMMCounting = st.lap();  // analysis + binning + symbolic + scan are one async batch
+        publish_counts(c, s);
+        if (c->h_stats->nnz_overflow) return SPECK_ERR_NNZ_OVERFLOW;
+        *empty = c->h_stats->sum_products == 0;
+        if (!*empty) return SPECK_OK;
         // reference: Multiply.cu:256-261 -> matOut.alloc(rows, cols, 0, false)
         if (own_ro) (void)guarded_free(c_ro);
+        own_ro = false;
         speck_dcsr_free(C);
-        C->rows = A->rows;
-        C->cols = B->cols;
-        C->nnz = 0;
+        C->rows = A->rows, C->cols = B->cols, C->nnz = 0;
         c->last_key_valid = false;
         return finish_complete();
     }
 
     // Spill pool of the NUM_G rows FIRST: every failure up to here leaves C untouched (header contract).
-    num_mask = mask_of(c->h_stats->num.count, NUM_CLASSES);
-    if (num_mask >> NUM_G & 1u) {
-        // global-memory spill buffers of the heavy rows (role of the reference's global maps,
-        // Multiply.cu:357-427), grow-only: per-row plan, per-bucket counters, and two product
-        // pools sized from the EXACT product count of the NUM_G rows (numeric.hip, NUM_G)
-        const u64 pg = c->h_stats->g_products;
-        const u32 rows_g = c->h_stats->num.count[NUM_G];
-        const u64 buckets = pg / kGBucketTarget + rows_g + 16;
-        const u64 cells = u64(kGCellsPerBucket) * buckets;
-        if (cells > 0x7FFFFFFFull) return fail(SPECK_ERR_OOM);
-        const size_t need = Carver::need(rows_g, sizeof(GRowPlan)) + Carver::need(cells + 3 * buckets + 4, 4) +
-                            Carver::need(buckets, 8) +
-                            Carver::need(cells, 4) + Carver::need(buckets, 8) + 2 * Carver::need(buckets, 4) +
-                            2 * Carver::need(pg, 4) + 2 * Carver::need(pg, sizeof(T)) + 4096;
-        if (need > c->gpool_bytes) {
-            drop_plan(c);
-            if (c->gpool) (void)guarded_free(c->gpool);
-            c->gpool = nullptr;
-            c->gpool_bytes = 0;
-            if (guarded_malloc(&c->gpool, need + need / 8) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(SPECK_ERR_OOM);
+    int size_spill_pool()
+    {
+        num_mask = mask_of(c->h_stats->num.count, NUM_CLASSES);
+        if (num_mask >> NUM_G & 1u) {
+            // global-memory spill buffers of the heavy rows (role of the reference's global maps,
+            // Multiply.cu:357-427), grow-only: per-row plan, per-bucket counters, and two product
+            // pools sized from the EXACT product count of the NUM_G rows (numeric.hip, NUM_G)
+            const u64 pg = c->h_stats->g_products;
+            const u32 rows_g = c->h_stats->num.count[NUM_G];
+            const u64 buckets = pg / kGBucketTarget + rows_g + 16;
+            const u64 cells = u64(kGCellsPerBucket) * buckets;
+            if (cells > 0x7FFFFFFFull) return SPECK_ERR_OOM;
+            const size_t need = Carver::need(rows_g, sizeof(GRowPlan)) + Carver::need(cells + 3 * buckets + 4, 4) +
+                                Carver::need(buckets, 8) +
+                                Carver::need(cells, 4) + Carver::need(buckets, 8) + 2 * Carver::need(buckets, 4) +
+                                2 * Carver::need(pg, 4) + 2 * Carver::need(pg, sizeof(T)) + 4096;
+            if (need > c->gpool_bytes) {
+                drop_plan(c);
+                if (c->gpool) (void)guarded_free(c->gpool);
+                c->gpool = nullptr, c->gpool_bytes = 0;
+                if (guarded_malloc(&c->gpool, need + need / 8) != hipSuccess) {
+                    (void)hipGetLastError();
+                    return SPECK_ERR_OOM;
+                }
+                c->gpool_bytes = need + need / 8;
             }
-            c->gpool_bytes = need + need / 8;
+            c->gpool_zones.clear();
+            Carver cv(c->gpool, guard_bytes(), &c->gpool_zones);
+            SpillBuffers sp{};
+            sp.plan = cv.take<GRowPlan>(rows_g);
+            // fcount | bcount | bcursor | dcount are cleared by ONE memset: keep them back to back
+            u32* counters = cv.take<u32>(cells + 3 * buckets + 4);
+            sp.fcount = counters, sp.bcount = counters + cells;
+            sp.bcursor = sp.bcount + buckets, sp.dcount = sp.bcursor + buckets, sp.big_count = sp.dcount + buckets;
+            sp.big_list = cv.take<u64>(buckets);
+            sp.fmap = cv.take<u32>(cells);
+            sp.bstart = cv.take<u64>(buckets);
+            sp.clo = cv.take<u32>(buckets), sp.chi = cv.take<u32>(buckets);
+            sp.pcol[0] = cv.take<u32>(pg), sp.pcol[1] = cv.take<u32>(pg);
+            sp.pval[0] = cv.take<T>(pg), sp.pval[1] = cv.take<T>(pg);
+            sp.bucket_cap = (u32)buckets, sp.cell_cap = (u32)cells;
+            if (sp.plan != c->spill.plan || sp.pcol[0] != c->spill.pcol[0] || sp.pval[1] != c->spill.pval[1] ||
+                sp.bucket_cap != c->spill.bucket_cap)
+                drop_plan(c);  // a reuse sequence holds the old layout
+            c->spill = sp;
+            if (guard_bytes()) HIP_TRY(guard_fill(c->gpool_zones, s));  // (nothing of an earlier call is in flight on the pool)
         }
-        c->gpool_zones.clear();
-        Carver cv(c->gpool, guard_bytes(), &c->gpool_zones);
-        SpillBuffers sp{};
-        sp.plan = cv.take<GRowPlan>(rows_g);
-        // fcount | bcount | bcursor | dcount are cleared by ONE memset: keep them back to back
-        u32* counters = cv.take<u32>(cells + 3 * buckets + 4);
-        sp.fcount = counters;
-        sp.bcount = counters + cells;
-        sp.bcursor = sp.bcount + buckets;
-        sp.dcount = sp.bcursor + buckets;
-        sp.big_count = sp.dcount + buckets;
-        sp.big_list = cv.take<u64>(buckets);
-        sp.fmap = cv.take<u32>(cells);
-        sp.bstart = cv.take<u64>(buckets);
-        sp.clo = cv.take<u32>(buckets);
-        sp.chi = cv.take<u32>(buckets);
-        sp.pcol[0] = cv.take<u32>(pg);
-        sp.pcol[1] = cv.take<u32>(pg);
-        sp.pval[0] = cv.take<T>(pg);
-        sp.pval[1] = cv.take<T>(pg);
-        sp.bucket_cap = (u32)buckets;
-        sp.cell_cap = (u32)cells;
-        if (sp.plan != c->spill.plan || sp.pcol[0] != c->spill.pcol[0] || sp.pval[1] != c->spill.pval[1] ||
-            sp.bucket_cap != c->spill.bucket_cap)
-            drop_plan(c);  // a reuse sequence holds the old layout
-        c->spill = sp;
-        if (guard_bytes()) HIP_TRY(guard_fill(c->gpool_zones, s));  // (nothing of an earlier call is in flight on the pool)
+        t->globalMapsNumeric = st.lap();
+        return SPECK_OK;
     }
-    t->globalMapsNumeric = st.lap();
-    // ALLOC C: only when nnz changed (Multiply.cu:589-602)
-    void* c_val = C->data;
-    u32* c_col = C->col_ids;
-    if (C->nnz != nnz_c || !c_val || !c_col) {
-        void* nv = nullptr;
-        u32* nc = nullptr;
-        hipError_t e1 = guarded_malloc(&nv, std::max<size_t>(nnz_c, 1) * sizeof(T));
-        hipError_t e2 = e1 == hipSuccess
-                            ? guarded_malloc(reinterpret_cast<void**>(&nc), std::max<size_t>(nnz_c, 1) * 4)
-                            : e1;
-        if (e1 != hipSuccess || e2 != hipSuccess) {
-            if (nv) (void)guarded_free(nv);
-            (void)hipGetLastError();
-            return fail(SPECK_ERR_OOM);
+
+    // ALLOC C: only when nnz changed (Multiply.cu:589-602); publish (Multiply.cu:1116-1121) -- from here C owns c_ro
+    int adopt_output()
+    {
+        const u64 nnz_c = c->h_stats->nnz_c;
+        void* c_val = C->data;
+        u32* c_col = C->col_ids;
+        if (C->nnz != nnz_c || !c_val || !c_col) {
+            void* nv = nullptr;
+            u32* nc = nullptr;
+            hipError_t e1 = guarded_malloc(&nv, std::max<size_t>(nnz_c, 1) * sizeof(T));
+            hipError_t e2 = e1 == hipSuccess ? guarded_malloc(reinterpret_cast<void**>(&nc), std::max<size_t>(nnz_c, 1) * 4) : e1;
+            if (e1 != hipSuccess || e2 != hipSuccess) {
+                if (nv) (void)guarded_free(nv);
+                (void)hipGetLastError();
+                return SPECK_ERR_OOM;
+            }
+            if (C->data) (void)guarded_free(C->data);
+            if (C->col_ids) (void)guarded_free(C->col_ids);
+            if (C->row_offsets && C->row_offsets != c_ro) (void)guarded_free(C->row_offsets);
+            c_val = nv;
+            c_col = nc;
+        } else if (C->row_offsets && C->row_offsets != c_ro) {
+            (void)guarded_free(C->row_offsets);
         }
-        if (C->data) (void)guarded_free(C->data);
-        if (C->col_ids) (void)guarded_free(C->col_ids);
-        if (C->row_offsets && C->row_offsets != c_ro) (void)guarded_free(C->row_offsets);
-        c_val = nv;
-        c_col = nc;
-    } else if (C->row_offsets && C->row_offsets != c_ro) {
-        (void)guarded_free(C->row_offsets);
+        C->rows = A->rows, C->cols = B->cols, C->nnz = nnz_c;
+        C->data = c_val, C->col_ids = c_col, C->row_offsets = c_ro;
+        own_ro = false;
+        t->allocC = st.lap();
+        t->loadBalanceNumeric = 0.f;
+        return SPECK_OK;
     }
-    // publish (Multiply.cu:1116-1121); from here C owns c_ro
-    C->rows = A->rows;
-    C->cols = B->cols;
-    C->nnz = nnz_c;
-    C->data = c_val;
-    C->col_ids = c_col;
-    C->row_offsets = c_ro;
-    own_ro = false;
-    // the staged offsets -> C.row_offsets: by extra workgroups of the numeric light launch when there is one, else by a
-    // copy of its own (enqueue_back)
-    CallForm staged;
-    staged.off_src = sc.offsets, staged.off_dst = c_ro, staged.off_n = m + 1;
-    t->allocC = st.lap();
-    t->loadBalanceNumeric = 0.f;
 
-
-    // NUMERIC (Multiply.cu:835-1014) + in-kernel sort (Multiply.cu:1028-1043)
-    c->last_g_products = c->h_stats->g_products;
-    if (c->profile_kernels) {
-        tm.ev_num = tm.ev;
-        (void)hipEventRecord(kernel_event(c, tm.ev++), s);
-    }
-    rc = enqueue_back<T>(c, s, A, B, sc, staged, c_col, static_cast<T*>(c_val), num_mask, c->h_stats->num.count, &tm);
-    if (rc != SPECK_OK) return rc;
-    ev_num_end = tm.ev;
-    if (c->profile_kernels) (void)hipEventRecord(kernel_event(c, tm.ev++), s);
-    // The reference may return before its kernels finish when measureCompleteTime is off
-    // (Multiply.cu:1082-1085) and relies on blocking streams to order later copies.  The
-    // pipeline streams here are non-blocking, so the call always returns with C complete.
-    if (c->spin_wait && !c->profile_kernels) {
-        launch_done(s, c->d_ticket, c->h_ticket_dev, c->d_stats, c->h_stats_dev);
-        rc = wait_ticket(c, s);
+    // NUMERIC (Multiply.cu:835-1014) + in-kernel sort (Multiply.cu:1028-1043), into the C adopt_output published
+    int numeric_two_phase()
+    {
+        // the staged offsets -> C.row_offsets: by extra workgroups of the numeric light launch when there is one, else by a
+        // copy of its own (enqueue_back)
+        CallForm staged;
+        staged.off_src = sc.offsets, staged.off_dst = C->row_offsets, staged.off_n = m + 1;
+        c->prev.g_products = c->h_stats->g_products;
+        int rc = timed_numeric([&] { return back(staged, C->col_ids, C->data, num_mask, c->h_stats->num.count); });
         if (rc != SPECK_OK) return rc;
-    } else {
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    t->spGEMMNumeric = st.lap();
-    }  // !walked && !through_ok
-    t->sorting = 0.f;  // sorting is fused into the numeric kernels
-    t->cleanup = 0.f;  // nothing to free: the arena persists
-
-    // remember what this call ran on: an identical next call may reuse its placement
-    c->last_was_walk = walked;
-    c->last_nf_entries = c->h_stats->nf_entries;
-    c->last_sym_mask = mask_of(c->h_stats->sym.count, SYM_CLASSES);
-    c->last_num_mask = num_mask;
-    c->last_max_row_nnz = c->h_stats->max_row_nnz_c;
-    c->last_max_row_ops = c->h_stats->max_row_ops;
-    std::memcpy(c->last_sym_counts, c->h_stats->sym.count, sizeof(c->last_sym_counts));
-    std::memcpy(c->last_num_counts, c->h_stats->num.count, sizeof(c->last_num_counts));
-    c->last_key = make_key<T>(c, A, B, C, s);
-    c->last_key_valid = true;
-    c->arena_key = c->last_key;
-    c->arena_key_valid = true;
-    c->arena_from_replay = false;
-    c->spec_valid = true;
-    c->spec_rows_a = A->rows;
-    c->spec_rows_b = B->rows;
-    // ... and where every row went: the scan kernel wrote the config's copy of the offsets as it went
-    c->pred_valid = keep_pred;
-    c->last_eager_stats = *c->h_stats;
-    if (through_missed) {
-        c->last.eager_through = -1;
-        if (!through_front) c->last.eager_speculated = -1;  // (what the batch was sized from did not hold)
+        // The reference may return before its kernels finish when measureCompleteTime is off
+        // (Multiply.cu:1082-1085) and relies on blocking streams to order later copies.  The
+        // pipeline streams here are non-blocking, so the call always returns with C complete.
+        if (c->spin_wait && !c->profile_kernels) {
+            launch_done(s, c->d_ticket, c->h_ticket_dev, c->d_stats, c->h_stats_dev);
+            rc = wait_ticket(c, s);
+            if (rc != SPECK_OK) return rc;
+        } else {
+            HIP_TRY(hipStreamSynchronize(s));
+        }
+        t->spGEMMNumeric = st.lap();
+        return SPECK_OK;
     }
 
-    rc = finish_complete();
-    if (rc != SPECK_OK) return rc;
-
-    if (c->profile_kernels) {
-        HIP_TRY(hipStreamSynchronize(s));
-        auto span = [&](size_t a, size_t b) {
-            float v = 0.f;
-            (void)hipEventElapsedTime(&v, c->kev[a], c->kev[b]);
-            return v;
-        };
-        publish_kernel_times(c, tm, ev_num_end);
-        if (t->measureAll) {
-            // the reference's eleven stage fields (Timings.h:7-18, filled at Multiply.cu:227-1073) from
-            // the kernel events: stages that are fused here report under the field of their role
-            t->countProducts = span(tm.ev_analysis, tm.ev_analysis_end);    // readOperations + symbolic binning: ONE kernel
-            t->loadBalanceCounting = 0.f;                                     //   since round 5 (stages.hip)
-            t->spGEMMCounting = c->last.sym_phase_ms;                          // symbolic launches
-            t->loadBalanceNumeric = c->last.scan_ms;                           // scan + numeric binning
-            t->spGEMMNumeric = c->last.num_phase_ms;                           // numeric launches ...
-            t->sorting = 0.f;                                                  // ... which sort in-kernel
+    // remember what this call ran on: the next call on the config is sized from it, an identical one may reuse its placement
+    void remember_call(bool walked, Attempt through)
+    {
+        t->sorting = 0.f;  // sorting is fused into the numeric kernels
+        t->cleanup = 0.f;  // nothing to free: the arena persists
+        LastCall& prev = c->prev;
+        prev.was_walk = walked;
+        prev.nf_entries = c->h_stats->nf_entries;
+        prev.sym_mask = mask_of(c->h_stats->sym.count, SYM_CLASSES);
+        prev.num_mask = num_mask;
+        prev.max_row_nnz = c->h_stats->max_row_nnz_c, prev.max_row_ops = c->h_stats->max_row_ops;
+        std::memcpy(prev.sym_counts, c->h_stats->sym.count, sizeof(prev.sym_counts));
+        std::memcpy(prev.num_counts, c->h_stats->num.count, sizeof(prev.num_counts));
+        c->last_key = c->arena_key = make_key<T>(c, A, B, C, s);
+        c->last_key_valid = c->arena_key_valid = true;
+        c->arena_from_replay = false;
+        prev.valid = true, prev.rows_a = A->rows, prev.rows_b = B->rows;
+        // ... and where every row went: the scan kernel wrote the config's copy of the offsets as it went
+        c->pred_valid = keep_pred;
+        prev.eager_stats = *c->h_stats;
+        if (through == Attempt::missed || through == Attempt::front_stands) {
+            c->last.eager_through = -1;
+            if (through == Attempt::missed) c->last.eager_speculated = -1;  // (what the batch was sized from did not hold)
         }
     }
-    if (t->measureAll) {
-        // same table the reference prints (Multiply.cu:1097-1113)
-        std::printf("spECK     initial mallocs = %f ms\n", t->init);
-        std::printf("spECK  count computations = %f ms\n", t->countProducts);
-        std::printf("spECK       load-balancer = %f ms\n", t->loadBalanceCounting);
-        std::printf("spECK      GlobalMaps Cnt = %f ms\n", t->globalMapsCounting);
-        std::printf("spECK     counting kernel = %f ms\n", t->spGEMMCounting);
-        std::printf("spECK        malloc mat C = %f ms\n", t->allocC);
-        std::printf("spECK   num load-balancer = %f ms\n", t->loadBalanceNumeric);
-        std::printf("spECK     init GlobalMaps = %f ms\n", t->globalMapsNumeric);
-        std::printf("spECK      numeric kernel = %f ms\n", t->spGEMMNumeric);
-        std::printf("spECK      Sorting kernel = %f ms\n", t->sorting);
-        std::printf("spECK             cleanup = %f ms\n", t->cleanup);
-        std::printf("--------------------------------------------------------------\n");
+
+    // the complete time, the times of the kernel events, the reference's table of stage times
+    int report_times()
+    {
+        const int rc = finish_complete();
+        if (rc != SPECK_OK) return rc;
+        if (c->profile_kernels) {
+            HIP_TRY(hipStreamSynchronize(s));
+            publish_kernel_times(c, tm, ev_num_end);
+            if (t->measureAll) {
+                // the reference's eleven stage fields (Timings.h:7-18, filled at Multiply.cu:227-1073) from
+                // the kernel events: stages that are fused here report under the field of their role
+                t->countProducts = c->last.analysis_ms;                            // readOperations + symbolic binning: ONE kernel
+                t->loadBalanceCounting = 0.f;                                     //   since round 5 (stages.hip)
+                t->spGEMMCounting = c->last.sym_phase_ms;                          // symbolic launches
+                t->loadBalanceNumeric = c->last.scan_ms;                           // scan + numeric binning
+                t->spGEMMNumeric = c->last.num_phase_ms;                           // numeric launches ...
+                t->sorting = 0.f;                                                  // ... which sort in-kernel
+            }
+        }
+        if (t->measureAll) {
+            // same table the reference prints (Multiply.cu:1097-1113)
+            const std::pair<const char*, float> rows[] = {
+                {"initial mallocs", t->init}, {"count computations", t->countProducts}, {"load-balancer", t->loadBalanceCounting},
+                {"GlobalMaps Cnt", t->globalMapsCounting}, {"counting kernel", t->spGEMMCounting}, {"malloc mat C", t->allocC},
+                {"num load-balancer", t->loadBalanceNumeric}, {"init GlobalMaps", t->globalMapsNumeric},
+                {"numeric kernel", t->spGEMMNumeric}, {"Sorting kernel", t->sorting}, {"cleanup", t->cleanup}};
+            for (const auto& r : rows) std::printf("spECK %19s = %f ms\n", r.first, r.second);
+            std::printf("--------------------------------------------------------------\n");
+        }
+        return SPECK_OK;
     }
-    return SPECK_OK;
+};
+
+// The dispatcher: argument checks, the product of an empty input, arena and zones, then the kinds of call in their order
+//  -- each attempt completes the call, does not apply, or misses and hands over to the next
+template <typename T>
+int multiply_impl(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, speck_dcsr* C,
+                  speck_timings* t)
+{
+    if (!c || !C) return SPECK_ERR_INVALID;
+    int rc = check_inputs(A, B);
+    if (rc != SPECK_OK) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    speck_timings local_t{};
+    if (!t) t = &local_t;
+    c->last = speck_stats{};
+    // reference: source/GPU/Multiply.cu:67-70
+    if (A->nnz == 0 || B->nnz == 0) {
+        C->nnz = 0;
+        return SPECK_OK;
+    }
+    hipStream_t s = main_stream(c);
+    if (t->measureCompleteTime) HIP_TRY(hipEventRecord(c->completeStart, s));
+    Call<T> k(c, A, B, C, t, s);
+    struct RestoreFlag {
+        int& flag;
+        int value;
+        ~RestoreFlag() { flag = value; }
+    } restore_profile{c->profile_kernels, c->profile_kernels};
+    if (t->measureAll) c->profile_kernels = 1;  // per-stage times come from per-launch events
+
+    rc = ensure_arena(c, scratch_bytes(k.m, A->nnz));
+    if (rc != SPECK_OK) return rc;
+    std::vector<GuardZone> carved;
+    k.sc = carve(c, k.m, A->nnz, guard_bytes() ? &carved : nullptr);
+    if (guard_bytes() && (c->zones_arena != c->arena || c->zones_m != k.m || c->zones_nnz != A->nnz || c->zones_gap != guard_bytes())) {
+        // (another layout of the arena than the one whose zones were filled last: canaries between ITS regions)
+        HIP_TRY(guard_fill(carved, s));
+        c->arena_zones = carved;
+        c->zones_arena = c->arena, c->zones_m = k.m, c->zones_nnz = A->nnz, c->zones_gap = guard_bytes();
+    }
+    c->snap_pending = false;
+    if (c->verify_inputs && c->overlap_analysis && c->reuse) ensure_snap(c, A->nnz, B->rows);
+    VerifierGuard verifier_guard{c};
+
+    Attempt how = Attempt::not_tried, walk = Attempt::not_tried, through = Attempt::not_tried;
+    rc = k.try_replay(how);
+    if (rc != SPECK_OK || how == Attempt::done) return rc;
+    rc = k.begin_complete();
+    if (rc != SPECK_OK) return rc;
+    rc = k.try_walk_hash(how);
+    if (rc != SPECK_OK || how == Attempt::done) return rc;
+    rc = k.try_one_walk(walk);
+    if (rc != SPECK_OK) return rc;
+    const bool walked = walk == Attempt::done;
+    if (!walked) rc = k.try_through(through);
+    if (rc != SPECK_OK) return rc;
+    if (!walked && through != Attempt::done) {
+        // the two-phase call: a front (the through call's if it stands, else a speculated batch, else the plain one with
+        // its read-backs), then on the host nnz(C), the spill pool and C, then the numeric launches
+        bool front_held = through == Attempt::front_stands, empty = false;
+        if (front_held) c->last.eager_speculated = 1;
+        if (through == Attempt::not_tried) rc = k.front_speculated(&front_held);
+        if (rc == SPECK_OK && !front_held) rc = k.front_two_phase();
+        if (rc == SPECK_OK) rc = k.settle_front(&empty);
+        if (rc != SPECK_OK || empty) return rc;
+        rc = k.size_spill_pool();
+        if (rc == SPECK_OK) rc = k.adopt_output();
+        if (rc == SPECK_OK) rc = k.numeric_two_phase();
+        if (rc != SPECK_OK) return rc;
+    }
+    k.remember_call(walked, through);
+    return k.report_times();
 }
 
 }  // namespace
@@ -2123,7 +2175,7 @@ int speck_config_set_option(speck_config* c, const char* name, int64_t value)
         c->nfpool = nullptr, c->nfpool_bytes = 0, c->nf_cap_entries = 0, c->nfpool_zones.clear();
         if (c->gpool) (void)guarded_free(c->gpool);
         c->gpool = nullptr, c->gpool_bytes = 0, c->gpool_zones.clear(), c->spill = SpillBuffers{};
-        c->spec_valid = false;
+        c->prev.valid = false;
         c->sort.release();
         c->masked.release();
         c->select.release();
