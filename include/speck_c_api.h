@@ -35,7 +35,13 @@ enum {
 /* ---- device CSR: field-for-field the reference's dCSR<T> / dCSRNoDealloc<T>
  *      (include/dCSR.h:9-35): rows, cols, nnz, data, row_offsets, col_ids.
  *      row_offsets has rows+1 entries; they may be ABSOLUTE offsets into
- *      col_ids/data of a larger matrix (a row-range view used for sharding). ---- */
+ *      col_ids/data of a larger matrix (a row-range view used for sharding).
+ *      Such a view may reach a last offset of 0xFFFFFFFF in every call that says
+ *      it takes one, except as A of speck_multiply_* (and of speck_analysis,
+ *      speck_symbolic, speck_partition_rows): row_offsets[0] + nnz > 2^32 - 2^16
+ *      is SPECK_ERR_INVALID there before any kernel starts, nothing written (the
+ *      walks over a row of A count in 32 bits and step by up to 2^11 entries;
+ *      DESIGN.md 4.18.1). ---- */
 typedef struct speck_dcsr {
     uint64_t rows, cols, nnz;
     void *data;             /* double* or float*  (device) */
@@ -328,7 +334,8 @@ int speck_multiply_masked_f32(speck_config *cfg, const speck_dcsr *A, const spec
  *      (data may be NULL).  A row of it that is not strictly ascending or holds an id >= cols: SPECK_ERR_UNSORTED (the
  *      remedy is speck_sort_rows_*, as for the mask of the masked product).  A and pattern may both be row-range views
  *      with absolute offsets.
- *  Offsets of A / pattern descending or leaving [row_offsets[0], row_offsets[0] + nnz], a column id of A >= cols, NULL
+ *  Offsets of A / pattern descending or leaving [row_offsets[0], row_offsets[0] + nnz], a last offset of A that is not
+ *      row_offsets[0] + nnz (as for speck_reduce_*: the declared nnz is what the rows hold), a column id of A >= cols, NULL
  *      buffers with nnz > 0, a NULL pattern or one of another shape, C sharing a buffer with A or pattern:
  *      SPECK_ERR_INVALID.  rows, cols <= 2^27 (SPECK_ERR_DIM_LIMIT), nnz < 2^32.
  *  Ownership of C as speck_multiply_* and speck_multiply_masked_* document it: row_offsets reused when C->rows == A->rows,
@@ -382,7 +389,7 @@ int speck_select_f32(speck_config *cfg, const speck_dcsr *A, const speck_select_
  *      atomics on values.  Subnormal results are kept.
  *  A and B under the multiply's rules for its B, checked with every call: a row of either that is not strictly ascending
  *      or holds an id >= cols: SPECK_ERR_UNSORTED (the remedy is speck_sort_rows_*).  Offsets descending or leaving
- *      [row_offsets[0], row_offsets[0] + nnz], rows(A) != rows(B) or cols(A) != cols(B), NULL buffers with nnz > 0, C sharing
+ *      [row_offsets[0], row_offsets[0] + nnz], a last offset that is not row_offsets[0] + nnz, rows(A) != rows(B) or cols(A) != cols(B), NULL buffers with nnz > 0, C sharing
  *      a buffer with A or B: SPECK_ERR_INVALID.  rows, cols <= 2^27 (SPECK_ERR_DIM_LIMIT).  nnz(A) + nnz(B) >= 2^32:
  *      SPECK_ERR_NNZ_OVERFLOW before anything runs -- conservative, an overlap might have fitted, but it is known without a
  *      device and keeps every count in 32 bits.  A and B may be the SAME matrix, and they may be row-range views with

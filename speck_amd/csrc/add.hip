@@ -45,7 +45,7 @@ struct AddStatus {
     u32 invalid;               // offsets of A / B
     u32 unsorted;              // a row of A / B not strictly ascending, or an id >= cols
     u32 base_a, base_b;        // row_offsets[0]
-    u32 entries_a, entries_b;  // row_offsets[rows] - row_offsets[0]: the entries the rows hold (<= nnz; the match bytes end there)
+    u32 entries_a, entries_b;  // row_offsets[rows] - row_offsets[0]: the entries the rows hold (== nnz, or the call is refused)
     unsigned long long both, nnz_out;
 };
 
@@ -264,14 +264,14 @@ int add_run(AddScratch* sc, hipStream_t s, double alpha, const speck_dcsr* A, do
     AddStatus h{};
     rc = read_status(s, st, &h);
     if (rc != SPECK_OK) return rc;
-    if (h.invalid) return SPECK_ERR_INVALID;
+    // (the last offset of each operand spans its nnz, as for speck_reduce_*)
+    if (h.invalid || h.entries_a != A->nnz || h.entries_b != B->nnz) return SPECK_ERR_INVALID;
     if (h.unsorted) return SPECK_ERR_UNSORTED;
 
     // ---- write
     const u64 nnz_out = h.nnz_out;
     rc = prepare_c(C, rows, nnz_out, sizeof(T), out);
     if (rc != SPECK_OK) return rc;
-    // (h.entries_x <= nnz(X), checked by the pass: entries of the buffers behind the last row have no match byte)
     const T *va = static_cast<const T*>(A->data), *vb_ = static_cast<const T*>(B->data);
     if (h.entries_a) {
         const KeepWord words{reinterpret_cast<const u32*>(match_a), h.entries_a};

@@ -236,8 +236,9 @@ __global__ __launch_bounds__(256) void masked_group_kernel(const MaskedArgs<T> g
         }
         wave_lds_fence();
         const u32 cmin = col[0], cmax = col[n - 1];  // (n >= 1: a row with work; no hit is marked yet)
-        for (u32 ab = a0; ab < a1; ab += L) {
-            const u32 nb = min(L, a1 - ab);
+        // (ab in 64 bits: a view may end at entry 2^32 - 1, and a u32 `ab += L` past it starts over at 0)
+        for (u64 ab = a0; ab < a1; ab += L) {
+            const u32 nb = min(L, (u32)(a1 - ab));
             u32 len = 0, b0 = 0;
             if (gl < nb) {
                 const u32 k = g.a_col[ab + gl];
@@ -362,8 +363,8 @@ __global__ __launch_bounds__(THREADS) void masked_lds_kernel(const MaskedArgs<T>
             }
         }
         const u32 cmin = col[0], cmax = col[n - 1];  // (no hit is marked before the barriers of the first batch)
-        for (u32 ab = a0; ab < a1; ab += THREADS) {
-            const u32 nb = min(THREADS, a1 - ab);
+        for (u64 ab = a0; ab < a1; ab += THREADS) {  // (64 bits: as in the group class)
+            const u32 nb = min(THREADS, (u32)(a1 - ab));
             u32 len = 0, b0 = 0;
             if (t < nb) {
                 const u32 k = g.a_col[ab + t];
@@ -435,8 +436,8 @@ __global__ __launch_bounds__(1024) void masked_global_kernel(const MaskedArgs<T>
         const u32* mc = g.m_col + m0;
         const size_t at0 = size_t(m0 - g.base_m);
         const u32 cmin = mc[0], cmax = mc[n - 1];
-        for (u32 ab = a0; ab < a1; ab += THREADS) {
-            const u32 nb = min(THREADS, a1 - ab);
+        for (u64 ab = a0; ab < a1; ab += THREADS) {  // (64 bits: as in the group class)
+            const u32 nb = min(THREADS, (u32)(a1 - ab));
             u32 len = 0, b0 = 0;
             if (t < nb) {
                 const u32 k = g.a_col[ab + t];

@@ -579,6 +579,32 @@ struct StageTimer {
     }
 };
 
+// The walks over a row of A (for_each_product, WindowCursors, the analysis' walk_entries, the register classes) count its
+// entries in u32 and step by up to 2^11 entries (the eight waves of the analysis, four tiles of 64 each): behind entry 2^32 - 1 such a counter starts
+// over at 0.  A row-range view of A whose entries reach the last 2^16 below 2^32 is therefore refused before any kernel
+// starts.  Entries that high exist only in an allocation that holds them: the runtime says how far col_ids reaches, and
+// row_offsets[0] is read back (4 bytes, the stream waited for) only where it reaches that far -- 16 GiB of column ids.
+constexpr u64 kViewTopMargin = 1ull << 16;
+
+int check_view_below_the_top(const speck_dcsr* A, hipStream_t s)
+{
+    constexpr u64 limit = (1ull << 32) - kViewTopMargin;
+    if (!A->rows || !A->nnz || !A->col_ids) return SPECK_OK;
+    if (A->nnz > limit) return SPECK_ERR_INVALID;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)A->col_ids) == hipSuccess) {
+        const u64 reach = (u64(reinterpret_cast<uintptr_t>(base)) + size - u64(reinterpret_cast<uintptr_t>(A->col_ids))) / 4;
+        if (reach <= limit) return SPECK_OK;
+    } else {
+        (void)hipGetLastError();  // (not an allocation the runtime knows: ask the offsets)
+    }
+    u32 first = 0;
+    HIP_TRY(hipMemcpyAsync(&first, A->row_offsets, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return u64(first) + A->nnz > limit ? SPECK_ERR_INVALID : SPECK_OK;
+}
+
 int check_inputs(const speck_dcsr* A, const speck_dcsr* B)
 {
     if (!A || !B) return SPECK_ERR_INVALID;
@@ -1908,6 +1934,8 @@ int multiply_impl(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, spe
         return SPECK_OK;
     }
     hipStream_t s = main_stream(c);
+    rc = check_view_below_the_top(A, s);
+    if (rc != SPECK_OK) return rc;
     if (t->measureCompleteTime) HIP_TRY(hipEventRecord(c->completeStart, s));
     Call<T> k(c, A, B, C, t, s);
     struct RestoreFlag {
@@ -2283,6 +2311,8 @@ int speck_analysis(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, ui
     if (rc != SPECK_OK) return rc;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = main_stream(c);
+    rc = check_view_below_the_top(A, s);
+    if (rc != SPECK_OK) return rc;
     c->arena_key_valid = false;  // (... and writes the arena)
     const u32 m = (u32)A->rows;
     if (m == 0 || A->nnz == 0 || B->nnz == 0) {
@@ -2325,6 +2355,8 @@ int speck_symbolic(speck_config* c, const speck_dcsr* A, const speck_dcsr* B, ui
     if (rc != SPECK_OK) return rc;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t s = main_stream(c);
+    rc = check_view_below_the_top(A, s);
+    if (rc != SPECK_OK) return rc;
     c->arena_key_valid = false;  // (... and writes the arena)
     const u32 m = (u32)A->rows;
     if (A->nnz == 0 || B->nnz == 0) {
@@ -2363,6 +2395,8 @@ int speck_partition_rows(speck_config* c, const speck_dcsr* A, const speck_dcsr*
     int rc = check_inputs(A, B);
     if (rc != SPECK_OK) return rc;
     HIP_TRY(hipSetDevice(c->device));
+    rc = check_view_below_the_top(A, main_stream(c));
+    if (rc != SPECK_OK) return rc;
     const u32 m = (u32)A->rows;
     rc = ensure_arena(c, scratch_bytes(m, A->nnz));
     if (rc != SPECK_OK) return rc;

@@ -42,7 +42,7 @@ struct SelectStatus {
     u32 unsorted;   // a pattern row
     u32 base_a;     // A.row_offsets[0]
     u32 unchanged;  // rows that kept every entry
-    u32 entries;    // A.row_offsets[rows] - A.row_offsets[0]: the entries the rows hold (<= nnz; the keep bytes end there)
+    u32 entries;    // A.row_offsets[rows] - A.row_offsets[0]: the entries the rows hold (== nnz, or the call is refused)
     unsigned long long kept, nnz_out;
 };
 
@@ -193,14 +193,13 @@ int select_run(SelectScratch* sc, hipStream_t s, const speck_dcsr* A, const spec
     SelectStatus h{};
     rc = read_status(s, st, &h);
     if (rc != SPECK_OK) return rc;
-    if (h.invalid) return SPECK_ERR_INVALID;
+    if (h.invalid || h.entries != A->nnz) return SPECK_ERR_INVALID;  // (the last offset spans nnz, as for speck_reduce_*)
     if (h.unsorted) return SPECK_ERR_UNSORTED;
 
     // ---- finish
     const u64 nnz_out = h.nnz_out;
     rc = prepare_c(C, rows, nnz_out, sizeof(T), out);
     if (rc != SPECK_OK) return rc;
-    // (h.entries <= nnz, checked by the pass: entries of the buffers behind the last row have no keep byte)
     const KeepWord words{reinterpret_cast<const u32*>(keep), h.entries};
     rc = finish_subset<T, T>(s, words, tile_sums, A->col_ids + h.base_a, static_cast<const T*>(A->data) + h.base_a, f.new_ro, rows,
                              A->cols, nnz_out, C, out);
