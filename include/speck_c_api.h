@@ -517,8 +517,8 @@ int speck_reduce_f32(speck_config *cfg, const speck_dcsr *A, int op, double *d_r
  *      SPECK_SCALE_TILE_ENTRIES, aligned to absolute positions as the reduction's; one path for every row length; l[i]
  *      is loaded once per row segment.  The 16-byte form needs data (and col_ids where read) on 16-byte boundaries and,
  *      out of place, row_offsets[0] a multiple of 4; elsewhere the entries go one by one, with the same results.
- *  Not built: pow and other libm maps (not bit-reproducible against numpy); sqrt modes (the vector is the caller's: a
- *      torch rsqrt_ on it is plumbing); per-row thresholds in speck_select_*; a scale fused into the product that made A;
+ *  Not built: pow and other libm maps (not bit-reproducible against numpy; the row softmax, exp included, is
+ *      speck_softmax_*); sqrt modes (the vector is the caller's: a torch rsqrt_ on it is plumbing); per-row thresholds in speck_select_*; a scale fused into the product that made A;
  *      vectors in float. ---- */
 enum { SPECK_MAP_IDENTITY = 0, SPECK_MAP_ABS = 1, SPECK_MAP_SQUARE = 2, SPECK_MAP_ONE = 3 };
 enum { SPECK_SCALE_NONE = 0, SPECK_SCALE_MUL = 1, SPECK_SCALE_DIV = 2 };
@@ -696,8 +696,8 @@ int speck_spmm_f32(speck_config *cfg, double alpha, const speck_dcsr *A, const d
  *  The entries are walked in tiles of SPECK_SDDMM_TILE_ENTRIES, aligned to absolute positions as the reduction's; one path
  *      for every row length.  The ids are loaded 16 bytes at a time where col_ids (and C's) lie on 16-byte boundaries,
  *      one by one elsewhere, with the same results.
- *  Not built: U^T / column-major or float blocks; a softmax or another map fused behind the dot; the product fused into
- *      speck_multiply_masked_*. ---- */
+ *  Not built: U^T / column-major or float blocks; a map fused behind the dot (the row softmax of the scores is the next
+ *      call, speck_softmax_*, in place on the same matrix); the product fused into speck_multiply_masked_*. ---- */
 #define SPECK_SDDMM_MAX_K 1024            /* = SPECK_SPMM_MAX_RHS */
 #define SPECK_SDDMM_TILE_ENTRIES 4096
 enum { SPECK_SDDMM_AXPBY = 0, SPECK_SDDMM_HADAMARD = 1 };
@@ -721,6 +721,89 @@ int speck_sddmm_f64(speck_config *cfg, const speck_dcsr *A, const speck_sddmm_pa
                     speck_sddmm_info *info /* may be NULL */);
 int speck_sddmm_f32(speck_config *cfg, const speck_dcsr *A, const speck_sddmm_params *p, speck_dcsr *C,
                     speck_sddmm_info *info);
+
+/* ---- row softmax (new: the reference has no counterpart): the softmax of every row over the entries the row holds, on a
+ *      matrix that is already on the device, and its backward -- the step between speck_sddmm_* (the edge scores) and
+ *      speck_spmm_* (the aggregation) of an attention layer on a graph (GAT, graph transformers, sparse attention with a
+ *      fixed pattern): sddmm -> softmax -> spmm runs on one device CSR, in place, and with SPECK_SOFTMAX_BACKWARD (sddmm
+ *      and spmm being each other's gradients) the layer can be trained.  The structure does not change, so C == NULL works
+ *      IN PLACE, as speck_scale_*.
+ *  Values: every step in double for both value types, each rounded on its own, nothing fused; ONE rounding to T at the end.
+ *      Forward, for an entry a of row i:  x = alpha * (double)a (first: any finite alpha of either sign is served);
+ *      m_i = the largest x of the row, as speck_reduce_*(MAX) combines (a NaN comes out; exact, so no tree matters);
+ *      e = exp(x - m_i), the device's double exp;  s_i = the sum of the row's e IN THE TREE OF speck_reduce_*(SUM) -- over
+ *      the absolute positions of the entries;  SPECK_SOFTMAX_NORMALIZED: p = e / s_i, the IEEE division;
+ *      SPECK_SOFTMAX_EXP: the result is e.  d_row_max[i] = m_i and d_row_sum[i] = s_i are written where the pointers are
+ *      given; a row without entries has m_i = -inf and s_i = +0.0, the reduction's identities.
+ *      SPECK_SOFTMAX_BACKWARD: A holds P, g = (double)d_G[q] for the entry at ABSOLUTE position q of A->data -- d_G is
+ *      indexed exactly as A->data, so for a row-range view the caller passes the owner's sibling array, not an offset one;
+ *      w = p * g;  r_i = the sum of the row's w in the same tree;  x = g - r_i;  x = p * x;  x = alpha * x.
+ *      d_row_sum[i] = r_i where given; d_row_max must be NULL.
+ *  What follows: the same bits from run to run, in place and out of place; a row-range view gives bit for bit the entries
+ *      and vector elements of the whole matrix's result; _f32 on A32 equals _f64 on the widened matrix, rounded to float;
+ *      the bits of an entry do not depend on whether the 16-byte or the entry-by-entry path served it.  For fp64:
+ *      d_row_max is bit for bit speck_reduce_f64(MAX) of speck_scale_f64(A, alpha); with E the EXP result, d_row_sum is
+ *      bit for bit speck_reduce_f64(E, SUM), and the NORMALIZED result is bit for bit speck_scale_f64(E, row = that, DIV):
+ *      only exp itself is left to a tolerance.  The backward is bit for bit numpy's (alpha * (p * (g - r[row]))).astype(T)
+ *      with r from speck_reduce_f64(SUM) of the matrix of the products p g in double.
+ *  Nothing is hidden, as torch.softmax: a -inf entry (a mask) gives e = 0, p = 0; a row of only -inf becomes NaN
+ *      (-inf - -inf); a +inf entry makes its whole row NaN; a NaN entry makes its row NaN and touches no other row;
+ *      alpha * a overflowing to +inf makes that row NaN.  info->nonfinite counts the results that are inf or NaN AFTER
+ *      the rounding to T; they do not make the call fail.  Structural: no entry is dropped, a result of 0.0 stays.  Rows
+ *      need not be sorted; duplicates are separate terms.  No floating-point atomic anywhere.
+ *  The vectors (DEVICE, A->rows doubles, double for both value types) are indexed by the row INSIDE A -- for a row-range
+ *      view the caller offsets the pointer, as for speck_scale_*.
+ *  In place (C == NULL): only A->data[row_offsets[0] .. row_offsets[0] + nnz) is written; row_offsets, col_ids, nnz and
+ *      the three pointers stay as they were; col_ids is not read and may be NULL or garbage.  On a row-range view only
+ *      the view's entries are touched: the owner's entries in front of and behind them keep their bytes.
+ *  Out of place: C receives A's pattern -- the offsets rebased to 0, col_ids copied bit for bit -- under the ownership
+ *      rule of speck_select_*: rows(C) == rows(A) keeps C->row_offsets, nnz(C) == nnz(A) keeps data / col_ids, anything
+ *      else is freed and re-allocated.
+ *  Refused before anything runs, SPECK_ERR_INVALID: NULL A or p; an unknown mode; reserved != 0; alpha NaN or infinite
+ *      (speck_scale_* refuses the NaN only); d_G NULL in BACKWARD with nnz > 0, or given in a forward mode; d_row_max
+ *      given in BACKWARD; any of d_G, d_row_max, d_row_sum equal to one of A's or C's three pointers, or to each other;
+ *      the ranges [d_row_max, + rows) and [d_row_sum, + rows) overlapping; C sharing a buffer with A; NULL row_offsets with
+ *      rows > 0; NULL data with nnz > 0; out of place, NULL col_ids with nnz > 0.  SPECK_ERR_DIM_LIMIT: rows or cols >
+ *      2^27.  SPECK_ERR_NNZ_OVERFLOW: nnz >= 2^32.  rows == 0 or nnz == 0 is valid.
+ *  Refused on the device, SPECK_ERR_INVALID: offsets descending, leaving [row_offsets[0], row_offsets[0] + nnz], or a last
+ *      offset that is not row_offsets[0] + nnz; out of place, a column id >= cols.
+ *  On any error NOTHING is written: not A->data, not C's buffers, not C's struct, not the two vectors (*info is zero once
+ *      the arguments have passed).  No offset is used as an address before it was checked: a checking pass (two kernels
+ *      out of place) raises its verdict in a status block, every kernel that writes -- the vectors included -- is queued
+ *      behind it and does nothing where it is raised, and the host reads the status ONCE, at the end.
+ *  Runs on the config's stream and returns complete.  Temporaries are three grow-only buffers of the config's own (not
+ *      the multiply's arena, not another operation's), released with it; cfg == NULL is allowed.  With the debug option
+ *      guard_bytes the canary zones of the temporaries and of C (in place: of A's buffers) are checked after the call.
+ *  The entries are walked in tiles of SPECK_SOFTMAX_TILE_ENTRIES, aligned to absolute positions as the reduction's.  A row
+ *      that lies whole inside one tile -- on everything but pathological inputs nearly every row -- is finished in the one
+ *      visit of its tile: data is read once and written once.  A row that leaves its tile (info->rows_split) gets its m_i
+ *      and s_i from the tile records in kernels of their own and its entries in a last visit of the tiles that hold a part
+ *      of such a row; no kernel waits on another workgroup.  The 16-byte form needs data (d_G; out of place col_ids) on
+ *      16-byte boundaries and, out of place, row_offsets[0] a multiple of 4.
+ *  Not built: log_softmax and the log-sum-exp vector; a column softmax (transpose, then softmax); the softmax fused into
+ *      speck_sddmm_* or speck_spmm_*; vectors in float; a per-row temperature; a pattern check of G inside the call (the
+ *      Python wrapper offers speck_compare_* first). ---- */
+enum { SPECK_SOFTMAX_NORMALIZED = 0, SPECK_SOFTMAX_EXP = 1, SPECK_SOFTMAX_BACKWARD = 2 };
+#define SPECK_SOFTMAX_TILE_ENTRIES 4096
+typedef struct speck_softmax_params {
+    uint32_t mode;                /* SPECK_SOFTMAX_* */
+    uint32_t reserved;            /* 0; anything else: SPECK_ERR_INVALID */
+    double alpha;                 /* the temperature: the softmax of alpha * A */
+    const void *d_G;              /* BACKWARD only: DEVICE, values of type T laid out as A->data; NULL otherwise */
+    double *d_row_max;            /* optional DEVICE out, A->rows doubles (the forward modes) */
+    double *d_row_sum;            /* optional DEVICE out, A->rows doubles (all modes; BACKWARD: r_i) */
+} speck_softmax_params;
+typedef struct speck_softmax_info {
+    uint64_t entries;             /* entries written = nnz */
+    uint64_t nonfinite;           /* ... of which the result, after rounding to T, is inf or NaN */
+    uint64_t rows_empty;          /* rows without an entry */
+    uint64_t rows_split;          /* rows whose entries lie in more than one tile */
+    uint64_t tiles;               /* entry tiles walked */
+} speck_softmax_info;
+int speck_softmax_f64(speck_config *cfg, const speck_dcsr *A, const speck_softmax_params *p, speck_dcsr *C /* NULL: in place */,
+                      speck_softmax_info *info /* may be NULL */);
+int speck_softmax_f32(speck_config *cfg, const speck_dcsr *A, const speck_softmax_params *p, speck_dcsr *C,
+                      speck_softmax_info *info);
 
 /* ---- row-sharded multi-GPU (new: the reference is single-GPU, source/Executor.cpp:25).  One process per GPU;
  *      rank p multiplies the row range [b_p, b_{p+1}) of A (a view with absolute offsets, boundaries from

@@ -20,4 +20,6 @@ from .api import (  # noqa: F401
     spmv, SpmvInfo, SPMV_TILE_ENTRIES,
     spmm, SpmmInfo, SPMM_MAX_RHS, SPMM_COLUMN_BLOCK,
     sddmm, sddmm_lanes, SddmmInfo, SDDMM_MAX_K, SDDMM_TILE_ENTRIES, SDDMM_AXPBY, SDDMM_HADAMARD, SDDMM_MODES,
+    softmax, softmax_backward, SoftmaxInfo, SOFTMAX_NORMALIZED, SOFTMAX_EXP, SOFTMAX_BACKWARD, SOFTMAX_MODES,
+    SOFTMAX_TILE_ENTRIES,
 )

@@ -109,6 +109,18 @@ class CSddmmInfo(C.Structure):
                 ("lanes", C.c_uint64)]
 
 
+class CSoftmaxParams(C.Structure):
+    # include/speck_c_api.h: speck_softmax_params
+    _fields_ = [("mode", C.c_uint32), ("reserved", C.c_uint32), ("alpha", C.c_double), ("d_G", C.c_void_p),
+                ("d_row_max", C.c_void_p), ("d_row_sum", C.c_void_p)]
+
+
+class CSoftmaxInfo(C.Structure):
+    # include/speck_c_api.h: speck_softmax_info
+    _fields_ = [("entries", C.c_uint64), ("nonfinite", C.c_uint64), ("rows_empty", C.c_uint64), ("rows_split", C.c_uint64),
+                ("tiles", C.c_uint64)]
+
+
 # every symbol include/speck_c_api.h declares, with its ctypes signature
 _P = C.POINTER
 _SIGS = {
@@ -158,6 +170,8 @@ _SIGS = {
                                  C.c_uint64, _P(CSpmmInfo)]),
     "speck_sddmm_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(CSddmmParams), _P(DCsr), _P(CSddmmInfo)]),
     "speck_sddmm_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(CSddmmParams), _P(DCsr), _P(CSddmmInfo)]),
+    "speck_softmax_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(CSoftmaxParams), _P(DCsr), _P(CSoftmaxInfo)]),
+    "speck_softmax_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(CSoftmaxParams), _P(DCsr), _P(CSoftmaxInfo)]),
     "speck_compare_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), C.c_int, C.c_double, _P(C.c_uint64)]),
     "speck_compare_bounded_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), _P(DCsr), C.c_double, _P(C.c_uint64),
                                             _P(C.c_uint64)]),

@@ -916,3 +916,89 @@ def sddmm(A, U, V, config, alpha=1.0, beta=0.0, mode="axpby", matOut=None, inpla
     ro = A._host_row_offsets   # (C's offsets are A's, from 0: the host copy is shared where A's start there)
     matOut._host_row_offsets = ro if ro is None or ro[0] == 0 else (ro - ro[0]).astype(np.uint32)
     return matOut, SddmmInfo(info)
+
+
+# include/speck_c_api.h: SPECK_SOFTMAX_*; the entries of a tile of the pass
+SOFTMAX_NORMALIZED, SOFTMAX_EXP, SOFTMAX_BACKWARD = range(3)
+SOFTMAX_MODES = {"normalized": SOFTMAX_NORMALIZED, "exp": SOFTMAX_EXP}
+SOFTMAX_TILE_ENTRIES = 4096
+
+
+class SoftmaxInfo(_Info):
+    """speck_softmax_info: what the row softmax wrote and walked."""
+    _fields = ("entries", "nonfinite", "rows_empty", "rows_split", "tiles")
+
+
+def _softmax_call(who, A, p, config, matOut, inplace):
+    """the call of softmax and softmax_backward behind their checks: in place, or into matOut (a new matrix when None)"""
+    L = _lib.load()
+    fn = L.speck_softmax_f32 if A.dtype == np.float32 else L.speck_softmax_f64
+    info = _lib.CSoftmaxInfo()
+    h = config._h if config is not None else None
+    if inplace:
+        _check(fn(h, C.byref(A._c), C.byref(p), None, C.byref(info)), who)
+        return A, SoftmaxInfo(info)
+    if matOut is None:
+        matOut = dCSR(A.dtype)
+    if matOut.dtype != A.dtype:
+        matOut.reset()
+        matOut.dtype = A.dtype
+    _check(fn(h, C.byref(A._c), C.byref(p), C.byref(matOut._c), C.byref(info)), who)
+    ro = A._host_row_offsets   # (C's offsets are A's, from 0: the host copy is shared where A's start there)
+    matOut._host_row_offsets = ro if ro is None or ro[0] == 0 else (ro - ro[0]).astype(np.uint32)
+    return matOut, SoftmaxInfo(info)
+
+
+def softmax(A, config, alpha=1.0, mode="normalized", matOut=None, inplace=False, row_max=None, row_sum=None):
+    """The softmax of every row of A over the entries the row holds (speck_softmax_f64 / _f32): p = exp(alpha a - m_i) / s_i
+    with m_i the row's largest alpha a and s_i the sum of the row's exp(alpha a - m_i); mode "exp" leaves the division out.
+    Every step in double, s_i in the tree of reduce(.., "sum"), one rounding to A's value type: the same bits from run to
+    run, in place or not, and a row_view gives the entries of the whole matrix's result bit for bit.  As torch.softmax, a
+    -inf entry (a mask) becomes 0, a row of only -inf becomes NaN, a +inf or a NaN makes its row NaN and touches no other;
+    such results are counted in info.nonfinite.  alpha is the temperature, any finite number.  row_max and row_sum
+    (A.rows float64 each, a device address or an object with data_ptr(); indexed by the row inside A, so for a row_view
+    pass the slice) receive m_i and s_i; a row without entries gets -inf and 0.0.  inplace=True overwrites A's values
+    (on a row_view: the view's entries only) and never reads col_ids; otherwise the result goes to matOut (a new matrix
+    when None) with A's pattern, offsets rebased to 0.  Rows need not be sorted, duplicates are separate terms.  The
+    scores of sddmm go in, the result goes into spmm.  config may be None.  Returns (matOut or A, SoftmaxInfo)."""
+    if isinstance(mode, str):
+        if mode not in SOFTMAX_MODES:
+            raise ValueError(f"softmax: unknown mode {mode!r} (one of {', '.join(SOFTMAX_MODES)})")
+        mode = SOFTMAX_MODES[mode]
+    elif isinstance(mode, bool) or mode not in SOFTMAX_MODES.values():
+        raise ValueError(f"softmax: unknown mode {mode!r}")
+    if inplace and matOut is not None:
+        raise ValueError("softmax: inplace=True and matOut exclude each other")
+    p = _lib.CSoftmaxParams()
+    p.mode, p.alpha = int(mode), float(alpha)
+    p.d_row_max = _device_vector(row_max, A.rows, "row_max", "softmax")
+    p.d_row_sum = _device_vector(row_sum, A.rows, "row_sum", "softmax")
+    return _softmax_call("softmax", A, p, config, matOut, inplace)
+
+
+def softmax_backward(P, G, config, alpha=1.0, matOut=None, inplace=False, row_sum=None, check_pattern=False, row_max=None):
+    """The gradient of softmax(A, alpha) with respect to A's values (speck_softmax_* with SPECK_SOFTMAX_BACKWARD): P is the
+    forward result, G the gradient with respect to it, a dCSR with P's rows, nnz and value type whose entries stand where
+    P's do (for a row_view of P: the same row_view of G's matrix).  Every entry becomes alpha p (g - r_i), r_i the sum of
+    the row's p g in the tree of reduce(.., "sum"), each step rounded to double on its own: bit for bit numpy's
+    (alpha * (p * (g - r[row]))).astype(dtype).  row_sum (P.rows float64) receives r_i.  The pattern of G is not
+    compared inside the call; check_pattern=True runs compare(P, G) on the structures first and raises ValueError on a
+    difference (it needs a config).  inplace=True overwrites P's values.  row_max is refused: the backward has no
+    maximum.  config may be None.  Returns (matOut or P, SoftmaxInfo)."""
+    if row_max is not None:
+        raise ValueError("softmax_backward: row_max belongs to the forward call (the backward has no maximum)")
+    if inplace and matOut is not None:
+        raise ValueError("softmax_backward: inplace=True and matOut exclude each other")
+    if not isinstance(G, dCSR):
+        raise ValueError(f"softmax_backward: G must be a dCSR with P's pattern, not {type(G).__name__}")
+    if (G.rows, G.nnz) != (P.rows, P.nnz):
+        raise ValueError(f"softmax_backward: G has {G.rows} rows and {G.nnz} entries, P has {P.rows} and {P.nnz}")
+    if G.dtype != P.dtype:
+        raise ValueError(f"softmax_backward: G holds {G.dtype}, P holds {P.dtype}")
+    if check_pattern and not compare(P, G, config, compare_data=False):
+        raise ValueError("softmax_backward: G does not have P's pattern")
+    p = _lib.CSoftmaxParams()
+    p.mode, p.alpha = SOFTMAX_BACKWARD, float(alpha)
+    p.d_G = G._c.data
+    p.d_row_sum = _device_vector(row_sum, P.rows, "row_sum", "softmax_backward")
+    return _softmax_call("softmax_backward", P, p, config, matOut, inplace)

@@ -238,6 +238,7 @@ struct speck_config {
     TileScratch spmv;  // ... and of speck_spmv_* (spmv.hip)
     TileScratch spmm;  // ... and of speck_spmm_* (spmm.hip): its own, a spmv after a wide spmm keeps its small buffers
     ScaleScratch sddmm;  // ... and of speck_sddmm_* (sddmm.hip): scale's pair of buffers, its own
+    TileScratch softmax;  // ... and of speck_softmax_* (softmax.hip): two sets of tile records, the m and s of the split rows
     const void* zones_arena = nullptr;
     u64 zones_m = 0, zones_nnz = 0, zones_gap = 0;
     bool gpool_zones_filled = false;
@@ -2003,6 +2004,7 @@ ScaleScratch* scale_scratch(speck_config* c) { return &c->scale; }
 TileScratch* spmv_scratch(speck_config* c) { return &c->spmv; }
 TileScratch* spmm_scratch(speck_config* c) { return &c->spmm; }
 ScaleScratch* sddmm_scratch(speck_config* c) { return &c->sddmm; }
+TileScratch* softmax_scratch(speck_config* c) { return &c->softmax; }
 }  // namespace speck
 
 extern "C" {
@@ -2124,6 +2126,7 @@ int speck_config_destroy(speck_config* c)
     c->spmv.release();
     c->spmm.release();
     c->sddmm.release();
+    c->softmax.release();
     if (c->pred.off) (void)guarded_free(c->pred.off);
     if (c->gpred.off) (void)guarded_free(c->gpred.off);
     if (c->d_stats) (void)hipFree(c->d_stats);
@@ -2213,6 +2216,7 @@ int speck_config_set_option(speck_config* c, const char* name, int64_t value)
         c->spmv.release();
         c->spmm.release();
         c->sddmm.release();
+        c->softmax.release();
     }
     else if (n == "sort_reg_max") c->sort.reg_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_REG_MAX);
     else if (n == "sort_lds_max") c->sort.lds_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_LDS_MAX);

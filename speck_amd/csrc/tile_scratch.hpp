@@ -1,5 +1,5 @@
-// tile_scratch.hpp -- what speck_reduce_*, speck_spmv_* and speck_spmm_* (reduce.hip, spmv.hip, spmm.hip) need from a
-// config (pipeline.hip owns the structure).
+// tile_scratch.hpp -- what speck_reduce_*, speck_spmv_*, speck_spmm_* and speck_softmax_* (reduce.hip, spmv.hip, spmm.hip,
+// softmax.hip) need from a config (pipeline.hip owns the structure).
 #pragma once
 #include "host_common.hpp"
 
@@ -10,7 +10,8 @@ namespace speck {
 // must not disturb the second one).  `fixed` is the status block; `var` the records of every entry tile -- one per tile,
 // k per tile for k right-hand sides -- and two row words per tile, sized from nnz before the first kernel; `sums` the row
 // sums of the two products, which wait for the verdict on the column ids (rows, rows k doubles; the reduction leaves it
-// empty).  The config holds one per operation: a spmv after a spmm of many columns keeps its small buffers.  Released
+// empty; the softmax keeps there the m and s of the rows that leave a tile where the caller takes no vector, 2 rows
+// doubles).  The config holds one per operation: a spmv after a spmm of many columns keeps its small buffers.  Released
 // with the config.
 struct TileScratch {
     DeviceBuffer fixed, var, sums;
@@ -20,5 +21,6 @@ struct TileScratch {
 TileScratch* reduce_scratch(speck_config* c);
 TileScratch* spmv_scratch(speck_config* c);
 TileScratch* spmm_scratch(speck_config* c);
+TileScratch* softmax_scratch(speck_config* c);
 
 }  // namespace speck
