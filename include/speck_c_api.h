@@ -577,7 +577,7 @@ int speck_scale_f32(speck_config *cfg, const speck_dcsr *A, const speck_scale_pa
  *  The entries are walked in tiles of SPECK_SPMV_TILE_ENTRIES, the reduction's, aligned to absolute positions; one path for
  *      every row length.  The 16-byte loads need data and col_ids on 16-byte boundaries; elsewhere the entries are loaded
  *      one by one, with the same results.
- *  Not built: A^T x (transpose, then spmv); vectors in float; a semiring other than (+, x); a spmv fused into the product
+ *  Not built (A^T x: speck_spmm_t_* below with k = 1): vectors in float; a semiring other than (+, x); a spmv fused into the product
  *      that made A.  (Several right-hand sides: speck_spmm_* below.) ---- */
 #define SPECK_SPMV_TILE_ENTRIES 4096
 typedef struct speck_spmv_info {
@@ -624,7 +624,7 @@ int speck_spmv_f32(speck_config *cfg, double alpha, const speck_dcsr *A, const d
  *      blocks of SPECK_SPMM_COLUMN_BLOCK whose gathers are in flight together -- one 16-byte load per entry and pair of
  *      columns where d_X lies on a 16-byte boundary and ldx is even, 8-byte loads elsewhere, with the same results.
  *  info: rows_empty, rows_split, tiles and entries as speck_spmv_info -- they describe A, not k.
- *  Not built: A^T X; column-major or float vectors; a semiring other than (+, x). ---- */
+ *  Not built (A^T X: speck_spmm_t_* below): column-major or float vectors; a semiring other than (+, x). ---- */
 #define SPECK_SPMM_MAX_RHS 1024
 #define SPECK_SPMM_COLUMN_BLOCK 4
 typedef struct speck_spmm_info {
@@ -804,6 +804,74 @@ int speck_softmax_f64(speck_config *cfg, const speck_dcsr *A, const speck_softma
                       speck_softmax_info *info /* may be NULL */);
 int speck_softmax_f32(speck_config *cfg, const speck_dcsr *A, const speck_softmax_params *p, speck_dcsr *C,
                       speck_softmax_info *info);
+
+/* ---- transposed product through a plan (new: the reference has no counterpart): Y = alpha A^T X + beta Y, the gradient of
+ *      speck_spmm_* with respect to X (dX = A^T dY) and of speck_sddmm_* with respect to V (dV = (dC)^T U) -- what the
+ *      backward pass of the attention layer above needs beside speck_softmax_*(BACKWARD).  In a training step the values
+ *      change every iteration and the pattern never does, so the work that depends on the pattern alone -- the stable sort
+ *      of the entries by column, speck_transpose_*'s -- is done ONCE, as a speck_tplan, and every call gathers the current
+ *      values through it.  No floating-point atomic: the entries of a column are added in the tree of speck_reduce_*(SUM).
+ *  THE PLAN holds four device arrays: t_ro[cols + 1], the offsets of A^T from 0; t_row[nnz], the row INSIDE A of the e-th
+ *      entry in column order; t_pos[nnz], that entry's position in A relative to row_offsets[0]; ro0[rows + 1], A's offsets
+ *      from 0.  Column order is speck_transpose_*'s: inside a column ascending position in A, duplicates of one (i,j) in
+ *      their input order.  A->data is not read and may be NULL: a plan belongs to a PATTERN and fits every matrix that has
+ *      it wherever its entries lie in their buffers -- a row-range view, its speck_dcsr_copy, the out-of-place result of
+ *      speck_scale_*, speck_sddmm_* or speck_softmax_* on it -- and both value types.
+ *  Unlike speck_transpose_* the creation CHECKS its input before it sorts or follows anything: offsets that descend or leave
+ *      [row_offsets[0], row_offsets[0] + nnz], a last offset that is not row_offsets[0] + nnz, a column id >= cols, NULL
+ *      buffers with nnz > 0: SPECK_ERR_INVALID, *out untouched, nothing left allocated.  Rows need not be sorted.  rows or
+ *      cols > 2^27: SPECK_ERR_DIM_LIMIT; nnz >= 2^32: SPECK_ERR_NNZ_OVERFLOW; a failed allocation: SPECK_ERR_OOM, nothing
+ *      leaked.  nnz == 0 and rows == 0 give valid plans.  Like speck_transpose_* the creation works on the NULL stream and
+ *      returns complete; cfg may be NULL.  After the creation a plan is only ever read: several calls, streams and configs
+ *      may use one.  speck_tplan_destroy(NULL) is SPECK_OK.
+ *  THE PRODUCT: X is rows x k, indexed by the row INSIDE A (for a row-range view the caller offsets the pointer by
+ *      r0 ldx), Y is cols x k, both row-major device arrays of doubles as for speck_spmm_* (ld >= k, padding never read
+ *      or written, 64-bit index arithmetic).  A ROW-RANGE VIEW GIVES THE PARTIAL SUM OF ITS ROWS, not rows of the whole
+ *      result: a row-sharded A^T X needs an all-reduce of the shards' Y, which is not built.
+ *  The defining property: for every c < k, column c of Y is BIT FOR BIT what speck_spmm_*(alpha, At, X, beta, Y) writes with
+ *      At = speck_transpose_*(A) -- the transpose keeps the order, the tree depends on the absolute positions in At->data
+ *      alone, and those start at 0 as the plan's do.  So per column: the term (double)a * X(i,c) rounded once, nothing
+ *      fused; the tree of speck_reduce_*(SUM); the same bits from run to run; beta == 0.0 does NOT READ Y; alpha is always
+ *      applied; a NaN or 0 * inf of X(i,c) lands in column c of exactly the rows j of Y with (i,j) in A; duplicates add.
+ *  THE PLAN IS VERIFIED, EXACTLY, IN EVERY CALL (a plan applied to another pattern would give plausible wrong numbers).
+ *      Before anything runs: plan == NULL, or rows, cols or nnz of A differing from the plan's: SPECK_ERR_INVALID.  On the
+ *      device the kernel queued first compares row_offsets[i] - row_offsets[0] with ro0[i] for all i, and the tile kernel
+ *      compares col_ids[base + t_pos[e]] with the column entry e lies in according to t_ro; t_pos is a bijection, so the
+ *      two together prove the patterns equal.  Any difference: SPECK_ERR_INVALID with NOTHING of Y written -- the column
+ *      sums wait in a temporary of cols k doubles, and only the kernel queued last, which has seen the verdict of every
+ *      tile, writes Y, each element once by one thread.  The call never follows an index of the caller's: t_pos < nnz and
+ *      t_row < rows are the library's, A's ids are only compared, and base is used only behind the offsets check.
+ *  Refused before anything runs beside that: alpha or beta NaN, ld < k, d_X or d_Y one of A's three arrays, the spans
+ *      [d_X, d_X + (rows - 1) ldx + k) and [d_Y, d_Y + (cols - 1) ldy + k) overlapping (spans that touch are served), NULL
+ *      where something would be read or written: SPECK_ERR_INVALID.  k > SPECK_SPMM_MAX_RHS, ld > 2^32: SPECK_ERR_DIM_LIMIT.
+ *      k == 0 or cols == 0: SPECK_OK, nothing written.  nnz == 0 gives Y = alpha * (+0.0) + beta * Y.
+ *  Config stream, ONE read-back at the end, cfg == NULL and the guard_bytes canary zones as for speck_spmm_*; the
+ *      temporaries are grow-only buffers of the config's own, not those of speck_spmm_*.
+ *  One workgroup per tile of SPECK_SPMV_TILE_ENTRIES plan entries, from 0; a thread loads 16 t_pos and 16 t_row with
+ *      16-byte loads, gathers its 16 values and ids through t_pos and takes the k columns in speck_spmm_*'s blocks.
+ *  info: cols_empty and cols_split describe A^T as rows_empty and rows_split of speck_spmm_info describe A.
+ *  Not built: a switch that trusts the plan and skips the verification; a transpose that only gathers values through a
+ *      plan; a column-side reduce or softmax; float blocks; a torch.autograd.Function; the sharded all-reduce. ---- */
+typedef struct speck_tplan speck_tplan;          /* opaque; owns its device buffers */
+typedef struct speck_tplan_info {
+    uint64_t rows, cols, nnz;     /* of the matrix the plan was made from */
+    uint64_t cols_empty;          /* columns without an entry */
+    uint64_t max_col_entries;     /* the longest column */
+    uint64_t bytes;               /* device memory the plan holds */
+} speck_tplan_info;
+int speck_tplan_create(speck_config *cfg, const speck_dcsr *A, speck_tplan **out, speck_tplan_info *info /* may be NULL */);
+int speck_tplan_destroy(speck_tplan *plan);      /* NULL is SPECK_OK */
+typedef struct speck_spmm_t_info {
+    uint64_t cols_empty;   /* columns of A without an entry: s(j,c) = +0.0 */
+    uint64_t cols_split;   /* columns whose entries lie in more than one tile of the plan */
+    uint64_t tiles;        /* tiles of the plan walked (each once, for all k) */
+    uint64_t entries;      /* = nnz */
+    uint64_t terms;        /* = entries * k */
+} speck_spmm_t_info;
+int speck_spmm_t_f64(speck_config *cfg, const speck_tplan *plan, double alpha, const speck_dcsr *A, const double *d_X,
+                     uint64_t ldx, uint32_t k, double beta, double *d_Y, uint64_t ldy, speck_spmm_t_info *info /* may be NULL */);
+int speck_spmm_t_f32(speck_config *cfg, const speck_tplan *plan, double alpha, const speck_dcsr *A, const double *d_X,
+                     uint64_t ldx, uint32_t k, double beta, double *d_Y, uint64_t ldy, speck_spmm_t_info *info);
 
 /* ---- row-sharded multi-GPU (new: the reference is single-GPU, source/Executor.cpp:25).  One process per GPU;
  *      rank p multiplies the row range [b_p, b_{p+1}) of A (a view with absolute offsets, boundaries from

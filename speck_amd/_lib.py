@@ -121,6 +121,18 @@ class CSoftmaxInfo(C.Structure):
                 ("tiles", C.c_uint64)]
 
 
+class CTplanInfo(C.Structure):
+    # include/speck_c_api.h: speck_tplan_info
+    _fields_ = [("rows", C.c_uint64), ("cols", C.c_uint64), ("nnz", C.c_uint64), ("cols_empty", C.c_uint64),
+                ("max_col_entries", C.c_uint64), ("bytes", C.c_uint64)]
+
+
+class CSpmmTInfo(C.Structure):
+    # include/speck_c_api.h: speck_spmm_t_info
+    _fields_ = [("cols_empty", C.c_uint64), ("cols_split", C.c_uint64), ("tiles", C.c_uint64), ("entries", C.c_uint64),
+                ("terms", C.c_uint64)]
+
+
 # every symbol include/speck_c_api.h declares, with its ctypes signature
 _P = C.POINTER
 _SIGS = {
@@ -172,6 +184,12 @@ _SIGS = {
     "speck_sddmm_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(CSddmmParams), _P(DCsr), _P(CSddmmInfo)]),
     "speck_softmax_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(CSoftmaxParams), _P(DCsr), _P(CSoftmaxInfo)]),
     "speck_softmax_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(CSoftmaxParams), _P(DCsr), _P(CSoftmaxInfo)]),
+    "speck_tplan_create": (C.c_int, [C.c_void_p, _P(DCsr), _P(C.c_void_p), _P(CTplanInfo)]),
+    "speck_tplan_destroy": (C.c_int, [C.c_void_p]),
+    "speck_spmm_t_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, _P(DCsr), C.c_void_p, C.c_uint64, C.c_uint32, C.c_double,
+                                   C.c_void_p, C.c_uint64, _P(CSpmmTInfo)]),
+    "speck_spmm_t_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, _P(DCsr), C.c_void_p, C.c_uint64, C.c_uint32, C.c_double,
+                                   C.c_void_p, C.c_uint64, _P(CSpmmTInfo)]),
     "speck_compare_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), C.c_int, C.c_double, _P(C.c_uint64)]),
     "speck_compare_bounded_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), _P(DCsr), C.c_double, _P(C.c_uint64),
                                             _P(C.c_uint64)]),

@@ -851,6 +851,111 @@ def spmm(A, X, config, alpha=1.0, beta=0.0, Y=None, k=None, ldx=None, ldy=None):
     return (_download_f64(buf, A.rows * k, "spmm").reshape(A.rows, k) if buf is not None else None), SpmmInfo(info)
 
 
+class TplanInfo(_Info):
+    """speck_tplan_info: the matrix a transpose plan was made from, its empty and longest columns, the plan's device bytes."""
+    _fields = ("rows", "cols", "nnz", "cols_empty", "max_col_entries", "bytes")
+
+
+class SpmmTInfo(_Info):
+    """speck_spmm_t_info: what the transposed product walked (the counts of A's columns, and terms = entries * k)."""
+    _fields = ("cols_empty", "cols_split", "tiles", "entries", "terms")
+
+
+class TransposePlan:
+    """speck_tplan: the pattern of a device matrix sorted by column once (speck_tplan_create), for any number of spmm_t /
+    spmv_t calls on matrices with that pattern -- the values may change between them, the plan is verified in every call.
+    `info` is a TplanInfo.  free() releases the device buffers (also at the end of a `with` block, and with the object);
+    a freed plan raises SpeckError where it is used."""
+
+    def __init__(self, A, config=None):
+        self._h = C.c_void_p()
+        info = _lib.CTplanInfo()
+        _check(_lib.load().speck_tplan_create(config._h if config is not None else None, C.byref(A._c), C.byref(self._h),
+                                              C.byref(info)), "transpose_plan")
+        self.info = TplanInfo(info)
+
+    def _handle(self, who):
+        if not self._h:
+            raise SpeckError(1, f"{who}: the plan was freed")
+        return self._h
+
+    def free(self):
+        if self._h:
+            h, self._h = self._h, C.c_void_p()
+            _check(_lib.load().speck_tplan_destroy(h), "TransposePlan.free")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.free()
+        return False
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def transpose_plan(A, config=None):
+    """The TransposePlan of A's pattern (A's values are not read).  The creation checks A -- offsets, every column id --
+    before it follows anything; unsound input raises SpeckError (SPECK_ERR_INVALID)."""
+    return TransposePlan(A, config)
+
+
+def spmm_t(A, X, config, plan=None, alpha=1.0, beta=0.0, Y=None, k=None, ldx=None, ldy=None):
+    """Y = alpha A^T X + beta Y on a device matrix through a TransposePlan (speck_spmm_t_f64 / _f32): X is A.rows x k
+    (indexed by the row inside A), Y is A.cols x k, row-major device blocks of float64 passed as spmm takes them.  Column c
+    of Y is bit for bit spmm(transpose(A), X, ...)'s, so all that spmm promises holds per column; a row_view gives the
+    partial sum of its rows.  The plan is verified against A in every call: another pattern raises SpeckError
+    (SPECK_ERR_INVALID) with nothing of Y written.  plan=None builds a plan for this one call and frees it -- a training
+    loop makes one with transpose_plan(A) and keeps it.  Y=None is allowed only with beta == 0: the result is then a
+    (cols, k) numpy array.  config may be None.  Returns (that array, or None where Y was given, SpmmTInfo)."""
+    return _spmm_t("spmm_t", A, X, config, plan, alpha, beta, Y, k, ldx, ldy)
+
+
+def _spmm_t(who, A, X, config, plan, alpha, beta, Y, k, ldx, ldy):
+    if Y is None and float(beta) != 0.0:
+        raise ValueError(f"{who}: beta != 0 needs a Y to read")
+    if plan is not None and not isinstance(plan, TransposePlan):
+        raise ValueError(f"{who}: plan must be a TransposePlan, not {type(plan).__name__}")
+    x_ptr, k, ldx = _device_block(X, A.rows, k, ldx, "X", who)
+    if Y is not None:
+        y_ptr, _, ldy = _device_block(Y, A.cols, k, ldy, "Y", who)
+    if k < 0 or ldx < k or (Y is not None and ldy < k):
+        raise ValueError(f"{who}: k = {k} with ldx = {ldx}, ldy = {ldy}: a leading dimension is at least k >= 0")
+    L = _lib.load()
+    fn = L.speck_spmm_t_f32 if A.dtype == np.float32 else L.speck_spmm_t_f64
+    own = None
+    if plan is None:
+        plan = own = TransposePlan(A, config)
+    try:
+        handle = plan._handle(who)
+        buf = None
+        if Y is None:
+            buf = _dev_f64(A.cols * k)
+            y_ptr, ldy = buf._c.data, k
+        info = _lib.CSpmmTInfo()
+        _check(fn(config._h if config is not None else None, handle, float(alpha), C.byref(A._c), x_ptr, ldx, k, float(beta),
+                  y_ptr, ldy, C.byref(info)), who)
+    finally:
+        if own is not None:
+            own.free()
+    return (_download_f64(buf, A.cols * k, who).reshape(A.cols, k) if buf is not None else None), SpmmTInfo(info)
+
+
+def spmv_t(A, x, config, plan=None, alpha=1.0, beta=0.0, y=None):
+    """y = alpha A^T x + beta y: spmm_t with k = 1 and ld = 1.  x (A.rows float64) and y (A.cols float64) are device vectors
+    as spmv takes them.  Returns (a numpy array of A.cols values, or None where y was given, SpmmTInfo)."""
+    if y is None and float(beta) != 0.0:
+        raise ValueError("spmv_t: beta != 0 needs a y to read")
+    x_ptr = _device_vector(x, A.rows, "x", "spmv_t")
+    y_ptr = _device_vector(y, A.cols, "y", "spmv_t")
+    out, info = _spmm_t("spmv_t", A, x_ptr if x_ptr is not None else 0, config, plan, alpha, beta, y_ptr, 1, 1, 1)
+    return (out.reshape(A.cols) if out is not None else None), info
+
+
 # include/speck_c_api.h: SPECK_SDDMM_*; the most columns U and V may have, and the entries of a tile of the pass
 SDDMM_AXPBY, SDDMM_HADAMARD = range(2)
 SDDMM_MODES = {"axpby": SDDMM_AXPBY, "hadamard": SDDMM_HADAMARD}

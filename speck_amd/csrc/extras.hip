@@ -1,4 +1,4 @@
-// extras.hip -- the two side utilities the reference driver uses around the hot path:
+// extras.hip -- the two side utilities the reference driver uses around the hot path, and the plan made of the second:
 //   * spECK::Compare   (reference source/GPU/Compare.cu:11-82) -- made strict: offsets and
 //     column ids bit-exact, values by relative tolerance
 //   * transpose for non-square A (reference source/GPU/Transpose.cu:10-117: a column histogram with global
@@ -7,6 +7,8 @@
 //     (column, position) pairs, hand-written for wave64 (8-bit digits, ranks from ballots, no atomics on the
 //     ordered path) -- the CSR order is by row, so a stable sort by column IS the transpose, rows ascending
 //     inside every output row, whatever the length of that row (hub columns included).  Outside the timed path.
+//   * speck_tplan_create / _destroy (no reference counterpart): that sort run once per PATTERN and kept as a
+//     permutation, for speck_spmm_t_* (spmm_t.hip, tplan.hpp) -- with the check of the input the transpose lacks
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -14,8 +16,11 @@
 
 #include <cmath>
 #include <cstdio>
+#include <new>
 
+#include "entry_tiles.hpp"
 #include "host_common.hpp"
+#include "tplan.hpp"
 
 using namespace speck;
 
@@ -328,6 +333,153 @@ int transpose_impl(const speck_dcsr* A, speck_dcsr* At)
     return SPECK_OK;
 }
 
+// ---- speck_tplan: the transpose's sort, kept as a permutation --------------------------------------------------
+// What the transpose computes and throws away -- where the e-th entry in column order lies in A -- is the plan of
+// speck_spmm_t_* (spmm_t.hip): the sort runs once per PATTERN, the values are gathered through it in every call.
+// Unlike the transpose the creation checks its input first: the offsets (entry_tiles.hpp), then every id against cols.
+// the workgroups of the creation's grid-stride kernels (the transpose's)
+constexpr u32 kPlanGrid = 2048;
+
+struct PlanStatus {
+    u32 invalid;  // the offsets
+    u32 bad_id;   // a column id >= cols
+    u32 max_col;  // the longest column
+    u32 pad_;
+    unsigned long long cols_empty;
+};
+
+// a thread per row: the family's offset check, and the offsets from 0 (written whatever the verdict: nobody follows them
+// before it was read)
+__global__ void plan_offsets_kernel(const u32* __restrict__ ro, u32 rows, u64 nnz, u32* __restrict__ ro0, PlanStatus* st)
+{
+    SPECK_POISON();
+    const u32 base = ro[0];
+    for (u64 r = u64(blockIdx.x) * blockDim.x + threadIdx.x; r < rows; r += u64(gridDim.x) * blockDim.x) {
+        bool empty;
+        if (!row_offsets_sound<kPlanTile>(ro, (u32)r, rows, base, nnz, 0u, nullptr, &empty)) st->invalid = 1;
+        ro0[r] = ro[r] - base;
+        if (r == rows - 1u) ro0[rows] = ro[rows] - base;
+    }
+}
+
+// behind a sound verdict on the offsets: col is A->col_ids + row_offsets[0]
+__global__ void plan_ids_kernel(const u32* __restrict__ col, u32 nnz, u32 cols, PlanStatus* st)
+{
+    SPECK_POISON();
+    bool bad = false;
+    for (u64 i = u64(blockIdx.x) * blockDim.x + threadIdx.x; i < nnz; i += u64(gridDim.x) * blockDim.x) bad |= col[i] >= cols;
+    if (bad) st->bad_id = 1;
+}
+
+// t_pos = the sorted payload, t_row = the row of that position; zeros from nnz to the end of the last tile
+__global__ void plan_fill_kernel(const u32* __restrict__ perm, const u32* __restrict__ row_of, u32 nnz, u64 padded,
+                                 u32* __restrict__ t_pos, u32* __restrict__ t_row)
+{
+    SPECK_POISON();
+    for (u64 i = u64(blockIdx.x) * blockDim.x + threadIdx.x; i < padded; i += u64(gridDim.x) * blockDim.x) {
+        const u32 src = i < nnz ? perm[i] : 0u;
+        t_pos[i] = src;
+        t_row[i] = i < nnz ? row_of[src] : 0u;
+    }
+}
+
+__global__ void plan_stats_kernel(const u32* __restrict__ t_ro, u32 cols, PlanStatus* st)
+{
+    SPECK_POISON();
+    u32 empty = 0, longest = 0;
+    for (u64 c = u64(blockIdx.x) * blockDim.x + threadIdx.x; c < cols; c += u64(gridDim.x) * blockDim.x) {
+        const u32 len = t_ro[c + 1] - t_ro[c];
+        empty += len == 0;
+        longest = max(longest, len);
+    }
+    empty = wave_reduce_add(empty);
+    longest = wave_reduce_max(longest);
+    if (lane_id() == 0) {
+        if (empty) atomicAdd(&st->cols_empty, (unsigned long long)empty);
+        if (longest) atomicMax(&st->max_col, longest);
+    }
+}
+
+int tplan_create_impl(const speck_dcsr* A, speck_tplan** out, speck_tplan_info* info)
+{
+    if (!A || !out) return SPECK_ERR_INVALID;
+    if (A->rows > (1ull << 27) || A->cols > (1ull << 27)) return SPECK_ERR_DIM_LIMIT;
+    if (A->nnz >= (1ull << 32)) return SPECK_ERR_NNZ_OVERFLOW;
+    if (A->rows && !A->row_offsets) return SPECK_ERR_INVALID;
+    if (A->nnz && (!A->col_ids || A->rows == 0 || A->cols == 0)) return SPECK_ERR_INVALID;
+    if (!device_present()) return SPECK_ERR_NO_DEVICE;
+    const u32 nnz = (u32)A->nnz, rows = (u32)A->rows, cols = (u32)A->cols;
+
+    // every allocation of the creation is released on every way out but the last
+    struct Held {
+        void* p = nullptr;
+        ~Held() { if (p) (void)hipFree(p); }
+    } mem, temp;
+    const size_t padded = plan_padded(nnz);
+    const size_t b_tro = up256((size_t(cols) + 1) * 4), b_ent = up256(padded * 4), b_ro0 = up256((size_t(rows) + 1) * 4);
+    const size_t plan_bytes = b_tro + 2 * b_ent + b_ro0;
+    HIP_TRY(hipMalloc(&mem.p, plan_bytes));
+    unsigned char* pb = static_cast<unsigned char*>(mem.p);
+    u32* t_ro = reinterpret_cast<u32*>(pb);
+    u32* t_row = reinterpret_cast<u32*>(pb + b_tro);
+    u32* t_pos = reinterpret_cast<u32*>(pb + b_tro + b_ent);
+    u32* ro0 = reinterpret_cast<u32*>(pb + b_tro + 2 * b_ent);
+    const size_t n4 = up256(size_t(nnz) * 4);
+    HIP_TRY(hipMalloc(&temp.p, 256 + (nnz ? 5 * n4 + size_t(256) * kRadixBlocks * 4 : 0)));
+    unsigned char* tb = static_cast<unsigned char*>(temp.p);
+    PlanStatus* st = reinterpret_cast<PlanStatus*>(tb);
+    HIP_TRY(hipMemset(st, 0, sizeof(PlanStatus)));
+    HIP_TRY(hipMemset(ro0, 0, 4));  // (no row: the one offset)
+
+    PlanStatus h{};
+    if (rows) {
+        hipLaunchKernelGGL(plan_offsets_kernel, dim3(grid_of((u64(rows) + 255) / 256, 8192)), dim3(256), 0, 0, A->row_offsets, rows,
+                           A->nnz, ro0, st);
+        HIP_TRY(hipMemcpy(&h, st, sizeof h, hipMemcpyDeviceToHost));
+        if (h.invalid) return SPECK_ERR_INVALID;
+    }
+    if (nnz == 0) {
+        HIP_TRY(hipMemset(t_ro, 0, (size_t(cols) + 1) * 4));
+    } else {
+        // (the offsets are sound: [base, base + nnz) is the matrix)
+        u32 base = 0;
+        HIP_TRY(hipMemcpy(&base, A->row_offsets, 4, hipMemcpyDeviceToHost));
+        hipLaunchKernelGGL(plan_ids_kernel, dim3(kPlanGrid), dim3(256), 0, 0, A->col_ids + base, nnz, cols, st);
+        HIP_TRY(hipMemcpy(&h, st, sizeof h, hipMemcpyDeviceToHost));
+        if (h.bad_id) return SPECK_ERR_INVALID;
+
+        // the transpose's sort of (column, position), word for word
+        u32* row_of = reinterpret_cast<u32*>(tb + 256);
+        u32* perm_a = reinterpret_cast<u32*>(tb + 256 + n4);
+        u32* perm_b = reinterpret_cast<u32*>(tb + 256 + 2 * n4);
+        u32* keys_a = reinterpret_cast<u32*>(tb + 256 + 3 * n4);
+        u32* keys_b = reinterpret_cast<u32*>(tb + 256 + 4 * n4);
+        u32* hist = reinterpret_cast<u32*>(tb + 256 + 5 * n4);
+        hipLaunchKernelGGL(expand_rows_kernel, dim3(grid_of((u64(rows) + 3) / 4, 8192)), dim3(256), 0, 0, A->row_offsets, rows, base,
+                           row_of);
+        hipLaunchKernelGGL(iota_kernel, dim3(kPlanGrid), dim3(256), 0, 0, perm_a, nnz);
+        HIP_TRY(hipMemcpyAsync(keys_a, A->col_ids + base, size_t(nnz) * 4, hipMemcpyDeviceToDevice, 0));
+        unsigned end_bit = 1;
+        while (end_bit < 32 && (1ull << end_bit) < cols) ++end_bit;
+        const int res = radix_sort_pairs(keys_a, perm_a, keys_b, perm_b, nnz, end_bit, hist);
+        hipLaunchKernelGGL(plan_fill_kernel, dim3(kPlanGrid), dim3(256), 0, 0, res ? perm_b : perm_a, row_of, nnz, (u64)padded, t_pos,
+                           t_row);
+        hipLaunchKernelGGL(offsets_from_sorted_kernel, dim3(kPlanGrid), dim3(256), 0, 0, res ? keys_b : keys_a, nnz, cols, t_ro);
+    }
+    if (cols) hipLaunchKernelGGL(plan_stats_kernel, dim3(grid_of((u64(cols) + 255) / 256, kPlanGrid)), dim3(256), 0, 0, t_ro, cols, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(&h, st, sizeof h, hipMemcpyDeviceToHost));
+    HIP_TRY(hipDeviceSynchronize());
+
+    speck_tplan* p = new (std::nothrow) speck_tplan{A->rows, A->cols, A->nnz, h.cols_empty, h.max_col, mem.p, plan_bytes,
+                                                     t_ro, t_row, t_pos, ro0};
+    if (!p) return SPECK_ERR_OOM;
+    mem.p = nullptr;  // (the plan's from here on)
+    if (info) *info = speck_tplan_info{A->rows, A->cols, A->nnz, h.cols_empty, h.max_col, plan_bytes};
+    *out = p;
+    return SPECK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -360,6 +512,19 @@ int speck_transpose_f64(speck_config* /*cfg*/, const speck_dcsr* A, speck_dcsr* 
 int speck_transpose_f32(speck_config* /*cfg*/, const speck_dcsr* A, speck_dcsr* At)
 {
     return transpose_impl<float>(A, At);
+}
+
+int speck_tplan_create(speck_config* /*cfg*/, const speck_dcsr* A, speck_tplan** out, speck_tplan_info* info)
+{
+    return tplan_create_impl(A, out, info);
+}
+
+int speck_tplan_destroy(speck_tplan* plan)
+{
+    if (!plan) return SPECK_OK;
+    const hipError_t e = hipFree(plan->mem);
+    delete plan;
+    return e == hipSuccess ? SPECK_OK : SPECK_ERR_HIP;
 }
 
 }  // extern "C"

@@ -239,6 +239,7 @@ struct speck_config {
     TileScratch spmm;  // ... and of speck_spmm_* (spmm.hip): its own, a spmv after a wide spmm keeps its small buffers
     ScaleScratch sddmm;  // ... and of speck_sddmm_* (sddmm.hip): scale's pair of buffers, its own
     TileScratch softmax;  // ... and of speck_softmax_* (softmax.hip): two sets of tile records, the m and s of the split rows
+    TileScratch spmm_t;  // ... and of speck_spmm_t_* (spmm_t.hip): the records of the plan's tiles, the column sums
     const void* zones_arena = nullptr;
     u64 zones_m = 0, zones_nnz = 0, zones_gap = 0;
     bool gpool_zones_filled = false;
@@ -2005,6 +2006,7 @@ TileScratch* spmv_scratch(speck_config* c) { return &c->spmv; }
 TileScratch* spmm_scratch(speck_config* c) { return &c->spmm; }
 ScaleScratch* sddmm_scratch(speck_config* c) { return &c->sddmm; }
 TileScratch* softmax_scratch(speck_config* c) { return &c->softmax; }
+TileScratch* spmm_t_scratch(speck_config* c) { return &c->spmm_t; }
 }  // namespace speck
 
 extern "C" {
@@ -2127,6 +2129,7 @@ int speck_config_destroy(speck_config* c)
     c->spmm.release();
     c->sddmm.release();
     c->softmax.release();
+    c->spmm_t.release();
     if (c->pred.off) (void)guarded_free(c->pred.off);
     if (c->gpred.off) (void)guarded_free(c->gpred.off);
     if (c->d_stats) (void)hipFree(c->d_stats);
@@ -2217,6 +2220,7 @@ int speck_config_set_option(speck_config* c, const char* name, int64_t value)
         c->spmm.release();
         c->sddmm.release();
         c->softmax.release();
+        c->spmm_t.release();
     }
     else if (n == "sort_reg_max") c->sort.reg_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_REG_MAX);
     else if (n == "sort_lds_max") c->sort.lds_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_LDS_MAX);

@@ -1,5 +1,5 @@
-// tile_scratch.hpp -- what speck_reduce_*, speck_spmv_*, speck_spmm_* and speck_softmax_* (reduce.hip, spmv.hip, spmm.hip,
-// softmax.hip) need from a config (pipeline.hip owns the structure).
+// tile_scratch.hpp -- what speck_reduce_*, speck_spmv_*, speck_spmm_*, speck_softmax_* and speck_spmm_t_* (reduce.hip,
+// spmv.hip, spmm.hip, softmax.hip, spmm_t.hip) need from a config (pipeline.hip owns the structure).
 #pragma once
 #include "host_common.hpp"
 
@@ -22,5 +22,6 @@ TileScratch* reduce_scratch(speck_config* c);
 TileScratch* spmv_scratch(speck_config* c);
 TileScratch* spmm_scratch(speck_config* c);
 TileScratch* softmax_scratch(speck_config* c);
+TileScratch* spmm_t_scratch(speck_config* c);
 
 }  // namespace speck
