@@ -873,6 +873,68 @@ int speck_spmm_t_f64(speck_config *cfg, const speck_tplan *plan, double alpha, c
 int speck_spmm_t_f32(speck_config *cfg, const speck_tplan *plan, double alpha, const speck_dcsr *A, const double *d_X,
                      uint64_t ldx, uint32_t k, double beta, double *d_Y, uint64_t ldy, speck_spmm_t_info *info);
 
+/* ---- device COO triplets to a device CSR and back (the reference converts on the host only: convert(CSR&, const COO&),
+ *      source/CSR.cpp:173-212).  The caller of a graph layer owns an edge list on the device -- a 2 x E int64 edge_index in
+ *      no particular order and perhaps E weights --, not a CSR: speck_from_coo_* is the way in without a trip through the
+ *      host, speck_to_coo the way out (the row index per entry that a CSR does not have).
+ *  speck_from_coo_*: row i of C holds exactly the triplets with row id i, IN INPUT ORDER (stable): with p the stable
+ *      argsort of the row ids, C.col_ids = col[p] and C.data = val[p] bit for bit (NaN payloads, -0.0 and subnormals are
+ *      kept), and row_offsets is the running sum of the ids' histogram from 0.  Rows are NOT sorted by column and duplicates
+ *      are kept: that is speck_sort_rows_*, one call away, and there is no flag for it here -- a second stage that can fail
+ *      after C was written would break the rule below.  data == NULL: every value is 1.0 (an unweighted edge list).
+ *  index_bytes 4: uint32_t ids; 8: int64_t ids (torch.long).  An 8-byte id is compared as an unsigned 64-bit number, so a
+ *      negative one and one whose upper word is not zero (2^32 + 3 does not pass as 3) are above every limit.
+ *  SPECK_ERR_INVALID with NOTHING written -- not C's struct, not its allocations, not the contents of buffers it would
+ *      reuse: a row id >= rows or a column id >= cols; index_bytes not 4 or 8; NULL id arrays with nnz > 0; nnz > 0 with
+ *      no row or no column; one of C's three buffers (as far as C declares them) overlapping an input array.  rows, cols
+ *      <= 2^27 (SPECK_ERR_DIM_LIMIT), nnz < 2^32 (SPECK_ERR_NNZ_OVERFLOW).  nnz == 0 is valid: every offset is 0.
+ *  One pass in tiles of SPECK_COO_TILE_ENTRIES checks every id (16-byte loads where both id arrays start on 16 bytes),
+ *      writes the u32 row keys -- clamped: no id is used as an address or a key before it was compared -- and decides
+ *      whether the row ids are already non-descending.  The host reads that verdict before anything of C is allocated.
+ *      Row ids in order (speck_to_coo's output, a row-sorted edge_index, anything exported from a CSR): NO sort; columns
+ *      and values are copied straight over, narrowed where 8 bytes wide.  Else: the stable radix sort of
+ *      speck_transpose_* on (row key, position), ceil(log2(rows) / 8) passes of 8 bits, and one gather through the
+ *      positions.  The offsets are the lower bounds of the rows in the sorted keys.  No atomic decides the order of two
+ *      entries and no floating-point atomic exists: the same bytes from run to run.
+ *  Ownership of C as speck_select_* documents it: row_offsets reused when C->rows == rows, data / col_ids re-allocated
+ *      only when C->nnz differs.  Runs on the config's stream (speck_config_set_stream is honoured: ids produced on that
+ *      stream need no synchronisation in front of the call) and returns with C complete.  Temporaries are grow-only
+ *      buffers of the config's own (not the multiply's arena), 16 bytes per entry and 1 MiB; cfg == NULL is allowed as
+ *      for speck_sort_rows_*.  With the debug option guard_bytes the canary zones of the temporaries and of C are checked
+ *      after the call.  Two read-backs: the verdict with the sorted flag, and the counters of info.
+ *  speck_to_coo: for entry e of row i INSIDE A, d_row_out[e - row_offsets[0]] = row_base + i; where d_col_out is given it
+ *      receives the column id widened to index_bytes.  Values are not touched -- the caller reads A->data from entry
+ *      row_offsets[0] on --, so this is ONE function for both value types.  A may be a row-range view with absolute
+ *      offsets; row_base is the global index of its first row.  Both outputs hold nnz indices of index_bytes each.
+ *  Refused with nothing written: offsets that descend or leave [row_offsets[0], row_offsets[0] + nnz] or whose last one
+ *      does not span nnz (as everywhere); where d_col_out is given, a column id >= cols; an output inside one of A's
+ *      buffers or the two outputs overlapping; row_base + rows exceeding 2^32 (index_bytes 4) or 2^63 (8); index_bytes
+ *      not 4 or 8; NULL d_row_out: SPECK_ERR_INVALID.  The limits are speck_from_coo_*'s.  rows == 0: SPECK_OK.
+ *  The checking kernel takes a thread per row and, for the ids, one streaming pass over the entries; the writing kernel
+ *      is queued behind it and does nothing where the verdict is raised: a wave takes 64 rows at a time, a lane each, a
+ *      row longer than 16 entries takes the whole wave, lanes striding its entries; the columns are widened in a streaming
+ *      pass.  ONE read-back, at the end.  Stream, cfg == NULL and guard_bytes as above.
+ *  Not built: a fused sort by column or sum of duplicates; COO with negative int32 sentinels; float16 values; CSC input
+ *      (speck_transpose_* afterwards); blocked or batched graphs. ---- */
+#define SPECK_COO_TILE_ENTRIES 2048
+typedef struct speck_dcoo {          /* field names of the reference's COO<T>, include/COO.h */
+    uint64_t rows, cols, nnz;
+    const void *data;                /* DEVICE, nnz values of T; NULL: every value is 1.0 */
+    const void *row_ids, *col_ids;   /* DEVICE, nnz indices each */
+    uint32_t index_bytes;            /* 4: uint32_t; 8: int64_t */
+} speck_dcoo;
+typedef struct speck_from_coo_info {
+    uint64_t entries;            /* = nnz */
+    uint64_t rows_empty;         /* rows of C without an entry */
+    uint64_t max_row_entries;    /* the longest row of C */
+    uint64_t sorted_input;       /* 1: the row ids were already non-descending -- nothing was sorted */
+    uint64_t sort_passes;        /* radix passes of 8 bits that ran: 0, or ceil(log2(rows) / 8) */
+} speck_from_coo_info;
+int speck_from_coo_f64(speck_config *cfg, const speck_dcoo *coo, speck_dcsr *C, speck_from_coo_info *info /* may be NULL */);
+int speck_from_coo_f32(speck_config *cfg, const speck_dcoo *coo, speck_dcsr *C, speck_from_coo_info *info);
+int speck_to_coo(speck_config *cfg, const speck_dcsr *A, uint32_t index_bytes, uint64_t row_base, void *d_row_out,
+                 void *d_col_out /* may be NULL */);
+
 /* ---- row-sharded multi-GPU (new: the reference is single-GPU, source/Executor.cpp:25).  One process per GPU;
  *      rank p multiplies the row range [b_p, b_{p+1}) of A (a view with absolute offsets, boundaries from
  *      speck_partition_rows) with a replicated B, then ONE exchange concatenates the shards on a root rank:

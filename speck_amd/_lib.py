@@ -133,6 +133,18 @@ class CSpmmTInfo(C.Structure):
                 ("terms", C.c_uint64)]
 
 
+class CDcoo(C.Structure):
+    # include/speck_c_api.h: speck_dcoo (reference COO<T>, include/COO.h) with the width of its indices
+    _fields_ = [("rows", C.c_uint64), ("cols", C.c_uint64), ("nnz", C.c_uint64), ("data", C.c_void_p),
+                ("row_ids", C.c_void_p), ("col_ids", C.c_void_p), ("index_bytes", C.c_uint32)]
+
+
+class CFromCooInfo(C.Structure):
+    # include/speck_c_api.h: speck_from_coo_info
+    _fields_ = [("entries", C.c_uint64), ("rows_empty", C.c_uint64), ("max_row_entries", C.c_uint64),
+                ("sorted_input", C.c_uint64), ("sort_passes", C.c_uint64)]
+
+
 # every symbol include/speck_c_api.h declares, with its ctypes signature
 _P = C.POINTER
 _SIGS = {
@@ -190,6 +202,9 @@ _SIGS = {
                                    C.c_void_p, C.c_uint64, _P(CSpmmTInfo)]),
     "speck_spmm_t_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, _P(DCsr), C.c_void_p, C.c_uint64, C.c_uint32, C.c_double,
                                    C.c_void_p, C.c_uint64, _P(CSpmmTInfo)]),
+    "speck_from_coo_f64": (C.c_int, [C.c_void_p, _P(CDcoo), _P(DCsr), _P(CFromCooInfo)]),
+    "speck_from_coo_f32": (C.c_int, [C.c_void_p, _P(CDcoo), _P(DCsr), _P(CFromCooInfo)]),
+    "speck_to_coo": (C.c_int, [C.c_void_p, _P(DCsr), C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]),
     "speck_compare_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), C.c_int, C.c_double, _P(C.c_uint64)]),
     "speck_compare_bounded_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), _P(DCsr), C.c_double, _P(C.c_uint64),
                                             _P(C.c_uint64)]),

@@ -956,6 +956,156 @@ def spmv_t(A, x, config, plan=None, alpha=1.0, beta=0.0, y=None):
     return (out.reshape(A.cols) if out is not None else None), info
 
 
+# include/speck_c_api.h: SPECK_COO_TILE_ENTRIES (the entries of a tile of from_coo's check pass); the limit on rows and cols
+COO_TILE_ENTRIES = 2048
+_DIM_MAX = 1 << 27
+_ID_BYTES = {"torch.int64": 8, "int64": 8, "torch.int32": 4, "int32": 4}
+_VALUE_TYPES = {"torch.float64": np.float64, "float64": np.float64, "torch.float32": np.float32, "float32": np.float32}
+
+
+class FromCooInfo(_Info):
+    """speck_from_coo_info: the entries grouped, the empty and the longest row, whether the row ids came in order (then
+    nothing was sorted) and the radix passes that ran."""
+    _fields = ("entries", "rows_empty", "max_row_entries", "sorted_input", "sort_passes")
+
+
+def _coo_array(v, what, who, types, nnz, width):
+    """What from_coo needs of one of its arrays, checked WITHOUT asking for its address: (object or address, entries, bytes per
+    entry or the value type).  A 1-D tensor of one of `types` with unit stride, or a device address with nnz and `width`."""
+    if hasattr(v, "data_ptr"):
+        kind = types.get(str(getattr(v, "dtype", None)))
+        if kind is None:
+            raise ValueError(f"{who}: {what} must be {' or '.join(t for t in types if '.' not in t)}, not {getattr(v, 'dtype', None)}")
+        if len(v.shape) != 1:
+            raise ValueError(f"{who}: {what} must have one dimension, not {len(v.shape)}")
+        if v.shape[0] > 1 and v.stride(0) != 1:
+            raise ValueError(f"{who}: {what} must be contiguous (stride {v.stride(0)})")
+        return v, int(v.shape[0]), kind
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise ValueError(f"{who}: {what} must be a tensor or a device address, not {type(v).__name__}")
+    if nnz is None or width is None:
+        raise ValueError(f"{who}: {what} is an address: pass nnz and {'index_bytes' if types is _ID_BYTES else 'dtype'}")
+    return int(v), int(nnz), width
+
+
+def _address(v):
+    return int(v.data_ptr()) if hasattr(v, "data_ptr") else v
+
+
+def _coo_shape(shape, who):
+    try:
+        rows, cols = (int(x) for x in shape)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: shape must be (rows, cols), not {shape!r}") from None
+    if not (0 <= rows <= _DIM_MAX and 0 <= cols <= _DIM_MAX):
+        raise ValueError(f"{who}: shape {(rows, cols)} is beyond the limit of {_DIM_MAX} rows and columns")
+    return rows, cols
+
+
+def from_coo(row, col, val, shape, config, dtype=None, canonical=False, sum_duplicates=False, matOut=None, nnz=None,
+             index_bytes=None, who="from_coo"):
+    """Device COO triplets grouped by row into a device CSR (speck_from_coo_f64 / _f32), stable: row i holds the triplets with
+    row id i in input order, bit for bit.  row and col are 1-D int64 or int32 tensors of one type (anything with data_ptr(),
+    shape, dtype and stride()), or device addresses with nnz and index_bytes (4: uint32, 8: int64); val is a float64 or
+    float32 tensor, an address with dtype, or None: every value is 1.0 in `dtype` (float64 by default).  shape is
+    (rows, cols).  An id out of range -- negative, >= its limit, an int64 beyond 32 bits -- raises SpeckError
+    (SPECK_ERR_INVALID) with matOut untouched.  Rows are not sorted by column and duplicates stay: canonical=True calls
+    sort_rows on the result, sum_duplicates=True (which implies it) merges equal columns.  config may be None.
+    Returns (matOut, FromCooInfo)."""
+    rows, cols = _coo_shape(shape, who)
+    r, n_r, w_r = _coo_array(row, "row", who, _ID_BYTES, nnz, index_bytes)
+    c, n_c, w_c = _coo_array(col, "col", who, _ID_BYTES, nnz, index_bytes)
+    if w_r != w_c or w_r not in (4, 8):
+        raise ValueError(f"{who}: row and col must hold ids of one width, 4 or 8 bytes (got {w_r} and {w_c})")
+    if n_r != n_c:
+        raise ValueError(f"{who}: row holds {n_r} ids, col {n_c}")
+    want = None
+    if dtype is not None:
+        try:
+            want = _VALUE_TYPES.get(str(dtype)) or np.dtype(dtype).type
+        except TypeError:
+            pass
+        if want not in (np.float64, np.float32):
+            raise ValueError(f"{who}: dtype must be float64 or float32, not {dtype}")
+    v = None
+    if val is not None:
+        v, n_v, vt = _coo_array(val, "val", who, _VALUE_TYPES, n_r, want if want is not None else np.float64)
+        if n_v != n_r:
+            raise ValueError(f"{who}: val holds {n_v} values for {n_r} ids")
+        if want is not None and vt is not want:
+            raise ValueError(f"{who}: val is {np.dtype(vt)}, dtype asks for {np.dtype(want)}")
+        want = vt
+    vtype = np.dtype(want if want is not None else np.float64)
+    if n_r >= 1 << 32:
+        raise ValueError(f"{who}: {n_r} entries; the limit is 2^32 - 1")
+    # ---- everything was checked: the addresses
+    coo = _lib.CDcoo()
+    coo.rows, coo.cols, coo.nnz, coo.index_bytes = rows, cols, n_r, w_r
+    coo.row_ids, coo.col_ids, coo.data = _address(r), _address(c), (_address(v) if v is not None else None)
+    L = _lib.load()
+    fn = L.speck_from_coo_f32 if vtype == np.float32 else L.speck_from_coo_f64
+    if matOut is None:
+        matOut = dCSR(vtype)
+    if matOut.dtype != vtype:
+        matOut.reset()
+        matOut.dtype = vtype
+    info = _lib.CFromCooInfo()
+    _check(fn(config._h if config is not None else None, C.byref(coo), C.byref(matOut._c), C.byref(info)), who)
+    matOut._host_row_offsets = None  # (row_offsets were rewritten on the device)
+    if canonical or sum_duplicates:
+        sort_rows(matOut, config, sum_duplicates=sum_duplicates)
+    return matOut, FromCooInfo(info)
+
+
+def from_edge_index(edge_index, val, shape, config, dtype=None, canonical=False, sum_duplicates=False, matOut=None):
+    """from_coo on a 2 x E int64 (or int32) tensor as graph libraries keep it: row 0 holds the row ids, row 1 the column ids.
+    The entries of a row must be adjacent (stride(1) == 1); the two rows may lie anywhere (any stride(0)): their two addresses
+    are passed, nothing is copied.  The other arguments and the result are from_coo's."""
+    who = "from_edge_index"
+    if not hasattr(edge_index, "data_ptr") or not hasattr(edge_index, "shape"):
+        raise ValueError(f"{who}: edge_index must be a tensor, not {type(edge_index).__name__}")
+    width = _ID_BYTES.get(str(getattr(edge_index, "dtype", None)))
+    if width is None:
+        raise ValueError(f"{who}: edge_index must be int64 or int32, not {getattr(edge_index, 'dtype', None)}")
+    if len(edge_index.shape) != 2 or edge_index.shape[0] != 2:
+        raise ValueError(f"{who}: edge_index must be 2 x E, not {tuple(edge_index.shape)}")
+    n = int(edge_index.shape[1])
+    if n > 1 and edge_index.stride(1) != 1:
+        raise ValueError(f"{who}: edge_index must hold the ids of a row side by side (stride(1) == 1, not {edge_index.stride(1)})")
+    _coo_shape(shape, who)
+    if val is not None and hasattr(val, "data_ptr"):
+        _coo_array(val, "val", who, _VALUE_TYPES, n, None)  # (refused before edge_index is asked for its address)
+    step = int(edge_index.stride(0)) * width
+    if step < 0:
+        raise ValueError(f"{who}: edge_index has a negative stride")
+    base = int(edge_index.data_ptr())
+    return from_coo(base, base + step, val, shape, config, dtype=dtype, canonical=canonical, sum_duplicates=sum_duplicates,
+                    matOut=matOut, nnz=n, index_bytes=width, who=who)
+
+
+def to_coo(A, config, index_dtype=None, cols=True, row_base=0):
+    """The row index of every entry of a device matrix, as torch tensors on A's device (speck_to_coo): entry e of row i inside
+    A gets row_base + i.  index_dtype is torch.int64 (the default) or torch.int32; cols=True also returns the column ids
+    widened to it.  Values are not touched: they are A's data from its first entry on.  A may be a row_view; row_base is the
+    global index of its first row.  Unsound offsets, or with cols=True an id >= A.cols, raise SpeckError (SPECK_ERR_INVALID).
+    config may be None.  Returns (row, col), col None where cols=False."""
+    import torch
+    index_dtype = torch.int64 if index_dtype is None else index_dtype
+    if index_dtype not in (torch.int64, torch.int32):
+        raise ValueError(f"to_coo: index_dtype must be torch.int64 or torch.int32, not {index_dtype}")
+    row_base = int(row_base)
+    limit = (1 << 63) if index_dtype is torch.int64 else (1 << 31)
+    if row_base < 0 or row_base + A.rows > limit:
+        raise ValueError(f"to_coo: row_base {row_base} + {A.rows} rows does not fit {index_dtype}")
+    device = torch.device("cuda", config.device) if config is not None else torch.device("cuda")
+    # (one index at least: a tensor without elements has no address, and the call wants one even where it writes nothing)
+    row = torch.empty(max(A.nnz, 1), dtype=index_dtype, device=device)
+    col = torch.empty(max(A.nnz, 1), dtype=index_dtype, device=device) if cols else None
+    _check(_lib.load().speck_to_coo(config._h if config is not None else None, C.byref(A._c), 8 if index_dtype is torch.int64 else 4,
+                                    row_base, row.data_ptr(), col.data_ptr() if cols else None), "to_coo")
+    return row[:A.nnz], (col[:A.nnz] if cols else None)
+
+
 # include/speck_c_api.h: SPECK_SDDMM_*; the most columns U and V may have, and the entries of a tile of the pass
 SDDMM_AXPBY, SDDMM_HADAMARD = range(2)
 SDDMM_MODES = {"axpby": SDDMM_AXPBY, "hadamard": SDDMM_HADAMARD}

@@ -20,6 +20,7 @@
 
 #include "entry_tiles.hpp"
 #include "host_common.hpp"
+#include "radix_pairs.hpp"
 #include "tplan.hpp"
 
 using namespace speck;
@@ -234,9 +235,13 @@ __global__ __launch_bounds__(kRadixThreads) void radix_scatter_kernel(const u32*
     }
 }
 
-// sorts (keys, vals) by the low `bits` bits of the keys; a/b are ping-pong buffers (the input is in a, the result
-// in the returned index: 0 = a, 1 = b)
-int radix_sort_pairs(u32* keys_a, u32* vals_a, u32* keys_b, u32* vals_b, u32 n, unsigned bits, u32* hist)
+static_assert(kRadixHistWords == size_t(256) * kRadixBlocks, "radix_pairs.hpp: the histogram its callers allocate");
+
+}  // namespace
+
+// sorts (keys, vals) by the low `bits` bits of the keys on stream `s`; a/b are ping-pong buffers (the input is in a, the
+// result in the returned index: 0 = a, 1 = b).  Declared in radix_pairs.hpp: coo.hip sorts row keys with it.
+int speck::radix_sort_pairs(u32* keys_a, u32* vals_a, u32* keys_b, u32* vals_b, u32 n, unsigned bits, u32* hist, hipStream_t s)
 {
     int cur = 0;
     for (unsigned shift = 0; shift < bits; shift += 8) {
@@ -244,14 +249,16 @@ int radix_sort_pairs(u32* keys_a, u32* vals_a, u32* keys_b, u32* vals_b, u32 n, 
         const u32* vi = cur ? vals_b : vals_a;
         u32* ko = cur ? keys_a : keys_b;
         u32* vo = cur ? vals_a : vals_b;
-        hipLaunchKernelGGL(radix_hist_kernel, dim3(kRadixBlocks), dim3(kRadixThreads), 0, 0, ki, n, shift, hist);
-        hipLaunchKernelGGL(radix_scan_kernel, dim3(1), dim3(1024), 0, 0, hist);
-        hipLaunchKernelGGL(radix_scatter_kernel, dim3(kRadixBlocks), dim3(kRadixThreads), 0, 0, ki, vi, n, shift,
+        hipLaunchKernelGGL(radix_hist_kernel, dim3(kRadixBlocks), dim3(kRadixThreads), 0, s, ki, n, shift, hist);
+        hipLaunchKernelGGL(radix_scan_kernel, dim3(1), dim3(1024), 0, s, hist);
+        hipLaunchKernelGGL(radix_scatter_kernel, dim3(kRadixBlocks), dim3(kRadixThreads), 0, s, ki, vi, n, shift,
                            (const u32*)hist, ko, vo);
         cur ^= 1;
     }
     return cur;
 }
+
+namespace {
 
 template <typename T>
 int compare_impl(const speck_dcsr* ref, const speck_dcsr* cmp, const speck_dcsr* scale, int compare_data,
@@ -322,7 +329,7 @@ int transpose_impl(const speck_dcsr* A, speck_dcsr* At)
     HIP_TRY(hipMemcpyAsync(keys_a, A->col_ids + base, size_t(nnz) * 4, hipMemcpyDeviceToDevice, 0));
     unsigned end_bit = 1;
     while (end_bit < 32 && (1ull << end_bit) < (cols ? cols : 1)) ++end_bit;
-    const int res = radix_sort_pairs(keys_a, perm_a, keys_b, perm_b, nnz, end_bit, hist);
+    const int res = radix_sort_pairs(keys_a, perm_a, keys_b, perm_b, nnz, end_bit, hist, nullptr);
     const u32* keys_out = res ? keys_b : keys_a;
     const u32* perm_out = res ? perm_b : perm_a;
     hipLaunchKernelGGL(transpose_gather_kernel<T>, dim3(2048), dim3(256), 0, 0, perm_out, row_of,
@@ -461,7 +468,7 @@ int tplan_create_impl(const speck_dcsr* A, speck_tplan** out, speck_tplan_info* 
         HIP_TRY(hipMemcpyAsync(keys_a, A->col_ids + base, size_t(nnz) * 4, hipMemcpyDeviceToDevice, 0));
         unsigned end_bit = 1;
         while (end_bit < 32 && (1ull << end_bit) < cols) ++end_bit;
-        const int res = radix_sort_pairs(keys_a, perm_a, keys_b, perm_b, nnz, end_bit, hist);
+        const int res = radix_sort_pairs(keys_a, perm_a, keys_b, perm_b, nnz, end_bit, hist, nullptr);
         hipLaunchKernelGGL(plan_fill_kernel, dim3(kPlanGrid), dim3(256), 0, 0, res ? perm_b : perm_a, row_of, nnz, (u64)padded, t_pos,
                            t_row);
         hipLaunchKernelGGL(offsets_from_sorted_kernel, dim3(kPlanGrid), dim3(256), 0, 0, res ? keys_b : keys_a, nnz, cols, t_ro);
