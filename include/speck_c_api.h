@@ -935,6 +935,79 @@ int speck_from_coo_f32(speck_config *cfg, const speck_dcoo *coo, speck_dcsr *C, 
 int speck_to_coo(speck_config *cfg, const speck_dcsr *A, uint32_t index_bytes, uint64_t row_base, void *d_row_out,
                  void *d_col_out /* may be NULL */);
 
+/* ---- sub-matrix by index (new: the reference has no counterpart): C = A(p, q) -- the rows of A a device index list
+ *      names, in the list's order, with every column id sent through a device map that renumbers or drops it.  A
+ *      mini-batch's induced subgraph A[nodes][:, nodes] with the vertices renumbered 0 .. m-1, a permutation P A P^T before
+ *      a triangle count or a Galerkin product, the four blocks of a coarse / fine splitting, the unsmoothed aggregation
+ *      A P with a piecewise constant P (a map that is not injective, then speck_sort_rows_* with SUM_DUPLICATES), a shard by
+ *      an arbitrary row set: one call each, nothing leaves the device.
+ *  d_row_index: n_rows indices into the rows INSIDE A (A may be a row-range view with absolute offsets), in any order,
+ *      REPEATS ALLOWED (sampling with replacement, hub duplication).  NULL: the rows 0 .. A->rows - 1 in order; then n_rows
+ *      must be A->rows.
+ *  d_col_map: A->cols entries; map[j] is the new id of column j, or "dropped".  It need be neither injective nor monotone.
+ *      NULL: identity; then out_cols must be A->cols.
+ *  index_bytes: the width of BOTH arrays, as for speck_from_coo_*.  8: int64_t (torch.long goes in as it is) -- any negative
+ *      map value means "dropped", a negative row index is refused.  4: uint32_t -- a map value of 0xFFFFFFFF means "dropped".
+ *  Row i of C is row p[i] of A without the dropped entries, IN INPUT ORDER, each column id replaced by map[id], each value
+ *      copied bit for bit (NaN payloads, -0.0 and subnormals survive); C->cols = out_cols; offsets start at 0.  Nothing is
+ *      sorted and duplicates stay -- rows of A need not be sorted or free of duplicates either.  The rows of C ascend where
+ *      those of A do and the map is monotone on what it keeps; otherwise speck_sort_rows_* is one call away (there is no flag
+ *      for it here: a second stage that can fail after C was written would break the rule below).  With
+ *          glen = ro[p+1] - ro[p];  G = [0, cumsum(glen)];  src = repeat(ro[p] - G[:-1], glen) + arange(G[-1])
+ *          m = map[col[src]];  keep = m is not "dropped"
+ *      C holds m[keep] and the bits of val[src][keep], and row i of it the kept entries among G[i] .. G[i+1] - 1.
+ *  SPECK_ERR_INVALID with NOTHING written -- not C's struct, not its allocations, not the contents of buffers it would reuse:
+ *      offsets of A that descend, leave [row_offsets[0], row_offsets[0] + nnz] or whose last one does not span nnz (all rows
+ *      are checked, as everywhere); a row index >= A->rows (8 bytes wide: compared as an unsigned 64-bit number, so a
+ *      negative one and 2^32 + 3 are above every limit); a map value that is neither "dropped" nor < out_cols (all A->cols
+ *      entries are checked, referenced or not); a column id >= A->cols in a GATHERED row, found before it indexes the map,
+ *      and without a map too (C must be a sound matrix) -- the ids of rows that are not gathered are NEVER READ, so a
+ *      matrix with a bad id in a row nobody asks for is served; index_bytes not 4 or 8; NULL buffers with a count > 0; a
+ *      NULL index with n_rows != A->rows; a NULL map with out_cols != A->cols; d_row_index or d_col_map overlapping one of
+ *      A's or C's buffers (spans, as for speck_to_coo); C sharing a buffer with A.  A->rows, A->cols, n_rows or out_cols >
+ *      2^27: SPECK_ERR_DIM_LIMIT.  The gathered rows holding 2^32 entries or more BEFORE the drop (repeats make that
+ *      possible), or A->nnz >= 2^32: SPECK_ERR_NNZ_OVERFLOW -- decided from a 64-bit sum before any 32-bit offset is used.
+ *      n_rows == 0 gives an empty C of out_cols columns; no gathered entry, or every one dropped, gives n_rows empty rows
+ *      (C owns buffers of one entry).  *info is zero once the arguments have passed, and again on an error.
+ *  Three passes, a read-back of the status block behind the first two.  CHECK: the rows of A, the indices and the map, a
+ *      thread each; the length of every gathered row -- 0 where its index or its own two offsets are unsound: clamped, never
+ *      followed -- and their 64-bit sum; the shared scan of the lengths gives the gross offsets G.  MARK: one workgroup per
+ *      tile of SPECK_EXTRACT_TILE_ENTRIES gathered ("gross") entries, four consecutive ones per thread, whatever the row
+ *      lengths -- a hub row repeated 1000 times is just many tiles; the tile's first row by one search in G, the following
+ *      ones from LDS; every id compared with A->cols before it indexes the map; a keep byte per entry and the kept entries
+ *      per row.  Without a map the pass checks the ids and writes nothing.  PLACE, after C's buffers were prepared: gross
+ *      order is output order, so an entry's place is the number of kept entries in front of it (the shared scan over the
+ *      keep bytes); every entry of C is written once by one thread.  Atomics run on integer counts only: the same bytes
+ *      from run to run.
+ *  Ownership of C as speck_select_* documents it: row_offsets reused when C->rows == n_rows, data / col_ids re-allocated
+ *      only when C->nnz differs.  There is no in-place mode.  Runs on the config's stream (speck_config_set_stream is
+ *      honoured: indices produced on that stream need no synchronisation in front of the call) and returns with C complete.
+ *      Temporaries are grow-only buffers of the config's own (not the multiply's arena): 16 bytes per output row, 1 byte per
+ *      gathered entry and 4 per tile; cfg == NULL is allowed as for speck_sort_rows_*.  With the debug option guard_bytes the
+ *      canary zones of the temporaries and of C are checked after the call.
+ *  Not built: the inverse map from a node list inside the C call (one scatter in the caller's framework: the Python
+ *      wrappers do it); a fused sort or sum of duplicates; in-place extraction; A(p, q) = B (scatter into a matrix);
+ *      hstack / vstack; per-row top-k; a plan that is reused across calls on one pattern. ---- */
+#define SPECK_EXTRACT_TILE_ENTRIES 4096
+typedef struct speck_extract_params {
+    uint64_t n_rows, out_cols;               /* rows and columns of C */
+    const void *d_row_index, *d_col_map;     /* DEVICE: n_rows indices / A->cols map values; either may be NULL */
+    uint32_t index_bytes;                    /* 4: uint32_t; 8: int64_t */
+} speck_extract_params;
+typedef struct speck_extract_info {
+    uint64_t rows_out;           /* rows of C = n_rows */
+    uint64_t rows_empty;         /* rows of C without an entry */
+    uint64_t gross;              /* entries of the gathered rows before the drop */
+    uint64_t nnz_out;            /* entries of C */
+    uint64_t dropped;            /* gross - nnz_out */
+    uint64_t cols_kept;          /* map entries that are not "dropped"; A->cols without a map */
+    uint64_t max_row_entries;    /* the longest row of C */
+} speck_extract_info;
+int speck_extract_f64(speck_config *cfg, const speck_dcsr *A, const speck_extract_params *p, speck_dcsr *C,
+                      speck_extract_info *info /* may be NULL */);
+int speck_extract_f32(speck_config *cfg, const speck_dcsr *A, const speck_extract_params *p, speck_dcsr *C,
+                      speck_extract_info *info);
+
 /* ---- row-sharded multi-GPU (new: the reference is single-GPU, source/Executor.cpp:25).  One process per GPU;
  *      rank p multiplies the row range [b_p, b_{p+1}) of A (a view with absolute offsets, boundaries from
  *      speck_partition_rows) with a replicated B, then ONE exchange concatenates the shards on a root rank:

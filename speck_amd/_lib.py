@@ -145,6 +145,18 @@ class CFromCooInfo(C.Structure):
                 ("sorted_input", C.c_uint64), ("sort_passes", C.c_uint64)]
 
 
+class CExtractParams(C.Structure):
+    # include/speck_c_api.h: speck_extract_params
+    _fields_ = [("n_rows", C.c_uint64), ("out_cols", C.c_uint64), ("d_row_index", C.c_void_p), ("d_col_map", C.c_void_p),
+                ("index_bytes", C.c_uint32)]
+
+
+class CExtractInfo(C.Structure):
+    # include/speck_c_api.h: speck_extract_info
+    _fields_ = [("rows_out", C.c_uint64), ("rows_empty", C.c_uint64), ("gross", C.c_uint64), ("nnz_out", C.c_uint64),
+                ("dropped", C.c_uint64), ("cols_kept", C.c_uint64), ("max_row_entries", C.c_uint64)]
+
+
 # every symbol include/speck_c_api.h declares, with its ctypes signature
 _P = C.POINTER
 _SIGS = {
@@ -205,6 +217,8 @@ _SIGS = {
     "speck_from_coo_f64": (C.c_int, [C.c_void_p, _P(CDcoo), _P(DCsr), _P(CFromCooInfo)]),
     "speck_from_coo_f32": (C.c_int, [C.c_void_p, _P(CDcoo), _P(DCsr), _P(CFromCooInfo)]),
     "speck_to_coo": (C.c_int, [C.c_void_p, _P(DCsr), C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "speck_extract_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(CExtractParams), _P(DCsr), _P(CExtractInfo)]),
+    "speck_extract_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(CExtractParams), _P(DCsr), _P(CExtractInfo)]),
     "speck_compare_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), C.c_int, C.c_double, _P(C.c_uint64)]),
     "speck_compare_bounded_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), _P(DCsr), C.c_double, _P(C.c_uint64),
                                             _P(C.c_uint64)]),

@@ -1106,6 +1106,128 @@ def to_coo(A, config, index_dtype=None, cols=True, row_base=0):
     return row[:A.nnz], (col[:A.nnz] if cols else None)
 
 
+# include/speck_c_api.h: SPECK_EXTRACT_TILE_ENTRIES (the gathered entries of a tile of extract's marking and placing passes)
+EXTRACT_TILE_ENTRIES = 4096
+
+
+class ExtractInfo(_Info):
+    """speck_extract_info: the rows of the result and the empty ones among them, the entries of the gathered rows before
+    the drop, the entries kept and dropped, the map entries that keep their column, and the longest row."""
+    _fields = ("rows_out", "rows_empty", "gross", "nnz_out", "dropped", "cols_kept", "max_row_entries")
+
+
+def _index_array(v, what, who, count, width):
+    """An index list or a column map of extract, checked WITHOUT asking for its address: (object or address, entries, bytes per
+    entry).  A 1-D int64 or int32 tensor with unit stride, or a device address with its count and index_bytes."""
+    if not hasattr(v, "data_ptr") and not isinstance(v, bool) and isinstance(v, (int, np.integer)) and (count is None or width is None):
+        raise ValueError(f"{who}: {what} is an address: pass {'n_rows and ' if what == 'rows' else ''}index_bytes")
+    return _coo_array(v, what, who, _ID_BYTES, count, width)
+
+
+def extract(A, rows=None, col_map=None, out_cols=None, config=None, matOut=None, canonical=False, sum_duplicates=False,
+            n_rows=None, index_bytes=None, who="extract"):
+    """C = A(rows, col_map) (speck_extract_f64 / _f32): row i of C is row rows[i] of the device matrix A -- any order,
+    repeats allowed, None: every row in order -- without the entries whose column the map drops, in input order, every column
+    id j replaced by col_map[j], every value copied bit for bit.  col_map holds A.cols entries: the new id, or "dropped"
+    (int64: any negative value; int32: -1); it need be neither injective nor monotone; None: identity.  rows and col_map are
+    1-D int64 or int32 tensors of one type (anything with data_ptr(), shape, dtype and stride()), or device addresses with
+    index_bytes (4: uint32, 8: int64) and, for rows, n_rows.  out_cols is C.cols: A.cols without a map, required with one.
+    An index >= A.rows, a map value >= out_cols, an id >= A.cols in a gathered row raise SpeckError (SPECK_ERR_INVALID) with
+    matOut untouched.  Nothing is sorted and duplicates stay: canonical=True calls sort_rows on the result,
+    sum_duplicates=True (which implies it) merges equal columns.  config may be None.  Returns (matOut, ExtractInfo)."""
+    r = m = None
+    w_r = w_m = None
+    n = A.rows
+    if rows is not None:
+        r, n, w_r = _index_array(rows, "rows", who, n_rows, index_bytes)
+    if col_map is not None:
+        m, n_m, w_m = _index_array(col_map, "col_map", who, A.cols, index_bytes)
+        if n_m != A.cols:
+            raise ValueError(f"{who}: col_map holds {n_m} entries for {A.cols} columns")
+        if out_cols is None:
+            raise ValueError(f"{who}: out_cols is required with a col_map")
+    if w_r is not None and w_m is not None and w_r != w_m:
+        raise ValueError(f"{who}: rows and col_map must hold ids of one width (got {w_r} and {w_m} bytes)")
+    width = w_r if w_r is not None else w_m if w_m is not None else 8
+    if width not in (4, 8):
+        raise ValueError(f"{who}: index_bytes must be 4 or 8, not {width}")
+    out_cols = A.cols if out_cols is None else int(out_cols)
+    if not (0 <= out_cols <= _DIM_MAX and 0 <= n <= _DIM_MAX):
+        raise ValueError(f"{who}: {n} rows x {out_cols} columns is beyond the limit of {_DIM_MAX} rows and columns")
+    # ---- everything was checked: the addresses
+    p = _lib.CExtractParams()
+    p.n_rows, p.out_cols, p.index_bytes = n, out_cols, width
+    p.d_row_index = _address(r) if r is not None else None
+    p.d_col_map = _address(m) if m is not None else None
+    L = _lib.load()
+    fn = L.speck_extract_f32 if A.dtype == np.float32 else L.speck_extract_f64
+    if matOut is None:
+        matOut = dCSR(A.dtype)
+    if matOut.dtype != A.dtype:
+        matOut.reset()
+        matOut.dtype = A.dtype
+    info = _lib.CExtractInfo()
+    _check(fn(config._h if config is not None else None, C.byref(A._c), C.byref(p), C.byref(matOut._c), C.byref(info)), who)
+    matOut._host_row_offsets = None  # (row_offsets were rewritten on the device)
+    if canonical or sum_duplicates:
+        sort_rows(matOut, config, sum_duplicates=sum_duplicates)
+    return matOut, ExtractInfo(info)
+
+
+def _inverse_map(ids, limit, who, what):
+    """The column map that sends ids[j] to j and drops every other column below `limit`, as a tensor of ids' type: ONE
+    scatter (plumbing; the C call takes the map, it does not build it).  ids: a 1-D int64 or int32 device tensor without
+    repeats, every id in [0, limit)."""
+    import torch
+    _coo_array(ids, what, who, _ID_BYTES, None, None)
+    if not isinstance(ids, torch.Tensor):
+        raise ValueError(f"{who}: {what} must be a torch tensor (the map is built with torch)")
+    k = int(ids.shape[0])
+    pos = torch.arange(k, dtype=ids.dtype, device=ids.device)
+    if k and bool(((ids < 0) | (ids >= limit)).any()):
+        raise ValueError(f"{who}: {what} holds an id outside [0, {limit})")
+    cmap = torch.full((limit,), -1, dtype=ids.dtype, device=ids.device)
+    at = ids.long()
+    cmap[at] = pos
+    if k and not bool((cmap[at] == pos).all()):      # a repeated id kept one of its positions, the other differs
+        raise ValueError(f"{who}: {what} holds an id more than once")
+    return cmap, k
+
+
+def gather_rows(A, rows, config=None, matOut=None):
+    """The rows of A the index list names, in its order, repeats allowed (scipy's A[rows]); the columns stay.  extract's
+    arguments and result."""
+    return extract(A, rows=rows, config=config, matOut=matOut, who="gather_rows")
+
+
+def select_columns(A, cols, config=None, matOut=None, canonical=False):
+    """scipy's A[:, cols] for a list without repeats (a repeated id is a ValueError): column cols[j] becomes column j, every
+    other column is dropped.  The entries of a row keep their input order; canonical=True sorts them by their new id."""
+    cmap, k = _inverse_map(cols, A.cols, "select_columns", "cols")
+    return extract(A, col_map=cmap, out_cols=k, config=config, matOut=matOut, canonical=canonical, who="select_columns")
+
+
+def induced_subgraph(A, nodes, config=None, matOut=None, canonical=True):
+    """A[nodes][:, nodes] with the vertices renumbered 0 .. len(nodes) - 1 in the order of the list, which holds no vertex
+    twice: the adjacency of a sampled mini-batch.  canonical=True (the default) sorts the rows, as the multiply wants them."""
+    cmap, k = _inverse_map(nodes, A.cols, "induced_subgraph", "nodes")
+    return extract(A, rows=nodes, col_map=cmap, out_cols=k, config=config, matOut=matOut, canonical=canonical, who="induced_subgraph")
+
+
+def permute(A, row_perm=None, col_perm=None, config=None, matOut=None, canonical=False):
+    """scipy's A[row_perm][:, col_perm]: row i of the result is row row_perm[i] of A, column j of it column col_perm[j] -- the
+    map is the inverse permutation.  None leaves that side as it is; P A P^T is permute(A, perm, perm).  The entries of a row
+    keep their input order: canonical=True sorts them by their new id."""
+    cmap = None
+    if col_perm is not None:
+        cmap, k = _inverse_map(col_perm, A.cols, "permute", "col_perm")
+        if k != A.cols:
+            raise ValueError(f"permute: col_perm holds {k} ids for {A.cols} columns")
+    if row_perm is not None and _coo_array(row_perm, "row_perm", "permute", _ID_BYTES, None, None)[1] != A.rows:
+        raise ValueError(f"permute: row_perm holds {row_perm.shape[0]} ids for {A.rows} rows")
+    return extract(A, rows=row_perm, col_map=cmap, out_cols=A.cols, config=config, matOut=matOut, canonical=canonical, who="permute")
+
+
 # include/speck_c_api.h: SPECK_SDDMM_*; the most columns U and V may have, and the entries of a tile of the pass
 SDDMM_AXPBY, SDDMM_HADAMARD = range(2)
 SDDMM_MODES = {"axpby": SDDMM_AXPBY, "hadamard": SDDMM_HADAMARD}

@@ -13,7 +13,8 @@
 //   general input          coo_positions_kernel, the tree's radix sort of (row key, position) on the call's stream
 //                          (radix_pairs.hpp; ceil(log2(rows) / 8) passes), coo_gather_kernel through the positions.
 //   coo_offsets_kernel     a thread per row: the lower bound of the row in the sorted keys = its offset.
-//   coo_stats_kernel       the rows without an entry and the longest row: the SECOND read-back, behind which C is published.
+//   offset_stats_kernel    (scan.hpp) the rows without an entry and the longest row: the SECOND read-back, behind which C is
+//                          published.
 //   to_coo_check_kernel    a thread per row: the family's offset check (entry_tiles.hpp); where columns were asked for,
 //                          one streaming pass over the ids of the entries [row_offsets[0], row_offsets[0] + nnz) against
 //                          cols; the first thread compares the outputs' spans with those entries, whose place only the
@@ -161,23 +162,6 @@ __global__ void coo_offsets_kernel(const u32* __restrict__ keys, u32 nnz, u32 ro
     }
 }
 
-__global__ void coo_stats_kernel(const u32* __restrict__ ro, u32 rows, CooStatus* st)
-{
-    SPECK_POISON();
-    u32 empty = 0, longest = 0;
-    for (u64 r = u64(blockIdx.x) * blockDim.x + threadIdx.x; r < rows; r += u64(gridDim.x) * blockDim.x) {
-        const u32 len = ro[r + 1] - ro[r];
-        empty += len == 0;
-        longest = max(longest, len);
-    }
-    empty = wave_reduce_add(empty);
-    longest = wave_reduce_max(longest);
-    if (lane_id() == 0) {
-        if (empty) atomicAdd(&st->rows_empty, (unsigned long long)empty);
-        if (longest) atomicMax(&st->max_row, longest);
-    }
-}
-
 template <typename I>
 void launch_check(hipStream_t s, const speck_dcoo* coo, u32* keys, CooStatus* st)
 {
@@ -259,7 +243,7 @@ int from_coo_run(CooScratch* sc, hipStream_t s, const speck_dcoo* coo, speck_dcs
     } else {
         HIP_TRY(hipMemsetAsync(out->ro, 0, (size_t(rows) + 1) * 4, s));
     }
-    if (rows) SPECK_LAUNCH(coo_stats_kernel, dim3(grid_of((u64(rows) + 255) / 256, kCooGrid)), dim3(256), 0, s, out->ro, rows, st);
+    if (rows) SPECK_LAUNCH(offset_stats_kernel, dim3(grid_of((u64(rows) + 255) / 256, kCooGrid)), dim3(256), 0, s, out->ro, rows, &st->max_row, &st->rows_empty);
     // ---- the counters: the second read-back, behind everything that fills C
     rc = read_status(s, st, &h);
     if (rc != SPECK_OK) return rc;
@@ -272,14 +256,6 @@ int from_coo_run(CooScratch* sc, hipStream_t s, const speck_dcoo* coo, speck_dcs
         info->sort_passes = (bits + 7) / 8;
     }
     return SPECK_OK;
-}
-
-// whether [p, p + plen) and [q, q + qlen) share a byte (a NULL span shares nothing)
-bool spans_overlap(const void* p, u64 plen, const void* q, u64 qlen)
-{
-    if (!p || !q) return false;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-    return a < b + std::max<u64>(qlen, 1) && b < a + std::max<u64>(plen, 1);
 }
 
 const char* const kFromGuardNames[5] = {"from_coo status", "from_coo keys and positions", "C.data", "C.col_ids", "C.row_offsets"};

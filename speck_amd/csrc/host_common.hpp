@@ -1,6 +1,6 @@
 // host_common.hpp -- what the host side of every entry point shares: the error macro, size and grid arithmetic, the
 // grow-only device buffer the side operations keep their temporaries in, two questions about an address a caller
-// passed (on_16_bytes, is_one_of), and the two questions an entry point asks of its config ("is there a device at all?"
+// passed (on_16_bytes, is_one_of, spans_overlap), and the two questions an entry point asks of its config ("is there a device at all?"
 // when none was given, "which stream?" when one was).  Light on purpose: dcsr.hip and extras.hip include it without the
 // launch machinery (launch.hpp, chain.hpp).
 #pragma once
@@ -61,6 +61,14 @@ inline bool on_16_bytes(const void* p) { return (reinterpret_cast<uintptr_t>(p) 
 
 // whether v is one of X's three arrays (a vector the caller passes may not be)
 inline bool is_one_of(const void* v, const speck_dcsr* X) { return v == X->data || v == X->col_ids || v == X->row_offsets; }
+
+// whether [p, p + plen) and [q, q + qlen) share a byte (a NULL span shares nothing): an array a caller passes against a buffer
+inline bool spans_overlap(const void* p, u64 plen, const void* q, u64 qlen)
+{
+    if (!p || !q) return false;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return a < b + std::max<u64>(qlen, 1) && b < a + std::max<u64>(plen, 1);
+}
 
 // an entry point called without a config: a config exists only where a device does, so nobody has asked yet
 inline bool device_present()

@@ -35,6 +35,7 @@
 #include "sort_rows.hpp"
 #include "tile_scratch.hpp"
 #include "coo.hpp"
+#include "extract.hpp"
 
 using namespace speck;
 
@@ -242,6 +243,7 @@ struct speck_config {
     TileScratch softmax;  // ... and of speck_softmax_* (softmax.hip): two sets of tile records, the m and s of the split rows
     TileScratch spmm_t;  // ... and of speck_spmm_t_* (spmm_t.hip): the records of the plan's tiles, the column sums
     CooScratch coo;  // ... and of speck_from_coo_* / speck_to_coo (coo.hip): the status block, the keys and buffers of the sort
+    ExtractScratch extract;  // ... and of speck_extract_* (extract.hip): the rows' lengths and offsets, the keep bytes
     const void* zones_arena = nullptr;
     u64 zones_m = 0, zones_nnz = 0, zones_gap = 0;
     bool gpool_zones_filled = false;
@@ -2010,6 +2012,7 @@ ScaleScratch* sddmm_scratch(speck_config* c) { return &c->sddmm; }
 TileScratch* softmax_scratch(speck_config* c) { return &c->softmax; }
 TileScratch* spmm_t_scratch(speck_config* c) { return &c->spmm_t; }
 CooScratch* coo_scratch(speck_config* c) { return &c->coo; }
+ExtractScratch* extract_scratch(speck_config* c) { return &c->extract; }
 }  // namespace speck
 
 extern "C" {
@@ -2134,6 +2137,7 @@ int speck_config_destroy(speck_config* c)
     c->softmax.release();
     c->spmm_t.release();
     c->coo.release();
+    c->extract.release();
     if (c->pred.off) (void)guarded_free(c->pred.off);
     if (c->gpred.off) (void)guarded_free(c->gpred.off);
     if (c->d_stats) (void)hipFree(c->d_stats);
@@ -2226,6 +2230,7 @@ int speck_config_set_option(speck_config* c, const char* name, int64_t value)
         c->softmax.release();
         c->spmm_t.release();
         c->coo.release();
+        c->extract.release();
     }
     else if (n == "sort_reg_max") c->sort.reg_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_REG_MAX);
     else if (n == "sort_lds_max") c->sort.lds_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_LDS_MAX);

@@ -7,6 +7,7 @@
 // F is a small functor passed by value: f(i) = the count of item i, i < n (never called beyond).  The counts are computed
 // twice rather than stored: they are a load or two each.  The sums are 32-bit -- the callers' totals are entries of a
 // matrix (< 2^32).  (The multiply's own scan, stages.hip, is another shape: one chained pass that also classifies.)
+// Beside them offset_stats_kernel: the rows without an entry and the longest row of offsets a call has made.
 #pragma once
 #include "device_common.hpp"
 #include "launch.hpp"
@@ -63,6 +64,26 @@ struct CountArray {
     const u32* count;
     __device__ u32 operator()(u32 i) const { return count[i]; }
 };
+
+// What a call reports about the rows behind such a scan (the conversion from COO, the extraction): the rows without an
+// entry and the longest row of the offsets ro[0 .. rows], a wave reduction and one integer atomic per wave and counter.
+static __global__ void offset_stats_kernel(const u32* __restrict__ ro, u32 rows, u32* __restrict__ longest_out,
+                                           unsigned long long* __restrict__ empty_out)
+{
+    SPECK_POISON();
+    u32 empty = 0, longest = 0;
+    for (u64 r = u64(blockIdx.x) * blockDim.x + threadIdx.x; r < rows; r += u64(gridDim.x) * blockDim.x) {
+        const u32 len = ro[r + 1] - ro[r];
+        empty += len == 0;
+        longest = max(longest, len);
+    }
+    empty = wave_reduce_add(empty);
+    longest = wave_reduce_max(longest);
+    if (lane_id() == 0) {
+        if (empty) atomicAdd(empty_out, (unsigned long long)empty);
+        if (longest) atomicMax(longest_out, longest);
+    }
+}
 
 // n >= 1 items; block_sums: (n + 1023) / 1024 words, left holding the scanned workgroup sums.  offsets_out: n + 1 words,
 // or nullptr -- the caller places the items itself, from the scanned sums (then total_out is not written either).
