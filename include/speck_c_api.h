@@ -1008,6 +1008,76 @@ int speck_extract_f64(speck_config *cfg, const speck_dcsr *A, const speck_extrac
 int speck_extract_f32(speck_config *cfg, const speck_dcsr *A, const speck_extract_params *p, speck_dcsr *C,
                       speck_extract_info *info);
 
+/* ---- per-row top-k (new: the reference has no counterpart; the "per-row top-k" the block above names): C = the k best
+ *      entries of every row of a matrix that is already on the device.  speck_select_* cuts by a threshold, a predicate on
+ *      one entry; "the k largest of my row" is a predicate on the row.  The pruning of an MCL iteration (multiply -> topk ->
+ *      scale(map = square) -> normalize_rows), a kNN or similarity graph from speck_sddmm_* scores, top-k sparse attention
+ *      in front of speck_softmax_*, the strength-of-connection cut of an AMG setup, "at most k neighbours per vertex" in
+ *      front of a sampled mini-batch: one call, nothing leaves the device.
+ *  The KEY of an entry with the value v, widened to double: v (SPECK_TOPK_LARGEST), -v (SPECK_TOPK_SMALLEST), |v|
+ *      (SPECK_TOPK_LARGEST_ABS).  A NaN ranks ABOVE every number in every mode: the call never drops one silently in favour
+ *      of a number (speck_select_* keeps a NaN too; torch.topk ranks it the same way).  -0.0 and +0.0 are equal keys.
+ *      Entry e of a row BEATS entry e' of the same row if its key is larger, or if the keys are equal and e comes first in
+ *      the row.  An entry is KEPT iff fewer than k entries of its row beat it.  So a row of at most k entries is kept whole,
+ *      a row of more than k keeps exactly k; k == 0 gives A->rows empty rows; a k of 2^32 or more keeps every row whole.
+ *  Kept entries stay IN INPUT ORDER -- ascending rows stay ascending: a canonical A gives a C that speck_multiply_* accepts
+ *      --, column ids and values are copied bit for bit (NaN payloads, -0.0 and subnormals survive); C->cols = A->cols; the
+ *      offsets of C start at 0.  Rows need not be sorted or free of duplicates; nothing is merged.  As numpy, per row:
+ *          order = np.lexsort((pos, -key, ~isnan));  kept = np.sort(order[:k])
+ *      (tests/test_topk_host.py states it as numpy_topk and compares it with a count of beaters).
+ *  A may be a row-range view with absolute offsets: the rows of the view's result are the rows of the whole matrix's
+ *      result, bit for bit.  _f32 gives the structure of the _f64 call on the widened matrix and the float bits (widening is
+ *      monotone and one-to-one: the kernels rank 32-bit keys).  Keys are order-preserving unsigned integers; atomics run on
+ *      integer counts only, there is no floating-point atomic and no floating-point arithmetic at all: the same bytes from
+ *      run to run.
+ *  *info: rows_cut = the rows longer than k; dropped = entries_in - nnz_out; ties_cut = the rows in which a dropped entry has
+ *      the key of a kept one (the tie rule decided there); nan_kept = the NaN entries of C; max_row_entries = the longest row
+ *      of C.  *info is zero once the arguments have passed, and again on an error.
+ *  SPECK_ERR_INVALID with NOTHING written -- not C's struct, not its allocations, not the contents of buffers it would reuse:
+ *      offsets that descend, leave [row_offsets[0], row_offsets[0] + nnz] or whose last one does not span nnz; a column id >=
+ *      A->cols ANYWHERE in A (C must be a sound matrix); mode not one of the three; reserved != 0; NULL A, p or C; NULL
+ *      buffers with a count > 0; C sharing a buffer with A.  A->rows or A->cols > 2^27: SPECK_ERR_DIM_LIMIT.  A->nnz >= 2^32:
+ *      SPECK_ERR_NNZ_OVERFLOW.  No offset is used as an address before it has been checked.
+ *  CHECK AND CLASSIFY: one pass over row_offsets and col_ids; min(len, k) per row, which the shared scan turns into C's
+ *      offsets -- they depend on the lengths alone: there is no marking pass and no keep byte; the rows longer than k go to
+ *      lists by length.  ONE read-back (the verdict, nnz(C), the lists) before C is allocated; every kernel that writes C
+ *      starts after it.  Rows of at most k entries: a streaming copy that knows nothing of keys -- on a matrix without a
+ *      longer row the call is that copy.  Rows of up to SPECK_TOPK_GROUP_MAX entries: a group of 8 / 16 / 32 / 64 lanes (up
+ *      to GROUP_MAX / 8, / 4, / 2, GROUP_MAX entries) counts for every entry the entries that beat it.  Rows of up to
+ *      SPECK_TOPK_LDS_MAX entries: one workgroup, the keys in LDS, a radix select from the most significant byte (a histogram
+ *      of 256 bins per pass; it stops where the narrowed set is exactly what is still needed) for the threshold key and the
+ *      number of its equals to keep, then one ordered walk.  Longer rows: the same select and walk with the values read
+ *      again from global memory in every pass -- nothing is moved, there is no temporary.  At most one more read-back at the
+ *      end, for ties_cut and nan_kept (none with info == NULL).
+ *  Ownership of C, the stream, cfg == NULL, guard_bytes and the grow-only scratch of the config's own (20 bytes per row) as
+ *      speck_select_* / speck_extract_* document them.  There is no in-place mode.  The debug options topk_group_max and
+ *      topk_lds_max (clamped to the two defines) lower the class limits: every class gives the same bytes.
+ *  Not built: a per-row k from a device array; a threshold or cumulative-mass cut fused in; the row's threshold key returned
+ *      as a vector; top-k per column (speck_transpose_* first); in-place; a hub row split over several workgroups; top-k
+ *      fused behind speck_sddmm_* or the product. ---- */
+enum { SPECK_TOPK_LARGEST = 0, SPECK_TOPK_SMALLEST = 1, SPECK_TOPK_LARGEST_ABS = 2 };
+#define SPECK_TOPK_GROUP_MAX 256    /* rows up to this many entries are ranked by a group of lanes */
+#define SPECK_TOPK_LDS_MAX 4096     /* rows up to this many entries are selected with their keys in LDS */
+typedef struct speck_topk_params {
+    uint64_t k;                  /* entries a row keeps at most */
+    uint32_t mode;               /* SPECK_TOPK_* */
+    uint32_t reserved;           /* must be 0 */
+} speck_topk_params;
+typedef struct speck_topk_info {
+    uint64_t rows;               /* rows of C = A->rows */
+    uint64_t rows_cut;           /* rows of A longer than k */
+    uint64_t entries_in;         /* entries of A */
+    uint64_t nnz_out;            /* entries of C */
+    uint64_t dropped;            /* entries_in - nnz_out */
+    uint64_t max_row_entries;    /* the longest row of C */
+    uint64_t ties_cut;           /* rows in which a dropped entry has the key of a kept one */
+    uint64_t nan_kept;           /* NaN entries of C */
+} speck_topk_info;
+int speck_topk_f64(speck_config *cfg, const speck_dcsr *A, const speck_topk_params *p, speck_dcsr *C,
+                   speck_topk_info *info /* may be NULL */);
+int speck_topk_f32(speck_config *cfg, const speck_dcsr *A, const speck_topk_params *p, speck_dcsr *C,
+                   speck_topk_info *info);
+
 /* ---- row-sharded multi-GPU (new: the reference is single-GPU, source/Executor.cpp:25).  One process per GPU;
  *      rank p multiplies the row range [b_p, b_{p+1}) of A (a view with absolute offsets, boundaries from
  *      speck_partition_rows) with a replicated B, then ONE exchange concatenates the shards on a root rank:

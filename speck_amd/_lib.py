@@ -157,6 +157,17 @@ class CExtractInfo(C.Structure):
                 ("dropped", C.c_uint64), ("cols_kept", C.c_uint64), ("max_row_entries", C.c_uint64)]
 
 
+class CTopKParams(C.Structure):
+    # include/speck_c_api.h: speck_topk_params
+    _fields_ = [("k", C.c_uint64), ("mode", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class CTopKInfo(C.Structure):
+    # include/speck_c_api.h: speck_topk_info
+    _fields_ = [("rows", C.c_uint64), ("rows_cut", C.c_uint64), ("entries_in", C.c_uint64), ("nnz_out", C.c_uint64),
+                ("dropped", C.c_uint64), ("max_row_entries", C.c_uint64), ("ties_cut", C.c_uint64), ("nan_kept", C.c_uint64)]
+
+
 # every symbol include/speck_c_api.h declares, with its ctypes signature
 _P = C.POINTER
 _SIGS = {
@@ -219,6 +230,8 @@ _SIGS = {
     "speck_to_coo": (C.c_int, [C.c_void_p, _P(DCsr), C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]),
     "speck_extract_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(CExtractParams), _P(DCsr), _P(CExtractInfo)]),
     "speck_extract_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(CExtractParams), _P(DCsr), _P(CExtractInfo)]),
+    "speck_topk_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(CTopKParams), _P(DCsr), _P(CTopKInfo)]),
+    "speck_topk_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(CTopKParams), _P(DCsr), _P(CTopKInfo)]),
     "speck_compare_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), C.c_int, C.c_double, _P(C.c_uint64)]),
     "speck_compare_bounded_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), _P(DCsr), C.c_double, _P(C.c_uint64),
                                             _P(C.c_uint64)]),

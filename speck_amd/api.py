@@ -1228,6 +1228,46 @@ def permute(A, row_perm=None, col_perm=None, config=None, matOut=None, canonical
     return extract(A, rows=row_perm, col_map=cmap, out_cols=A.cols, config=config, matOut=matOut, canonical=canonical, who="permute")
 
 
+# include/speck_c_api.h: SPECK_TOPK_*; SPECK_TOPK_GROUP_MAX / SPECK_TOPK_LDS_MAX (rows of more than k entries up to this many:
+# ranked by a group of 8 / 16 / 32 / 64 lanes -- up to GROUP_MAX / 8, / 4, / 2, GROUP_MAX entries -- / selected by one
+# workgroup with the row's keys in LDS; longer ones are selected from global memory)
+TOPK_LARGEST, TOPK_SMALLEST, TOPK_LARGEST_ABS = range(3)
+TOPK_MODES = {"largest": TOPK_LARGEST, "smallest": TOPK_SMALLEST, "abs": TOPK_LARGEST_ABS}
+TOPK_GROUP_MAX = 256
+TOPK_LDS_MAX = 4096
+
+
+class TopKInfo(_Info):
+    """speck_topk_info: the rows, those longer than k, the entries that went in, came out and were dropped, the longest row
+    of the result, the rows in which the tie rule decided and the NaN entries of the result."""
+    _fields = ("rows", "rows_cut", "entries_in", "nnz_out", "dropped", "max_row_entries", "ties_cut", "nan_kept")
+
+
+def topk(A, k, by="largest", cfg=None, out=None, return_info=False):
+    """C = the k best entries of every row of the device matrix A (speck_topk_f64 / _f32), in input order, ids and values
+    bit for bit.  by: "largest" (the key of a value v is v), "smallest" (-v) or "abs" (|v|).  A NaN ranks above every
+    number, -0.0 equals +0.0; of equal keys the entry that comes first in the row wins.  A row of at most k entries is kept
+    whole, k == 0 gives empty rows, a k of 2^32 or more keeps everything.  cfg may be None; out is the dCSR that takes the
+    result (its buffers are reused where their size stays).  Returns out, or (out, TopKInfo) with return_info."""
+    if by not in TOPK_MODES:
+        raise ValueError(f"topk: by must be one of {sorted(TOPK_MODES)}, not {by!r}")
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= int(k) < (1 << 64):
+        raise ValueError(f"topk: k must be an integer in [0, 2^64), not {k!r}")
+    L = _lib.load()
+    p = _lib.CTopKParams()
+    p.k, p.mode, p.reserved = int(k), TOPK_MODES[by], 0
+    fn = L.speck_topk_f32 if A.dtype == np.float32 else L.speck_topk_f64
+    if out is None:
+        out = dCSR(A.dtype)
+    if out.dtype != A.dtype:
+        out.reset()
+        out.dtype = A.dtype
+    info = _lib.CTopKInfo()
+    _check(fn(cfg._h if cfg is not None else None, C.byref(A._c), C.byref(p), C.byref(out._c), C.byref(info)), "topk")
+    out._host_row_offsets = None  # (row_offsets were rewritten on the device)
+    return (out, TopKInfo(info)) if return_info else out
+
+
 # include/speck_c_api.h: SPECK_SDDMM_*; the most columns U and V may have, and the entries of a tile of the pass
 SDDMM_AXPBY, SDDMM_HADAMARD = range(2)
 SDDMM_MODES = {"axpby": SDDMM_AXPBY, "hadamard": SDDMM_HADAMARD}

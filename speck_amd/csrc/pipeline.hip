@@ -36,6 +36,7 @@
 #include "tile_scratch.hpp"
 #include "coo.hpp"
 #include "extract.hpp"
+#include "topk.hpp"
 
 using namespace speck;
 
@@ -244,6 +245,7 @@ struct speck_config {
     TileScratch spmm_t;  // ... and of speck_spmm_t_* (spmm_t.hip): the records of the plan's tiles, the column sums
     CooScratch coo;  // ... and of speck_from_coo_* / speck_to_coo (coo.hip): the status block, the keys and buffers of the sort
     ExtractScratch extract;  // ... and of speck_extract_* (extract.hip): the rows' lengths and offsets, the keep bytes
+    TopKScratch topk;  // ... and of speck_topk_* (topk.hip): the row lists, the kept entries per row, the new row offsets
     const void* zones_arena = nullptr;
     u64 zones_m = 0, zones_nnz = 0, zones_gap = 0;
     bool gpool_zones_filled = false;
@@ -2013,6 +2015,7 @@ TileScratch* softmax_scratch(speck_config* c) { return &c->softmax; }
 TileScratch* spmm_t_scratch(speck_config* c) { return &c->spmm_t; }
 CooScratch* coo_scratch(speck_config* c) { return &c->coo; }
 ExtractScratch* extract_scratch(speck_config* c) { return &c->extract; }
+TopKScratch* topk_scratch(speck_config* c) { return &c->topk; }
 }  // namespace speck
 
 extern "C" {
@@ -2138,6 +2141,7 @@ int speck_config_destroy(speck_config* c)
     c->spmm_t.release();
     c->coo.release();
     c->extract.release();
+    c->topk.release();
     if (c->pred.off) (void)guarded_free(c->pred.off);
     if (c->gpred.off) (void)guarded_free(c->gpred.off);
     if (c->d_stats) (void)hipFree(c->d_stats);
@@ -2231,9 +2235,12 @@ int speck_config_set_option(speck_config* c, const char* name, int64_t value)
         c->spmm_t.release();
         c->coo.release();
         c->extract.release();
+        c->topk.release();
     }
     else if (n == "sort_reg_max") c->sort.reg_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_REG_MAX);
     else if (n == "sort_lds_max") c->sort.lds_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_LDS_MAX);
+    else if (n == "topk_group_max") c->topk.group_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_TOPK_GROUP_MAX);
+    else if (n == "topk_lds_max") c->topk.lds_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_TOPK_LDS_MAX);
     else if (n == "mask_group_max") c->masked.group_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_MASK_GROUP_MAX);
     else if (n == "mask_lds_max") c->masked.lds_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_MASK_LDS_MAX);
     else if (n == "walk_debug") set_walk_debug((u32)value & 0xFFFFu, (u32)(value >> 16));  // (tile rows | flags << 16)
