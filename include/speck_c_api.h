@@ -1078,6 +1078,93 @@ int speck_topk_f64(speck_config *cfg, const speck_dcsr *A, const speck_topk_para
 int speck_topk_f32(speck_config *cfg, const speck_dcsr *A, const speck_topk_params *p, speck_dcsr *C,
                    speck_topk_info *info);
 
+/* ---- fan-out neighbour sampling (new: the reference has no counterpart): row i of C = at most k entries of row p[i] of A,
+ *      chosen uniformly at random -- the step in front of a sampled mini-batch (DGL's sample_neighbors, PyG's NeighborLoader):
+ *      sample_neighbors -> induced_subgraph -> sddmm -> softmax -> spmm.  speck_topk_* keeps the k LARGEST and takes no row
+ *      list; speck_extract_* gathers the rows and keeps every entry of a hub.  This call does both in one, and the random key
+ *      of an entry is a PURE FUNCTION of (seed, global row, place in the row): the sample is reproducible bit for bit in
+ *      numpy, the same from run to run, and needs no random-number state and no floating point.
+ *  d_row_index / n_rows / index_bytes as for speck_extract_*: n_rows indices into the rows INSIDE A, any order, REPEATS
+ *      ALLOWED; NULL: the rows 0 .. A->rows - 1, then n_rows must be A->rows.  row_base: the global index of A's first row
+ *      where A is a row-range view, else 0.  C has n_rows rows and A->cols columns; its offsets start at 0.
+ *  KEYS.  All arithmetic modulo 2^64, GOLDEN = 0x9E3779B97F4A7C15:
+ *          mix(z):  z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31
+ *          row_key(seed, g) = mix(seed + GOLDEN * (g + 1))       g = row_base + p[i], the GLOBAL index of the source row
+ *          key(seed, g, t)  = mix(row_key(seed, g) + GOLDEN * (t + 1))        t = 0, 1, 2, ...
+ *      key(., ., t) is output number t of the SplitMix64 generator started at row_key.
+ *  SPECK_SAMPLE_WITHOUT_REPLACEMENT: the entry at place t of its row (0-based, in input order) carries key(seed, g, t); it is
+ *      KEPT iff fewer than k entries of the row have a lexicographically smaller (key, t).  A row of at most k entries is
+ *      kept whole, a longer one keeps exactly k; k == 0 gives empty rows, a k of 2^32 or more keeps everything.  Kept entries
+ *      stay IN INPUT ORDER, ids and values bit for bit (NaN payloads, -0.0 and subnormals survive): a canonical A gives a C
+ *      that speck_multiply_* accepts.  As numpy, per row:  kept = np.sort(np.lexsort((t, key))[:k]).
+ *  SPECK_SAMPLE_WITH_REPLACEMENT: a source row of len >= 1 entries gives exactly k entries, an empty one gives none.  Entry u
+ *      of the output row, in draw order u = 0 .. k - 1, is the source entry at place (key(seed, g, u) * len) >> 64 (the high
+ *      word of the 128-bit product).  The bias of that map is below len / 2^64.  Repeats stay and nothing is sorted:
+ *      speck_sort_rows_* is one call away.
+ *  (tests/test_sample_host.py states both as numpy_sample, compares it with a count of smaller (key, t) and tests the
+ *      uniformity of the places it takes.)
+ *  So the sample does not depend on values, column ids, the value type, the absolute offsets of a view or the class a row
+ *      falls in: _f32 and _f64 give the same structure; a view with the right row_base gives the rows of the whole matrix's
+ *      sample; the same row named twice gives the same sample twice -- the caller varies seed per hop or epoch.  Integer
+ *      arithmetic and integer atomics only: the same bytes from run to run.
+ *  *info: rows_out = n_rows; rows_empty = rows of C without an entry; rows_cut = gathered rows longer than k; gross = the
+ *      entries of the gathered rows; max_row_entries = the longest row of C.  *info is zero once the arguments have passed,
+ *      and again on an error.
+ *  SPECK_ERR_INVALID with NOTHING written -- not C's struct, not its allocations, not the contents of buffers it would reuse:
+ *      offsets of A that descend, leave [row_offsets[0], row_offsets[0] + nnz] or whose last one does not span nnz (all rows
+ *      are checked); a row index >= A->rows (8 bytes wide: compared unsigned, so -1 and 2^32 + 3 are refused); a column id >=
+ *      A->cols anywhere in a GATHERED row, whichever entries the sample would have taken -- the verdict does not depend on the
+ *      seed; the ids of rows nobody gathers are NEVER READ, so a matrix with a bad id in a row nobody asks for is served; an
+ *      unknown mode; index_bytes not 4 or 8; a NULL index with n_rows != A->rows; row_base > 2^62; the index overlapping a
+ *      buffer of A or C; C sharing a buffer with A; NULL A, p or C; NULL buffers with a count > 0.  A->rows, A->cols or
+ *      n_rows > 2^27: SPECK_ERR_DIM_LIMIT.  A->nnz >= 2^32, an output of 2^32 entries or more (mode 1 reaches that easily:
+ *      k times the non-empty gathered rows) or gathered rows of 2^32 entries or more (as speck_extract_*):
+ *      SPECK_ERR_NNZ_OVERFLOW, decided from 64-bit sums in the first pass before any 32-bit offset exists.
+ *  CHECK: a thread per row of A and per index -- the offsets, the indices, the gathered length (0 where unsound: clamped,
+ *      never followed), the output length min(len, k) or (len ? k : 0), the 64-bit sums of both and, for mode 0, the rows
+ *      longer than k sent to lists by length.  The shared scan gives C's offsets -- they depend on the lengths alone: no
+ *      marking pass, no keep byte -- and the gross offsets.  ID CHECK: tiles of SPECK_SAMPLE_TILE_ENTRIES gross entries over
+ *      the gathered rows, every id compared with A->cols.  ONE read-back (the verdict, nnz(C), the lists) before C is
+ *      allocated; every kernel that writes C starts after it.  Mode 0: rows of at most k entries are a streaming copy; rows
+ *      of up to SPECK_SAMPLE_GROUP_MAX entries: a group of 8 / 16 / 32 / 64 lanes counts, per entry, the entries with a smaller
+ *      (key, t); rows of up to SPECK_SAMPLE_LDS_MAX: one workgroup, the keys computed once into LDS, a radix select from the
+ *      most significant byte for the threshold key and the number of its equals to keep, then one ordered walk; longer rows:
+ *      the same select with the keys RECOMPUTED in every pass -- no global read before the walk.  Mode 1: one stream over the
+ *      output entries, the row by a search in C's offsets per tile; every entry is independent.  A key costs two 64-bit
+ *      multiplies; the work on a cut row is O(len), not O(k).
+ *  Ownership of C, the stream, cfg == NULL, guard_bytes and the grow-only scratch of the config's own (32 bytes per output
+ *      row) as speck_select_* / speck_extract_* document them.  The debug options sample_group_max and sample_lds_max
+ *      (clamped to the two defines) lower the class limits: every class gives the same bytes.
+ *  Not built: weighted sampling (needs log / pow: not bit-reproducible); a per-row k; several hops in one call; sampling
+ *      by column (speck_transpose_* first); an O(k) draw for hub rows (Floyd's algorithm: the work here is O(len) per cut
+ *      row); the positions of the kept entries returned by the C call (the Python wrapper gets them from a second call on
+ *      values that are positions). ---- */
+enum { SPECK_SAMPLE_WITHOUT_REPLACEMENT = 0, SPECK_SAMPLE_WITH_REPLACEMENT = 1 };
+#define SPECK_SAMPLE_GROUP_MAX 256    /* cut rows up to this many entries are ranked by a group of lanes */
+#define SPECK_SAMPLE_LDS_MAX 4096     /* cut rows up to this many entries are selected with their keys in LDS */
+#define SPECK_SAMPLE_TILE_ENTRIES 4096
+typedef struct speck_sample_params {
+    uint64_t k;                  /* fan-out: entries a row of C holds at most (mode 0) / exactly, if its source row is not empty (mode 1) */
+    uint64_t seed;
+    uint64_t row_base;           /* global index of A's first row (A a row-range view), else 0; > 2^62: INVALID */
+    uint64_t n_rows;             /* rows of C */
+    const void *d_row_index;     /* DEVICE, n_rows indices into the rows INSIDE A, any order, repeats allowed; NULL: rows 0..A->rows-1, n_rows == A->rows */
+    uint32_t index_bytes;        /* 4: uint32_t, 8: int64_t -- as speck_extract_* */
+    uint32_t mode;               /* SPECK_SAMPLE_* */
+} speck_sample_params;
+typedef struct speck_sample_info {
+    uint64_t rows_out;           /* rows of C = n_rows */
+    uint64_t rows_empty;         /* rows of C without an entry */
+    uint64_t rows_cut;           /* gathered rows longer than k */
+    uint64_t gross;              /* entries of the gathered rows */
+    uint64_t nnz_out;            /* entries of C */
+    uint64_t max_row_entries;    /* the longest row of C */
+} speck_sample_info;
+int speck_sample_f64(speck_config *cfg, const speck_dcsr *A, const speck_sample_params *p, speck_dcsr *C,
+                     speck_sample_info *info /* may be NULL */);
+int speck_sample_f32(speck_config *cfg, const speck_dcsr *A, const speck_sample_params *p, speck_dcsr *C,
+                     speck_sample_info *info);
+
 /* ---- row-sharded multi-GPU (new: the reference is single-GPU, source/Executor.cpp:25).  One process per GPU;
  *      rank p multiplies the row range [b_p, b_{p+1}) of A (a view with absolute offsets, boundaries from
  *      speck_partition_rows) with a replicated B, then ONE exchange concatenates the shards on a root rank:

@@ -168,6 +168,18 @@ class CTopKInfo(C.Structure):
                 ("dropped", C.c_uint64), ("max_row_entries", C.c_uint64), ("ties_cut", C.c_uint64), ("nan_kept", C.c_uint64)]
 
 
+class CSampleParams(C.Structure):
+    # include/speck_c_api.h: speck_sample_params
+    _fields_ = [("k", C.c_uint64), ("seed", C.c_uint64), ("row_base", C.c_uint64), ("n_rows", C.c_uint64),
+                ("d_row_index", C.c_void_p), ("index_bytes", C.c_uint32), ("mode", C.c_uint32)]
+
+
+class CSampleInfo(C.Structure):
+    # include/speck_c_api.h: speck_sample_info
+    _fields_ = [("rows_out", C.c_uint64), ("rows_empty", C.c_uint64), ("rows_cut", C.c_uint64), ("gross", C.c_uint64),
+                ("nnz_out", C.c_uint64), ("max_row_entries", C.c_uint64)]
+
+
 # every symbol include/speck_c_api.h declares, with its ctypes signature
 _P = C.POINTER
 _SIGS = {
@@ -232,6 +244,8 @@ _SIGS = {
     "speck_extract_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(CExtractParams), _P(DCsr), _P(CExtractInfo)]),
     "speck_topk_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(CTopKParams), _P(DCsr), _P(CTopKInfo)]),
     "speck_topk_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(CTopKParams), _P(DCsr), _P(CTopKInfo)]),
+    "speck_sample_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(CSampleParams), _P(DCsr), _P(CSampleInfo)]),
+    "speck_sample_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(CSampleParams), _P(DCsr), _P(CSampleInfo)]),
     "speck_compare_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), C.c_int, C.c_double, _P(C.c_uint64)]),
     "speck_compare_bounded_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), _P(DCsr), C.c_double, _P(C.c_uint64),
                                             _P(C.c_uint64)]),

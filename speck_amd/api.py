@@ -1268,6 +1268,102 @@ def topk(A, k, by="largest", cfg=None, out=None, return_info=False):
     return (out, TopKInfo(info)) if return_info else out
 
 
+# include/speck_c_api.h: SPECK_SAMPLE_*; SPECK_SAMPLE_GROUP_MAX / SPECK_SAMPLE_LDS_MAX (cut rows up to this many entries: ranked
+# by a group of 8 / 16 / 32 / 64 lanes / selected by one workgroup with the row's keys in LDS; longer ones are selected
+# with their keys recomputed in every pass); the gross entries of a tile of the id check and the draws of a tile of mode 1
+SAMPLE_WITHOUT_REPLACEMENT, SAMPLE_WITH_REPLACEMENT = range(2)
+SAMPLE_GROUP_MAX = 256
+SAMPLE_LDS_MAX = 4096
+SAMPLE_TILE_ENTRIES = 4096
+
+
+class SampleInfo(_Info):
+    """speck_sample_info: the rows of the result and the empty ones among them, the gathered rows longer than k, the
+    entries of the gathered rows, the entries of the result and its longest row."""
+    _fields = ("rows_out", "rows_empty", "rows_cut", "gross", "nnz_out", "max_row_entries")
+
+
+def _sample_call(A, p, cfg):
+    """one speck_sample_* call into a new matrix: (dCSR, SampleInfo)"""
+    L = _lib.load()
+    fn = L.speck_sample_f32 if A.dtype == np.float32 else L.speck_sample_f64
+    out = dCSR(A.dtype)
+    info = _lib.CSampleInfo()
+    _check(fn(cfg._h if cfg is not None else None, C.byref(A._c), C.byref(p), C.byref(out._c), C.byref(info)), "sample_neighbors")
+    out._host_row_offsets = None  # (row_offsets were written on the device)
+    return out, SampleInfo(info)
+
+
+def sample_neighbors(A, k, seed, rows=None, replace=False, row_base=0, return_pos=False, cfg=None):
+    """Fan-out neighbour sampling (speck_sample_f64 / _f32): row i of the result holds at most k entries of row rows[i] of the
+    device matrix A, chosen uniformly at random -- rows is a 1-D int64 or int32 tensor, any order, repeats allowed; None:
+    every row in order.  The random key of an entry is a pure function of (seed, row_base + rows[i], place in the row), so
+    the sample is the same from run to run, does not depend on values, ids or the value type, and is restated in numpy by
+    tests/test_sample_host.py; vary seed per hop or epoch.  replace=False: a row of at most k entries is kept whole, a
+    longer one keeps exactly k, in input order (k == 0: empty rows; k >= 2^32: everything).  replace=True: a non-empty
+    row gives exactly k entries in draw order, repeats stay.  Ids and values are copied bit for bit.  row_base is the
+    global index of A's first row where A is a row_view: the view's sample is then the rows of the whole matrix's sample.
+    return_pos=True also returns, per entry of the result, its position in A's data / col_ids (the edge id) as an int64
+    tensor: a second call on a matrix that shares A's offsets and ids and whose values are the positions as doubles (exact:
+    nnz < 2^32).  An index >= A.rows or an id >= A.cols in a gathered row raise SpeckError (SPECK_ERR_INVALID).  cfg may be
+    None.  Returns (C, SampleInfo), or (C, SampleInfo, pos) with return_pos."""
+    who = "sample_neighbors"
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 0 <= int(k) < (1 << 64):
+        raise ValueError(f"{who}: k must be an integer in [0, 2^64), not {k!r}")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < (1 << 64):
+        raise ValueError(f"{who}: seed must be an integer in [0, 2^64), not {seed!r}")
+    if isinstance(row_base, bool) or not isinstance(row_base, (int, np.integer)) or not 0 <= int(row_base) <= (1 << 62):
+        raise ValueError(f"{who}: row_base must be an integer in [0, 2^62], not {row_base!r}")
+    if not isinstance(replace, (bool, np.bool_)):
+        raise ValueError(f"{who}: replace must be True or False, not {replace!r}")
+    r, n, width = None, A.rows, 8
+    if rows is not None:
+        r, n, width = _index_array(rows, "rows", who, None, None)
+    if not 0 <= n <= _DIM_MAX:
+        raise ValueError(f"{who}: {n} rows are beyond the limit of {_DIM_MAX}")
+    # ---- everything was checked: the addresses
+    p = _lib.CSampleParams()
+    p.k, p.seed, p.row_base, p.n_rows, p.index_bytes = int(k), int(seed), int(row_base), n, width
+    p.mode = SAMPLE_WITH_REPLACEMENT if replace else SAMPLE_WITHOUT_REPLACEMENT
+    p.d_row_index = _address(r) if r is not None else None
+    if r is not None and n == 0 and hasattr(r, "data_ptr"):
+        import torch                     # (a tensor without elements has no address, and a NULL index names every row)
+        none = torch.zeros(1, dtype=torch.int64, device=torch.device("cuda", cfg.device) if cfg is not None else torch.device("cuda"))
+        p.d_row_index = none.data_ptr()
+    out, info = _sample_call(A, p, cfg)
+    if not return_pos:
+        return out, info
+    import torch
+    device = torch.device("cuda", cfg.device) if cfg is not None else torch.device("cuda")
+    # The positions count from the start of A's buffers, as the offsets of a row_view do: its entries start at its first offset.
+    if A._host_row_offsets is not None and len(A._host_row_offsets):
+        base = int(A._host_row_offsets[0])
+    elif A.rows and A._c.row_offsets:
+        first = np.zeros(1, dtype=np.uint32)
+        probe = _lib.DCsr()                  # (no row and one entry: not a view to the download, which then rebases nothing)
+        probe.nnz, probe.row_offsets = 1, A._c.row_offsets
+        _check(_lib.load().speck_dcsr_download(C.byref(probe), first.ctypes.data, None, None, 8), f"{who}: download")
+        base = int(first[0])
+    else:
+        base = 0
+    # (one element at least each: a tensor without elements has no address)
+    at = torch.arange(max(base + A.nnz, 1), dtype=torch.float64, device=device)
+    torch.cuda.current_stream(device).synchronize()   # (the call reads them on the config's stream)
+    twin = dCSR.from_device(A.rows, A.cols, A.nnz, A._c.row_offsets, A._c.col_ids, at.data_ptr(), dtype=np.float64, keep=(A, at))
+    # the second result goes into torch tensors: a C of the first result's rows and entries is reused, not re-allocated
+    pos = torch.empty(max(out.nnz, 1), dtype=torch.float64, device=device)
+    ids = torch.empty(max(out.nnz, 1), dtype=torch.int32, device=device)
+    offs = torch.empty(out.rows + 1, dtype=torch.int32, device=device)
+    where = dCSR.from_device(out.rows, A.cols, out.nnz, offs.data_ptr(), ids.data_ptr(), pos.data_ptr(), dtype=np.float64,
+                             keep=(pos, ids, offs))
+    before = (where._c.data, where._c.col_ids, where._c.row_offsets)
+    L = _lib.load()
+    _check(L.speck_sample_f64(cfg._h if cfg is not None else None, C.byref(twin._c), C.byref(p), C.byref(where._c), None), who)
+    if (where._c.data, where._c.col_ids, where._c.row_offsets) != before or where.nnz != out.nnz:
+        raise RuntimeError(f"{who}: the call on the positions gave another structure ({where.nnz} entries, not {out.nnz})")
+    return out, info, pos[:out.nnz].long()
+
+
 # include/speck_c_api.h: SPECK_SDDMM_*; the most columns U and V may have, and the entries of a tile of the pass
 SDDMM_AXPBY, SDDMM_HADAMARD = range(2)
 SDDMM_MODES = {"axpby": SDDMM_AXPBY, "hadamard": SDDMM_HADAMARD}

@@ -37,6 +37,7 @@
 #include "coo.hpp"
 #include "extract.hpp"
 #include "topk.hpp"
+#include "sample.hpp"
 
 using namespace speck;
 
@@ -246,6 +247,7 @@ struct speck_config {
     CooScratch coo;  // ... and of speck_from_coo_* / speck_to_coo (coo.hip): the status block, the keys and buffers of the sort
     ExtractScratch extract;  // ... and of speck_extract_* (extract.hip): the rows' lengths and offsets, the keep bytes
     TopKScratch topk;  // ... and of speck_topk_* (topk.hip): the row lists, the kept entries per row, the new row offsets
+    SampleScratch sample;  // ... and of speck_sample_* (sample.hip): the row lists, the rows' sources, lengths and offsets
     const void* zones_arena = nullptr;
     u64 zones_m = 0, zones_nnz = 0, zones_gap = 0;
     bool gpool_zones_filled = false;
@@ -2016,6 +2018,7 @@ TileScratch* spmm_t_scratch(speck_config* c) { return &c->spmm_t; }
 CooScratch* coo_scratch(speck_config* c) { return &c->coo; }
 ExtractScratch* extract_scratch(speck_config* c) { return &c->extract; }
 TopKScratch* topk_scratch(speck_config* c) { return &c->topk; }
+SampleScratch* sample_scratch(speck_config* c) { return &c->sample; }
 }  // namespace speck
 
 extern "C" {
@@ -2142,6 +2145,7 @@ int speck_config_destroy(speck_config* c)
     c->coo.release();
     c->extract.release();
     c->topk.release();
+    c->sample.release();
     if (c->pred.off) (void)guarded_free(c->pred.off);
     if (c->gpred.off) (void)guarded_free(c->gpred.off);
     if (c->d_stats) (void)hipFree(c->d_stats);
@@ -2236,11 +2240,14 @@ int speck_config_set_option(speck_config* c, const char* name, int64_t value)
         c->coo.release();
         c->extract.release();
         c->topk.release();
+        c->sample.release();
     }
     else if (n == "sort_reg_max") c->sort.reg_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_REG_MAX);
     else if (n == "sort_lds_max") c->sort.lds_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_LDS_MAX);
     else if (n == "topk_group_max") c->topk.group_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_TOPK_GROUP_MAX);
     else if (n == "topk_lds_max") c->topk.lds_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_TOPK_LDS_MAX);
+    else if (n == "sample_group_max") c->sample.group_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SAMPLE_GROUP_MAX);
+    else if (n == "sample_lds_max") c->sample.lds_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SAMPLE_LDS_MAX);
     else if (n == "mask_group_max") c->masked.group_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_MASK_GROUP_MAX);
     else if (n == "mask_lds_max") c->masked.lds_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_MASK_LDS_MAX);
     else if (n == "walk_debug") set_walk_debug((u32)value & 0xFFFFu, (u32)(value >> 16));  // (tile rows | flags << 16)
