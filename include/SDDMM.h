@@ -30,4 +30,23 @@ void SDDMM(const dCSR<DataType>& A, const double* d_U, uint64_t ldu, const doubl
     if (C) C->adopt(c);
     if (rc != SPECK_OK) throw std::runtime_error(std::string("spECK::SDDMM: ") + speck_status_string(rc));
 }
+
+// float blocks (speck_sddmm_f64_b32 / _f32_b32): ldu and ldv count floats; C is bit for bit the result above on the widened
+// blocks
+template <typename DataType>
+void SDDMM(const dCSR<DataType>& A, const float* d_U, uint64_t ldu, const float* d_V, uint64_t ldv, uint32_t k, spECKConfig& config,
+           double alpha = 1.0, double beta = 0.0, dCSR<DataType>* C = nullptr, int mode = SPECK_SDDMM_AXPBY,
+           speck_sddmm_info* info = nullptr)
+{
+    speck_dcsr a = A.raw();
+    speck_sddmm_params_b32 p{};
+    p.mode = (uint32_t)mode, p.k = k, p.alpha = alpha, p.beta = beta;
+    p.d_U = d_U, p.ldu = ldu, p.d_V = d_V, p.ldv = ldv;
+    speck_dcsr c{};
+    if (C) c = C->raw();
+    const int rc = sizeof(DataType) == 8 ? speck_sddmm_f64_b32(config.handle, &a, &p, C ? &c : nullptr, info)
+                                         : speck_sddmm_f32_b32(config.handle, &a, &p, C ? &c : nullptr, info);
+    if (C) C->adopt(c);
+    if (rc != SPECK_OK) throw std::runtime_error(std::string("spECK::SDDMM: ") + speck_status_string(rc));
+}
 }  // namespace spECK

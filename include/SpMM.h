@@ -23,4 +23,16 @@ void SpMM(const dCSR<DataType>& A, const double* d_X, uint64_t ldx, uint32_t k, 
                                          : speck_spmm_f32(config.handle, alpha, &a, d_X, ldx, k, beta, d_Y, ldy, info);
     if (rc != SPECK_OK) throw std::runtime_error(std::string("spECK::SpMM: ") + speck_status_string(rc));
 }
+
+// float blocks (speck_spmm_f64_b32 / _f32_b32): ldx and ldy count floats; Y is bit for bit the result above on the widened
+// blocks, rounded to float once
+template <typename DataType>
+void SpMM(const dCSR<DataType>& A, const float* d_X, uint64_t ldx, uint32_t k, float* d_Y, uint64_t ldy, spECKConfig& config,
+          double alpha = 1.0, double beta = 0.0, speck_spmm_info* info = nullptr)
+{
+    speck_dcsr a = A.raw();
+    const int rc = sizeof(DataType) == 8 ? speck_spmm_f64_b32(config.handle, alpha, &a, d_X, ldx, k, beta, d_Y, ldy, info)
+                                         : speck_spmm_f32_b32(config.handle, alpha, &a, d_X, ldx, k, beta, d_Y, ldy, info);
+    if (rc != SPECK_OK) throw std::runtime_error(std::string("spECK::SpMM: ") + speck_status_string(rc));
+}
 }  // namespace spECK

@@ -60,4 +60,16 @@ void SpMMT(const TransposePlan& plan, const dCSR<DataType>& A, const double* d_X
                                          : speck_spmm_t_f32(config.handle, plan.get(), alpha, &a, d_X, ldx, k, beta, d_Y, ldy, info);
     if (rc != SPECK_OK) throw std::runtime_error(std::string("spECK::SpMMT: ") + speck_status_string(rc));
 }
+
+// float blocks (speck_spmm_t_f64_b32 / _f32_b32): ldx and ldy count floats; Y is bit for bit the result above on the
+// widened blocks with the same plan, rounded to float once
+template <typename DataType>
+void SpMMT(const TransposePlan& plan, const dCSR<DataType>& A, const float* d_X, uint64_t ldx, uint32_t k, float* d_Y, uint64_t ldy,
+           spECKConfig& config, double alpha = 1.0, double beta = 0.0, speck_spmm_t_info* info = nullptr)
+{
+    speck_dcsr a = A.raw();
+    const int rc = sizeof(DataType) == 8 ? speck_spmm_t_f64_b32(config.handle, plan.get(), alpha, &a, d_X, ldx, k, beta, d_Y, ldy, info)
+                                         : speck_spmm_t_f32_b32(config.handle, plan.get(), alpha, &a, d_X, ldx, k, beta, d_Y, ldy, info);
+    if (rc != SPECK_OK) throw std::runtime_error(std::string("spECK::SpMMT: ") + speck_status_string(rc));
+}
 }  // namespace spECK

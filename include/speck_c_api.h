@@ -624,7 +624,8 @@ int speck_spmv_f32(speck_config *cfg, double alpha, const speck_dcsr *A, const d
  *      blocks of SPECK_SPMM_COLUMN_BLOCK whose gathers are in flight together -- one 16-byte load per entry and pair of
  *      columns where d_X lies on a 16-byte boundary and ldx is even, 8-byte loads elsewhere, with the same results.
  *  info: rows_empty, rows_split, tiles and entries as speck_spmv_info -- they describe A, not k.
- *  Not built (A^T X: speck_spmm_t_* below): column-major or float vectors; a semiring other than (+, x). ---- */
+ *  Not built (A^T X: speck_spmm_t_* below; float blocks: speck_spmm_*_b32 below): column-major vectors; a semiring other
+ *      than (+, x). ---- */
 #define SPECK_SPMM_MAX_RHS 1024
 #define SPECK_SPMM_COLUMN_BLOCK 4
 typedef struct speck_spmm_info {
@@ -696,8 +697,9 @@ int speck_spmm_f32(speck_config *cfg, double alpha, const speck_dcsr *A, const d
  *  The entries are walked in tiles of SPECK_SDDMM_TILE_ENTRIES, aligned to absolute positions as the reduction's; one path
  *      for every row length.  The ids are loaded 16 bytes at a time where col_ids (and C's) lie on 16-byte boundaries,
  *      one by one elsewhere, with the same results.
- *  Not built: U^T / column-major or float blocks; a map fused behind the dot (the row softmax of the scores is the next
- *      call, speck_softmax_*, in place on the same matrix); the product fused into speck_multiply_masked_*. ---- */
+ *  Not built (float blocks: speck_sddmm_*_b32 below): U^T / column-major blocks; a map fused behind the dot (the row
+ *      softmax of the scores is the next call, speck_softmax_*, in place on the same matrix); the product fused into
+ *      speck_multiply_masked_*. ---- */
 #define SPECK_SDDMM_MAX_K 1024            /* = SPECK_SPMM_MAX_RHS */
 #define SPECK_SDDMM_TILE_ENTRIES 4096
 enum { SPECK_SDDMM_AXPBY = 0, SPECK_SDDMM_HADAMARD = 1 };
@@ -851,7 +853,7 @@ int speck_softmax_f32(speck_config *cfg, const speck_dcsr *A, const speck_softma
  *      16-byte loads, gathers its 16 values and ids through t_pos and takes the k columns in speck_spmm_*'s blocks.
  *  info: cols_empty and cols_split describe A^T as rows_empty and rows_split of speck_spmm_info describe A.
  *  Not built: a switch that trusts the plan and skips the verification; a transpose that only gathers values through a
- *      plan; a column-side reduce or softmax; float blocks; a torch.autograd.Function; the sharded all-reduce. ---- */
+ *      plan; a column-side reduce or softmax; a torch.autograd.Function; the sharded all-reduce. ---- */
 typedef struct speck_tplan speck_tplan;          /* opaque; owns its device buffers */
 typedef struct speck_tplan_info {
     uint64_t rows, cols, nnz;     /* of the matrix the plan was made from */
@@ -872,6 +874,52 @@ int speck_spmm_t_f64(speck_config *cfg, const speck_tplan *plan, double alpha, c
                      uint64_t ldx, uint32_t k, double beta, double *d_Y, uint64_t ldy, speck_spmm_t_info *info /* may be NULL */);
 int speck_spmm_t_f32(speck_config *cfg, const speck_tplan *plan, double alpha, const speck_dcsr *A, const double *d_X,
                      uint64_t ldx, uint32_t k, double beta, double *d_Y, uint64_t ldy, speck_spmm_t_info *info);
+
+/* ---- float blocks for the three calls that take dense blocks (new: the reference has no counterpart): speck_spmm_*_b32,
+ *      speck_spmm_t_*_b32 and speck_sddmm_*_b32 take X, Y, U and V as ROW-MAJOR DEVICE arrays of FLOATS -- the features and
+ *      activations of a torch model as they are, without a widened copy, two conversion kernels and twice the gathered
+ *      bytes per call.  The first suffix is A's value type, as everywhere; _b32 says the blocks are float.  Everything not
+ *      said here is the double-block call's (speck_spmm_*, speck_spmm_t_*, speck_sddmm_* above): the arguments, alpha and
+ *      beta in double, the info structs, the refusals, the plan, the config, the temporaries (sums stays rows k DOUBLES).
+ *  What differs.  ld* count elements of 4 bytes; the spans are [d_X, d_X + 4 ((n - 1) ld + k)) bytes.  A block element is
+ *      widened to double where it is loaded (exact, subnormals included); from there every step is the double call's:
+ *      the term (double)a * (double)x rounded once, nothing fused, the same tree.
+ *        spmm_b32, spmm_t_b32:  Y(i,c) = (float)(alpha s + beta (double)Y(i,c)) -- ONE rounding to float, at the end;
+ *            beta == 0.0 does not read Y.  The defining property: the result is BIT FOR BIT
+ *            float(speck_spmm_*(alpha, A, double(X), beta, double(Y))) (speck_spmm_t_* with the same plan).  A result
+ *            beyond float's range becomes inf in its element, as a conversion makes it; it is neither refused nor counted.
+ *        sddmm_b32:  C is BIT FOR BIT what speck_sddmm_* writes for double(U), double(V) -- in place and into a new C,
+ *            both modes, info->nonfinite and info->lanes included.  L(k) and the tree are unchanged.
+ *      So what the double calls promise per column or per entry carries over: the same bits from run to run, views, where
+ *      a NaN lands, duplicates, the plan verified in every call, nothing written on any error, one read-back.
+ *  Alignment: the gathers of spmm / spmm_t take SPECK_SPMM_COLUMN_BLOCK_B32 columns per block, one 16-byte load per entry
+ *      and four columns where the block lies on 16 bytes and ld % 4 == 0, 8-byte loads where it lies on 8 and ld is even,
+ *      4-byte loads elsewhere; sddmm loads a lane's pair of columns with 8 bytes where the block lies on 8 and ld is
+ *      even, 4-byte loads elsewhere.  Every form gives the same bits; the padding [k, ld) is never touched.
+ *  Not built: half / bf16 blocks; accumulation in float; X in float with Y in double (or the reverse); float vectors for
+ *      speck_spmv_*, speck_scale_*, speck_reduce_* and speck_softmax_*. ---- */
+#define SPECK_SPMM_COLUMN_BLOCK_B32 4
+typedef struct speck_sddmm_params_b32 {           /* speck_sddmm_params field for field, the blocks in float */
+    uint32_t mode;                /* SPECK_SDDMM_* */
+    uint32_t k;
+    double alpha, beta;
+    const float *d_U;             /* DEVICE, rows x k row-major, indexed by the row INSIDE A */
+    uint64_t ldu;                 /* in floats */
+    const float *d_V;             /* DEVICE, cols x k row-major, indexed by the column id */
+    uint64_t ldv;
+} speck_sddmm_params_b32;
+int speck_spmm_f64_b32(speck_config *cfg, double alpha, const speck_dcsr *A, const float *d_X, uint64_t ldx, uint32_t k,
+                       double beta, float *d_Y, uint64_t ldy, speck_spmm_info *info /* may be NULL */);
+int speck_spmm_f32_b32(speck_config *cfg, double alpha, const speck_dcsr *A, const float *d_X, uint64_t ldx, uint32_t k,
+                       double beta, float *d_Y, uint64_t ldy, speck_spmm_info *info);
+int speck_spmm_t_f64_b32(speck_config *cfg, const speck_tplan *plan, double alpha, const speck_dcsr *A, const float *d_X,
+                         uint64_t ldx, uint32_t k, double beta, float *d_Y, uint64_t ldy, speck_spmm_t_info *info /* may be NULL */);
+int speck_spmm_t_f32_b32(speck_config *cfg, const speck_tplan *plan, double alpha, const speck_dcsr *A, const float *d_X,
+                         uint64_t ldx, uint32_t k, double beta, float *d_Y, uint64_t ldy, speck_spmm_t_info *info);
+int speck_sddmm_f64_b32(speck_config *cfg, const speck_dcsr *A, const speck_sddmm_params_b32 *p, speck_dcsr *C /* NULL: in place */,
+                        speck_sddmm_info *info /* may be NULL */);
+int speck_sddmm_f32_b32(speck_config *cfg, const speck_dcsr *A, const speck_sddmm_params_b32 *p, speck_dcsr *C,
+                        speck_sddmm_info *info);
 
 /* ---- device COO triplets to a device CSR and back (the reference converts on the host only: convert(CSR&, const COO&),
  *      source/CSR.cpp:173-212).  The caller of a graph layer owns an edge list on the device -- a 2 x E int64 edge_index in

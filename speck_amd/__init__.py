@@ -18,7 +18,7 @@ from .api import (  # noqa: F401
     scale, normalize_rows, pattern_ones, ScaleInfo, MAP_IDENTITY, MAP_ABS, MAP_SQUARE, MAP_ONE, SCALE_MAPS,
     SCALE_NONE, SCALE_MUL, SCALE_DIV, SCALE_TILE_ENTRIES,
     spmv, SpmvInfo, SPMV_TILE_ENTRIES,
-    spmm, SpmmInfo, SPMM_MAX_RHS, SPMM_COLUMN_BLOCK,
+    spmm, SpmmInfo, SPMM_MAX_RHS, SPMM_COLUMN_BLOCK, SPMM_COLUMN_BLOCK_B32,
     TransposePlan, transpose_plan, TplanInfo, spmm_t, spmv_t, SpmmTInfo,
     from_coo, from_edge_index, to_coo, FromCooInfo, COO_TILE_ENTRIES,
     extract, gather_rows, select_columns, induced_subgraph, permute, ExtractInfo, EXTRACT_TILE_ENTRIES,

@@ -103,6 +103,11 @@ class CSddmmParams(C.Structure):
                 ("d_U", C.c_void_p), ("ldu", C.c_uint64), ("d_V", C.c_void_p), ("ldv", C.c_uint64)]
 
 
+class CSddmmParamsB32(C.Structure):
+    # include/speck_c_api.h: speck_sddmm_params_b32 (speck_sddmm_params with the blocks in float: pointers either way)
+    _fields_ = list(CSddmmParams._fields_)
+
+
 class CSddmmInfo(C.Structure):
     # include/speck_c_api.h: speck_sddmm_info
     _fields_ = [("entries", C.c_uint64), ("terms", C.c_uint64), ("nonfinite", C.c_uint64), ("tiles", C.c_uint64),
@@ -237,6 +242,16 @@ _SIGS = {
                                    C.c_void_p, C.c_uint64, _P(CSpmmTInfo)]),
     "speck_spmm_t_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, _P(DCsr), C.c_void_p, C.c_uint64, C.c_uint32, C.c_double,
                                    C.c_void_p, C.c_uint64, _P(CSpmmTInfo)]),
+    "speck_spmm_f64_b32": (C.c_int, [C.c_void_p, C.c_double, _P(DCsr), C.c_void_p, C.c_uint64, C.c_uint32, C.c_double, C.c_void_p,
+                                     C.c_uint64, _P(CSpmmInfo)]),
+    "speck_spmm_f32_b32": (C.c_int, [C.c_void_p, C.c_double, _P(DCsr), C.c_void_p, C.c_uint64, C.c_uint32, C.c_double, C.c_void_p,
+                                     C.c_uint64, _P(CSpmmInfo)]),
+    "speck_spmm_t_f64_b32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, _P(DCsr), C.c_void_p, C.c_uint64, C.c_uint32,
+                                       C.c_double, C.c_void_p, C.c_uint64, _P(CSpmmTInfo)]),
+    "speck_spmm_t_f32_b32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, _P(DCsr), C.c_void_p, C.c_uint64, C.c_uint32,
+                                       C.c_double, C.c_void_p, C.c_uint64, _P(CSpmmTInfo)]),
+    "speck_sddmm_f64_b32": (C.c_int, [C.c_void_p, _P(DCsr), _P(CSddmmParamsB32), _P(DCsr), _P(CSddmmInfo)]),
+    "speck_sddmm_f32_b32": (C.c_int, [C.c_void_p, _P(DCsr), _P(CSddmmParamsB32), _P(DCsr), _P(CSddmmInfo)]),
     "speck_from_coo_f64": (C.c_int, [C.c_void_p, _P(CDcoo), _P(DCsr), _P(CFromCooInfo)]),
     "speck_from_coo_f32": (C.c_int, [C.c_void_p, _P(CDcoo), _P(DCsr), _P(CFromCooInfo)]),
     "speck_to_coo": (C.c_int, [C.c_void_p, _P(DCsr), C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]),

@@ -785,8 +785,33 @@ def spmv(A, x, config, alpha=1.0, beta=0.0, y=None):
 
 # include/speck_c_api.h: the most right-hand sides one call takes
 SPMM_MAX_RHS = 1024
-# ... and the columns a tile takes per round (SPECK_SPMM_COLUMN_BLOCK)
+# ... and the columns a tile takes per round (SPECK_SPMM_COLUMN_BLOCK; SPECK_SPMM_COLUMN_BLOCK_B32 with float blocks)
 SPMM_COLUMN_BLOCK = 4
+SPMM_COLUMN_BLOCK_B32 = 4
+# the element types of the dense blocks of spmm, spmm_t and sddmm (the keyword `blocks`): numpy's type, torch's names
+_BLOCK_TYPES = {"float64": (np.float64, ("torch.float64", "float64")), "float32": (np.float32, ("torch.float32", "float32"))}
+
+
+def _block_type(blocks, op):
+    """the name of a block type as the keyword `blocks` takes it; anything else is refused"""
+    if not isinstance(blocks, str) or blocks not in _BLOCK_TYPES:
+        raise ValueError(f"{op}: blocks must be 'float64' or 'float32', not {blocks!r}")
+    return blocks
+
+
+def _dev_block_buffer(n, blocks):
+    """a device buffer of n block elements from the library's allocator"""
+    d = dCSR(_BLOCK_TYPES[blocks][0])     # (as _dev_f64: the data array of a dCSR without rows)
+    d.alloc(0, 0, max(int(n), 1), allocOffsets=False)
+    return d
+
+
+def _download_block(buf, n, who, blocks):
+    """the first n elements of a _dev_block_buffer as a numpy array of the block type"""
+    dtype = np.dtype(_BLOCK_TYPES[blocks][0])
+    out = np.zeros(max(int(n), 1), dtype=dtype)
+    _check(_lib.load().speck_dcsr_download(C.byref(buf._c), None, None, out.ctypes.data, dtype.itemsize), f"{who}: download")
+    return out[:n]
 
 
 class SpmmInfo(_Info):
@@ -794,15 +819,16 @@ class SpmmInfo(_Info):
     _fields = ("rows_empty", "rows_split", "tiles", "entries", "terms")
 
 
-def _device_block(v, n, k, ld, what, op="spmm"):
-    """(address, k, ld) of a row-major n x k block of float64: a device address with k and ld given, or a 2-D object with
-    data_ptr(), shape, stride() and dtype (a torch tensor, a column slice of one) checked"""
+def _device_block(v, n, k, ld, what, op="spmm", blocks="float64"):
+    """(address, k, ld) of a row-major n x k block of `blocks` elements: a device address with k and ld given, or a 2-D
+    object with data_ptr(), shape, stride() and dtype (a torch tensor, a column slice of one) checked -- a tensor of
+    another type is refused, never converted"""
     who = f"{op}: {what}"
     if hasattr(v, "data_ptr"):
         if not all(hasattr(v, a) for a in ("shape", "stride", "dtype")):
             raise ValueError(f"{who} must have shape, stride() and dtype beside data_ptr()")
-        if str(v.dtype) not in ("torch.float64", "float64"):
-            raise ValueError(f"{who} must be float64, not {v.dtype}")
+        if str(v.dtype) not in _BLOCK_TYPES[blocks][1]:
+            raise ValueError(f"{who} must be {blocks}, not {v.dtype}")
         shape = tuple(int(d) for d in v.shape)
         if len(shape) != 2 or shape[0] != n or (k is not None and shape[1] != int(k)):
             raise ValueError(f"{who} has shape {shape}, the call asks for ({n}, {'k' if k is None else int(k)})")
@@ -816,13 +842,13 @@ def _device_block(v, n, k, ld, what, op="spmm"):
             raise ValueError(f"{who} has rows {s0} apart, not ld = {int(ld)}")
         return int(v.data_ptr()), k, max(s0, k) if n > 1 else (k if ld is None else int(ld))
     if isinstance(v, (bool, float)) or not hasattr(v, "__index__"):
-        raise ValueError(f"{who} must be a 2-D float64 device tensor or a device address, not {type(v).__name__}")
+        raise ValueError(f"{who} must be a 2-D {blocks} device tensor or a device address, not {type(v).__name__}")
     if k is None:
         raise ValueError(f"{who} is a device address: k must be given")
     return int(v), int(k), int(k) if ld is None else int(ld)
 
 
-def spmm(A, X, config, alpha=1.0, beta=0.0, Y=None, k=None, ldx=None, ldy=None):
+def spmm(A, X, config, alpha=1.0, beta=0.0, Y=None, k=None, ldx=None, ldy=None, blocks="float64"):
     """Y = alpha A X + beta Y on a device matrix with k right-hand sides (speck_spmm_f64 / _f32).  X (A.cols x k) and Y
     (A.rows x k, indexed by the row inside A: for a row_view pass the slice) are row-major device blocks of float64 for both
     value types: a 2-D object with data_ptr(), shape, stride() and dtype -- a torch tensor or a column slice Z[:, a:b] of
@@ -831,24 +857,31 @@ def spmm(A, X, config, alpha=1.0, beta=0.0, Y=None, k=None, ldx=None, ldy=None):
     spmv promises holds per column; the padding between the rows of Y is neither read nor written.  The memory X spans
     and the memory Y spans must not overlap (two column slices of one tensor do and are refused).  Y=None is allowed only
     with beta == 0: the result is then a (rows, k) numpy array downloaded from a buffer of the library's allocator.
-    config may be None.  Returns (that array, or None where Y was given and holds the result on the device, SpmmInfo)."""
+    blocks="float32" (speck_spmm_f64_b32 / _f32_b32): X and Y are float32 blocks, ldx and ldy count floats, and the result is
+    bit for bit the float64 call's on X.double(), Y.double(), rounded to float32 once; a float64 tensor is then refused as a
+    float32 one is by default -- a block is never converted.  config may be None.
+    Returns (that array, or None where Y was given and holds the result on the device, SpmmInfo)."""
+    blocks = _block_type(blocks, "spmm")
     if Y is None and float(beta) != 0.0:
         raise ValueError("spmm: beta != 0 needs a Y to read")
-    x_ptr, k, ldx = _device_block(X, A.cols, k, ldx, "X")
+    x_ptr, k, ldx = _device_block(X, A.cols, k, ldx, "X", blocks=blocks)
     if Y is not None:
-        y_ptr, _, ldy = _device_block(Y, A.rows, k, ldy, "Y")
+        y_ptr, _, ldy = _device_block(Y, A.rows, k, ldy, "Y", blocks=blocks)
     if k < 0 or ldx < k or (Y is not None and ldy < k):
         raise ValueError(f"spmm: k = {k} with ldx = {ldx}, ldy = {ldy}: a leading dimension is at least k >= 0")
     L = _lib.load()
-    fn = L.speck_spmm_f32 if A.dtype == np.float32 else L.speck_spmm_f64
+    if blocks == "float32":
+        fn = L.speck_spmm_f32_b32 if A.dtype == np.float32 else L.speck_spmm_f64_b32
+    else:
+        fn = L.speck_spmm_f32 if A.dtype == np.float32 else L.speck_spmm_f64
     buf = None
     if Y is None:
-        buf = _dev_f64(A.rows * k)
+        buf = _dev_block_buffer(A.rows * k, blocks)
         y_ptr, ldy = buf._c.data, k
     info = _lib.CSpmmInfo()
     _check(fn(config._h if config is not None else None, float(alpha), C.byref(A._c), x_ptr, ldx, k, float(beta), y_ptr, ldy,
               C.byref(info)), "spmm")
-    return (_download_f64(buf, A.rows * k, "spmm").reshape(A.rows, k) if buf is not None else None), SpmmInfo(info)
+    return (_download_block(buf, A.rows * k, "spmm", blocks).reshape(A.rows, k) if buf is not None else None), SpmmInfo(info)
 
 
 class TplanInfo(_Info):
@@ -904,29 +937,34 @@ def transpose_plan(A, config=None):
     return TransposePlan(A, config)
 
 
-def spmm_t(A, X, config, plan=None, alpha=1.0, beta=0.0, Y=None, k=None, ldx=None, ldy=None):
+def spmm_t(A, X, config, plan=None, alpha=1.0, beta=0.0, Y=None, k=None, ldx=None, ldy=None, blocks="float64"):
     """Y = alpha A^T X + beta Y on a device matrix through a TransposePlan (speck_spmm_t_f64 / _f32): X is A.rows x k
     (indexed by the row inside A), Y is A.cols x k, row-major device blocks of float64 passed as spmm takes them.  Column c
     of Y is bit for bit spmm(transpose(A), X, ...)'s, so all that spmm promises holds per column; a row_view gives the
     partial sum of its rows.  The plan is verified against A in every call: another pattern raises SpeckError
     (SPECK_ERR_INVALID) with nothing of Y written.  plan=None builds a plan for this one call and frees it -- a training
     loop makes one with transpose_plan(A) and keeps it.  Y=None is allowed only with beta == 0: the result is then a
-    (cols, k) numpy array.  config may be None.  Returns (that array, or None where Y was given, SpmmTInfo)."""
-    return _spmm_t("spmm_t", A, X, config, plan, alpha, beta, Y, k, ldx, ldy)
+    (cols, k) numpy array.  blocks="float32" (speck_spmm_t_f64_b32 / _f32_b32): X and Y are float32 blocks as spmm takes
+    them, the result bit for bit the float64 call's with the same plan rounded to float32 once; one plan serves both.
+    config may be None.  Returns (that array, or None where Y was given, SpmmTInfo)."""
+    return _spmm_t("spmm_t", A, X, config, plan, alpha, beta, Y, k, ldx, ldy, _block_type(blocks, "spmm_t"))
 
 
-def _spmm_t(who, A, X, config, plan, alpha, beta, Y, k, ldx, ldy):
+def _spmm_t(who, A, X, config, plan, alpha, beta, Y, k, ldx, ldy, blocks="float64"):
     if Y is None and float(beta) != 0.0:
         raise ValueError(f"{who}: beta != 0 needs a Y to read")
     if plan is not None and not isinstance(plan, TransposePlan):
         raise ValueError(f"{who}: plan must be a TransposePlan, not {type(plan).__name__}")
-    x_ptr, k, ldx = _device_block(X, A.rows, k, ldx, "X", who)
+    x_ptr, k, ldx = _device_block(X, A.rows, k, ldx, "X", who, blocks)
     if Y is not None:
-        y_ptr, _, ldy = _device_block(Y, A.cols, k, ldy, "Y", who)
+        y_ptr, _, ldy = _device_block(Y, A.cols, k, ldy, "Y", who, blocks)
     if k < 0 or ldx < k or (Y is not None and ldy < k):
         raise ValueError(f"{who}: k = {k} with ldx = {ldx}, ldy = {ldy}: a leading dimension is at least k >= 0")
     L = _lib.load()
-    fn = L.speck_spmm_t_f32 if A.dtype == np.float32 else L.speck_spmm_t_f64
+    if blocks == "float32":
+        fn = L.speck_spmm_t_f32_b32 if A.dtype == np.float32 else L.speck_spmm_t_f64_b32
+    else:
+        fn = L.speck_spmm_t_f32 if A.dtype == np.float32 else L.speck_spmm_t_f64
     own = None
     if plan is None:
         plan = own = TransposePlan(A, config)
@@ -934,7 +972,7 @@ def _spmm_t(who, A, X, config, plan, alpha, beta, Y, k, ldx, ldy):
         handle = plan._handle(who)
         buf = None
         if Y is None:
-            buf = _dev_f64(A.cols * k)
+            buf = _dev_block_buffer(A.cols * k, blocks)
             y_ptr, ldy = buf._c.data, k
         info = _lib.CSpmmTInfo()
         _check(fn(config._h if config is not None else None, handle, float(alpha), C.byref(A._c), x_ptr, ldx, k, float(beta),
@@ -942,7 +980,7 @@ def _spmm_t(who, A, X, config, plan, alpha, beta, Y, k, ldx, ldy):
     finally:
         if own is not None:
             own.free()
-    return (_download_f64(buf, A.cols * k, who).reshape(A.cols, k) if buf is not None else None), SpmmTInfo(info)
+    return (_download_block(buf, A.cols * k, who, blocks).reshape(A.cols, k) if buf is not None else None), SpmmTInfo(info)
 
 
 def spmv_t(A, x, config, plan=None, alpha=1.0, beta=0.0, y=None):
@@ -1384,7 +1422,8 @@ class SddmmInfo(_Info):
     _fields = ("entries", "terms", "nonfinite", "tiles", "lanes")
 
 
-def sddmm(A, U, V, config, alpha=1.0, beta=0.0, mode="axpby", matOut=None, inplace=False, k=None, ldu=None, ldv=None):
+def sddmm(A, U, V, config, alpha=1.0, beta=0.0, mode="axpby", matOut=None, inplace=False, k=None, ldu=None, ldv=None,
+          blocks="float64"):
     """C = alpha (U V^T) on A's pattern + beta A (speck_sddmm_f64 / _f32): d(i,j) = sum_c U(i,c) V(j,c) only where A holds
     an entry.  mode "hadamard" gives alpha d(i,j) A(i,j) instead (beta must be 0).  U (A.rows x k, indexed by the row inside
     A: for a row_view pass the slice) and V (A.cols x k) are row-major device blocks of float64 for both value types, as
@@ -1395,7 +1434,10 @@ def sddmm(A, U, V, config, alpha=1.0, beta=0.0, mode="axpby", matOut=None, inpla
     of U or V lands in exactly the entries that reference it and is counted in info.nonfinite.  The gradient of spmm
     with respect to A's values is sddmm(A, dY, X).  inplace=True overwrites A's values (on a row_view: the view's
     entries only); otherwise the result goes to matOut (a new matrix when None) with A's pattern, offsets rebased to 0.
-    config may be None.  Returns (matOut or A, SddmmInfo)."""
+    blocks="float32" (speck_sddmm_f64_b32 / _f32_b32): U and V are float32 blocks, ldu and ldv count floats, and the result
+    and the info are bit for bit the float64 call's on U.double(), V.double(); a float64 tensor is then refused as a
+    float32 one is by default -- a block is never converted.  config may be None.  Returns (matOut or A, SddmmInfo)."""
+    blocks = _block_type(blocks, "sddmm")
     if isinstance(mode, str):
         if mode not in SDDMM_MODES:
             raise ValueError(f"sddmm: unknown mode {mode!r} (one of {', '.join(SDDMM_MODES)})")
@@ -1406,15 +1448,18 @@ def sddmm(A, U, V, config, alpha=1.0, beta=0.0, mode="axpby", matOut=None, inpla
         raise ValueError("sddmm: beta must be 0 with mode 'hadamard'")
     if inplace and matOut is not None:
         raise ValueError("sddmm: inplace=True and matOut exclude each other")
-    p = _lib.CSddmmParams()
+    p = _lib.CSddmmParamsB32() if blocks == "float32" else _lib.CSddmmParams()
     p.mode, p.alpha, p.beta = int(mode), float(alpha), float(beta)
-    p.d_U, k, p.ldu = _device_block(U, A.rows, k, ldu, "U", "sddmm")
-    p.d_V, k, p.ldv = _device_block(V, A.cols, k, ldv, "V", "sddmm")
+    p.d_U, k, p.ldu = _device_block(U, A.rows, k, ldu, "U", "sddmm", blocks)
+    p.d_V, k, p.ldv = _device_block(V, A.cols, k, ldv, "V", "sddmm", blocks)
     if k < 0 or p.ldu < k or p.ldv < k:
         raise ValueError(f"sddmm: k = {k} with ldu = {p.ldu}, ldv = {p.ldv}: a leading dimension is at least k >= 0")
     p.k = k
     L = _lib.load()
-    fn = L.speck_sddmm_f32 if A.dtype == np.float32 else L.speck_sddmm_f64
+    if blocks == "float32":
+        fn = L.speck_sddmm_f32_b32 if A.dtype == np.float32 else L.speck_sddmm_f64_b32
+    else:
+        fn = L.speck_sddmm_f32 if A.dtype == np.float32 else L.speck_sddmm_f64
     info = _lib.CSddmmInfo()
     h = config._h if config is not None else None
     if inplace:

@@ -24,6 +24,11 @@
 //   scale_offsets_kernel  (scale.hpp) a new C only: its row offsets, rebased to 0.
 // Every entry is written once by one thread; `nonfinite` is an integer counter (one atomic per workgroup).  No kernel
 // uses scratch.  The host side is the side operations' own (side_call.hpp, compact.hpp: C by the multiply's rule).
+//
+// speck_sddmm_*_b32: U and V in float (B = float below).  The same tiles, the same L(k), the same tree through the same
+// kernel with the block type as a template parameter; an element is widened where its term is formed ((double)u *
+// (double)v: exact), so C is bit for bit the doubles' result on widened blocks.  A lane's pair of columns is 8 bytes: one
+// 8-byte load where the block lies on 8 bytes and its ld is even, 4-byte loads elsewhere.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -64,19 +69,19 @@ inline u32 lanes_of(u32 k)
 }
 #endif
 
-template <typename T>
+template <typename T, typename B = double>
 struct SddmmArgs {
     const u32* ro;
     const u32* col;  // null: k == 0 in place, nobody asks
     const T* src;    // read where need_a
     T* dst;          // in place: src, entry p at p; C's values otherwise, entry p at p - row_offsets[0]
     u32* dst_col;    // C's column ids (null: in place)
-    const double *u, *v;
+    const B *u, *v;
     u64 nnz, ldu, ldv;
     u32 rows, k, mode;
     u32 need_a;          // HADAMARD, or beta != 0
     u32 aligned;         // col (and dst_col) start on 16-byte boundaries
-    u32 wide_u, wide_v;  // the block starts on a 16-byte boundary and its ld is even: a pair of columns lies on one
+    u32 wide_u, wide_v;  // the block starts on a boundary of 2 sizeof(B) bytes and its ld is even: a pair of columns lies on one
     double alpha, beta;
     const u32* tile_rows;
     ScaleStatus* st;
@@ -89,21 +94,22 @@ struct alignas(N * sizeof(V)) Vec {
 
 // ------------------------------------------------------------------------------------------------ tiles
 // the columns c, c + 1 of a row (`two`: c + 1 < k; the column behind the last one is never read)
-__device__ __forceinline__ void load_pair(const double* at, bool wide, bool two, double& x0, double& x1)
+template <typename B>
+__device__ __forceinline__ void load_pair(const B* at, bool wide, bool two, B& x0, B& x1)
 {
     if (wide && two) {
-        const Vec<double, 2> p = *reinterpret_cast<const Vec<double, 2>*>(at);
+        const Vec<B, 2> p = *reinterpret_cast<const Vec<B, 2>*>(at);
         x0 = p.v[0], x1 = p.v[1];
     } else {
         x0 = at[0];
-        x1 = two ? at[1] : 0.0;
+        x1 = two ? at[1] : B(0);
     }
 }
 
 // Phase B: the entries [e_lo, e_hi) of the tile, whose (row, id) stand in LDS.  Returns the results this thread wrote that
 // are not finite.
-template <typename T, u32 L>
-__device__ __forceinline__ u32 dot_entries(const SddmmArgs<T>& g, const u32* s_row, const u32* s_id, u32 e_lo, u32 e_hi, u64 tile0,
+template <typename T, u32 L, typename B>
+__device__ __forceinline__ u32 dot_entries(const SddmmArgs<T, B>& g, const u32* s_row, const u32* s_id, u32 e_lo, u32 e_hi, u64 tile0,
                                            u64 d0)
 {
 #pragma clang fp contract(off)
@@ -114,7 +120,7 @@ __device__ __forceinline__ u32 dot_entries(const SddmmArgs<T>& g, const u32* s_r
     u32 bad = 0;
     for (u32 eb = e_lo; eb < e_hi; eb += G * kFlight) {
         u32 e[kFlight];
-        const double *ur[kFlight], *vr[kFlight];
+        const B *ur[kFlight], *vr[kFlight];
         double a[kFlight], p[kFlight];
 #pragma unroll
         for (u32 f = 0; f < kFlight; ++f) {
@@ -129,7 +135,7 @@ __device__ __forceinline__ u32 dot_entries(const SddmmArgs<T>& g, const u32* s_r
         // lane l: the pairs q = l, l + L, ...; all loads of a trip before its terms; the first term seeds the sum
         auto trip = [&](u32 c, auto seeds) {
             const bool two = c + 1 < k;
-            double x0[kFlight], x1[kFlight], y0[kFlight], y1[kFlight];
+            B x0[kFlight], x1[kFlight], y0[kFlight], y1[kFlight];
 #pragma unroll
             for (u32 f = 0; f < kFlight; ++f) {
                 load_pair(ur[f] + c, wide_u, two, x0[f], x1[f]);
@@ -137,8 +143,9 @@ __device__ __forceinline__ u32 dot_entries(const SddmmArgs<T>& g, const u32* s_r
             }
 #pragma unroll
             for (u32 f = 0; f < kFlight; ++f) {
-                p[f] = decltype(seeds)::value ? x0[f] * y0[f] : p[f] + x0[f] * y0[f];
-                if (two) p[f] = p[f] + x1[f] * y1[f];
+                const double t0 = (double)x0[f] * (double)y0[f];
+                p[f] = decltype(seeds)::value ? t0 : p[f] + t0;
+                if (two) p[f] = p[f] + (double)x1[f] * (double)y1[f];
             }
         };
         u32 c = 2 * l;
@@ -167,8 +174,8 @@ __device__ __forceinline__ u32 dot_entries(const SddmmArgs<T>& g, const u32* s_r
     return bad;
 }
 
-template <typename T, u32 L>
-__global__ __launch_bounds__(kThreads) void sddmm_tile_kernel(const SddmmArgs<T> g)
+template <typename T, u32 L, typename B>
+__global__ __launch_bounds__(kThreads) void sddmm_tile_kernel(const SddmmArgs<T, B> g)
 {
     SPECK_POISON();
     __shared__ u32 s_row[kTile];        // at the place of a row's first entry: the row; behind phase A: every entry's row
@@ -262,17 +269,25 @@ __global__ __launch_bounds__(kThreads) void sddmm_tile_kernel(const SddmmArgs<T>
 }
 
 // ------------------------------------------------------------------------------------------------ host
-template <typename T, u32 L>
-void launch_tiles(u32 lanes, u32 tiles, hipStream_t s, const SddmmArgs<T>& g)
+template <typename T, u32 L, typename B>
+void launch_tiles(u32 lanes, u32 tiles, hipStream_t s, const SddmmArgs<T, B>& g)
 {
-    if (lanes == L) SPECK_LAUNCH((sddmm_tile_kernel<T, L>), dim3(tiles), dim3(kThreads), 0, s, g);
+    if (lanes == L) SPECK_LAUNCH((sddmm_tile_kernel<T, L, B>), dim3(tiles), dim3(kThreads), 0, s, g);
     else if constexpr (L < kMaxLanes) launch_tiles<T, 2 * L>(lanes, tiles, s, g);
 }
 
-template <typename T>
-int sddmm_run(ScaleScratch* sc, hipStream_t s, const speck_dcsr* A, const speck_sddmm_params* p, speck_dcsr* C,
-              speck_sddmm_info* info, COut* out)
+// whether a pair of columns (c even) of a block lies on a boundary of its own size
+template <typename B>
+inline bool pair_aligned(const B* d, u64 ld)
 {
+    return reinterpret_cast<uintptr_t>(d) % (2 * sizeof(B)) == 0 && ld % 2 == 0;
+}
+
+// P: speck_sddmm_params or speck_sddmm_params_b32 (B: what its blocks hold)
+template <typename T, typename P>
+int sddmm_run(ScaleScratch* sc, hipStream_t s, const speck_dcsr* A, const P* p, speck_dcsr* C, speck_sddmm_info* info, COut* out)
+{
+    using B = std::remove_cv_t<std::remove_pointer_t<decltype(p->d_U)>>;
     const u32 rows = (u32)A->rows;
     const u64 nnz = A->nnz;
     if (rows == 0) return C ? publish_empty_c(C, A->cols, sizeof(T), s, out) : SPECK_OK;
@@ -298,10 +313,10 @@ int sddmm_run(ScaleScratch* sc, hipStream_t s, const speck_dcsr* A, const speck_
     if (nnz) {
         T* dst = C ? static_cast<T*>(out->val) : static_cast<T*>(A->data);
         const bool aligned = on_16_bytes(A->col_ids) && (!C || on_16_bytes(out->col));
-        const SddmmArgs<T> g{A->row_offsets, need_col ? A->col_ids : nullptr, static_cast<const T*>(A->data), dst,
-                             C ? out->col : nullptr, p->d_U, p->d_V, nnz, p->ldu, p->ldv, rows, p->k, p->mode, need_a ? 1u : 0u,
-                             aligned ? 1u : 0u, on_16_bytes(p->d_U) && p->ldu % 2 == 0 ? 1u : 0u,
-                             on_16_bytes(p->d_V) && p->ldv % 2 == 0 ? 1u : 0u, p->alpha, p->beta, tile_rows, st};
+        const SddmmArgs<T, B> g{A->row_offsets, need_col ? A->col_ids : nullptr, static_cast<const T*>(A->data), dst,
+                                C ? out->col : nullptr, p->d_U, p->d_V, nnz, p->ldu, p->ldv, rows, p->k, p->mode, need_a ? 1u : 0u,
+                                aligned ? 1u : 0u, pair_aligned(p->d_U, p->ldu) ? 1u : 0u, pair_aligned(p->d_V, p->ldv) ? 1u : 0u,
+                                p->alpha, p->beta, tile_rows, st};
         launch_tiles<T, 1>(lanes_of(p->k), max_tiles, s, g);
     }
     if (C) launch_scale_offsets(s, A, out->ro, st);
@@ -321,17 +336,18 @@ int sddmm_run(ScaleScratch* sc, hipStream_t s, const speck_dcsr* A, const speck_
 const char* const kGuardNamesC[5] = {"sddmm status", "sddmm tile rows", "C.data", "C.col_ids", "C.row_offsets"};
 const char* const kGuardNamesA[5] = {"sddmm status", "sddmm tile rows", "A.data", "A.col_ids", "A.row_offsets"};
 
-// whether [v, v + doubles) holds one of X's three pointers
-bool span_holds_one_of(const double* v, u64 doubles, const speck_dcsr* X)
+// whether the `elements` elements from v on hold one of X's three pointers
+template <typename B>
+bool span_holds_one_of(const B* v, u64 elements, const speck_dcsr* X)
 {
-    const u64 v0 = reinterpret_cast<uintptr_t>(v), bytes = 8 * doubles;
+    const u64 v0 = reinterpret_cast<uintptr_t>(v), bytes = sizeof(B) * elements;
     for (const void* q : {static_cast<const void*>(X->data), static_cast<const void*>(X->col_ids), static_cast<const void*>(X->row_offsets)})
         if (q && reinterpret_cast<uintptr_t>(q) - v0 < bytes) return true;  // (q < v0 wraps to more than any span)
     return false;
 }
 
-template <typename T>
-int sddmm_impl(speck_config* cfg, const speck_dcsr* A, const speck_sddmm_params* p, speck_dcsr* C, speck_sddmm_info* info)
+template <typename T, typename P>
+int sddmm_impl(speck_config* cfg, const speck_dcsr* A, const P* p, speck_dcsr* C, speck_sddmm_info* info)
 {
     if (!A || !p) return SPECK_ERR_INVALID;
     if (p->mode > SPECK_SDDMM_HADAMARD || p->alpha != p->alpha || p->beta != p->beta) return SPECK_ERR_INVALID;
@@ -349,7 +365,7 @@ int sddmm_impl(speck_config* cfg, const speck_dcsr* A, const speck_sddmm_params*
     if (A->nnz && !A->data && (need_a || !C)) return SPECK_ERR_INVALID;
     // what the call may read of the blocks, padding inside included, holds nothing the call reads as A or writes
     if (p->k) {
-        const double* blocks[2] = {p->d_U, p->d_V};
+        const decltype(p->d_U) blocks[2] = {p->d_U, p->d_V};
         const u64 spans[2] = {A->rows ? (A->rows - 1) * p->ldu + p->k : 0, A->cols ? (A->cols - 1) * p->ldv + p->k : 0};
         for (int b = 0; b < 2; ++b)
             if (blocks[b] && (span_holds_one_of(blocks[b], spans[b], A) || (C && span_holds_one_of(blocks[b], spans[b], C))))
@@ -378,6 +394,16 @@ int speck_sddmm_f64(speck_config* cfg, const speck_dcsr* A, const speck_sddmm_pa
 }
 
 int speck_sddmm_f32(speck_config* cfg, const speck_dcsr* A, const speck_sddmm_params* p, speck_dcsr* C, speck_sddmm_info* info)
+{
+    return sddmm_impl<float>(cfg, A, p, C, info);
+}
+
+int speck_sddmm_f64_b32(speck_config* cfg, const speck_dcsr* A, const speck_sddmm_params_b32* p, speck_dcsr* C, speck_sddmm_info* info)
+{
+    return sddmm_impl<double>(cfg, A, p, C, info);
+}
+
+int speck_sddmm_f32_b32(speck_config* cfg, const speck_dcsr* A, const speck_sddmm_params_b32* p, speck_dcsr* C, speck_sddmm_info* info)
 {
     return sddmm_impl<float>(cfg, A, p, C, info);
 }

@@ -26,6 +26,13 @@
 // All index arithmetic i ld + c is 64-bit.  No floating-point atomic; one read-back, at the end.
 // What is spmv.hip's word for word -- a tile kernel's opening, the load of the entries, the check of the ids, the write of
 // a y; the scratch, the check's launch, the frame of the call -- is tile_combine.hpp's and tile_call.hpp's.
+//
+// speck_spmm_*_b32: X and Y in float (B = float below).  The same walk through the same functions; an element of X is
+// widened where its term is formed ((double)a * (double)x: the widening is exact), Y is rounded to float once, in write_y.
+// A 16-byte load holds FOUR columns of an entry: a block of kCB32 columns keeps 16 kCB32 floats in flight -- half the
+// registers of the doubles' block -- loaded 16 bytes at a time where d_X lies on 16 bytes and ldx % 4 == 0, 8 bytes where
+// d_X lies on 8 and ldx is even, 4 bytes elsewhere, with the same bits.  The kernels are the doubles' with the block type as a
+// template parameter (a body shared through a function moved the doubles' registers: DESIGN.md 4.26).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -48,20 +55,28 @@ using Sum = Op<SPECK_REDUCE_SUM>;
 // the columns whose gathers are in flight together (the registers: DESIGN.md 4.17)
 constexpr u32 kCB = SPECK_SPMM_COLUMN_BLOCK;
 static_assert(kCB % 2 == 0, "a 16-byte gather takes two columns");
+// the same for float blocks (SPECK_SPMM_B32_FORCE_BLOCK: measurement builds only, profiles/blocks32.txt)
+#ifdef SPECK_SPMM_B32_FORCE_BLOCK
+constexpr u32 kCB32 = SPECK_SPMM_B32_FORCE_BLOCK;
+#else
+constexpr u32 kCB32 = SPECK_SPMM_COLUMN_BLOCK_B32;
+#endif
+static_assert(kCB32 % 4 == 0, "a 16-byte gather takes four columns");
 
-template <typename T>
+template <typename T, typename B = double>
 struct SpmmArgs {
     const u32* ro;
     const u32* col;
     const T* data;
-    const double* x;
+    const B* x;
     double* sums;  // rows k doubles: s(i,c) of the rows that lie whole in one tile
     u64 nnz, ldx;
     u32 rows, cols;  // cols >= 1
     u32 k;           // >= 1
     u32 max_tiles;   // the records of column c start at recs + c max_tiles
     u32 aligned;     // data and col start on 16-byte boundaries
-    u32 pairs;       // x starts on a 16-byte boundary and ldx is even: X(j, c) with even c lies on one
+    u32 pairs;       // x starts on a 16-byte boundary and ldx is even: X(j, c) with even c lies on one (B = float: the
+                     // elements of the widest load every X(j, c) with c a multiple of it is aligned to -- 4, 2 or 1)
     TileRec* recs;
     const u32* tile_rows;
     ProductStatus* st;
@@ -70,28 +85,30 @@ struct SpmmArgs {
 // ------------------------------------------------------------------------------------------------ tiles
 // The columns [c0, c0 + W) of a tile whose row-start bitmap stands (tile_begin): all 16 W gathers X[id ldx + c0 ..) are
 // issued before the first term, then per column the terms and the segmented combine, with a barrier before the next
-// column takes the LDS.  PAIR: X(j, c0) lies on a 16-byte boundary for every j and W is even -- one 16-byte load per entry
-// and pair of columns.  a: the thread's values, in double; c: its ids, checked, < cols; in_mask: which entries the
-// matrix reaches.
-template <u32 W, bool PAIR, typename T>
-__device__ __forceinline__ void column_block(const SpmmArgs<T>& g, TileLds& s_tile, const TileRows rows, const double (&a)[kPer],
+// column takes the LDS.  VW: the elements of X a load takes -- X(j, c0) lies on a boundary of VW elements for every j and
+// VW divides W (doubles: one 16-byte load per entry and pair of columns; floats: per four columns, or 8 bytes per pair).
+// a: the thread's values, in double; c: its ids, checked, < cols; in_mask: which entries the matrix reaches.  A gathered
+// element stays in B until its term is formed.
+template <u32 W, u32 VW, typename T, typename B>
+__device__ __forceinline__ void column_block(const SpmmArgs<T, B>& g, TileLds& s_tile, const TileRows rows, const double (&a)[kPer],
                                              u32 (&c)[kPer], u32 in_mask, const TileFrame& f, u32 c0)
 {
 #pragma clang fp contract(off)
-    static_assert(!PAIR || W % 2 == 0, "a 16-byte gather takes two columns");
+    static_assert(W % VW == 0 && VW * sizeof(B) <= 16, "whole loads of at most 16 bytes");
     // (the ids pass through an empty asm: the 16 addresses derived from them -- 32 registers -- are then computed per
     //  block and not kept over the whole column loop)
 #pragma unroll
     for (u32 e = 0; e < kPer; ++e) asm volatile("" : "+v"(c[e]));
-    double xv[W][kPer];
+    B xv[W][kPer];
 #pragma unroll
     for (u32 e = 0; e < kPer; ++e) {
-        const double* src = g.x + (u64(c[e]) * g.ldx + c0);
-        if (PAIR) {
+        const B* src = g.x + (u64(c[e]) * g.ldx + c0);
+        if (VW > 1) {
 #pragma unroll
-            for (u32 j = 0; j < W; j += 2) {
-                const Vec<double, 2> p = reinterpret_cast<const Vec<double, 2>*>(src)[j / 2];
-                xv[j][e] = p.v[0], xv[j + 1][e] = p.v[1];
+            for (u32 j = 0; j < W; j += VW) {
+                const BlockVec<B, VW> p = reinterpret_cast<const BlockVec<B, VW>*>(src)[j / VW];
+#pragma unroll
+                for (u32 i = 0; i < VW; ++i) xv[j + i][e] = p.v[i];
             }
         } else {
 #pragma unroll
@@ -104,7 +121,7 @@ __device__ __forceinline__ void column_block(const SpmmArgs<T>& g, TileLds& s_ti
     for (u32 j = 0; j < W; ++j) {
         double v[kPer];
 #pragma unroll
-        for (u32 e = 0; e < kPer; ++e) v[e] = ((in_mask >> e) & 1u) ? a[e] * xv[j][e] : Sum::ident();
+        for (u32 e = 0; e < kPer; ++e) v[e] = ((in_mask >> e) & 1u) ? a[e] * (double)xv[j][e] : Sum::ident();
         const u32 cc = c0 + j;
         combine_terms<Sum>(s_tile, rows, v, g.ro, g.recs + (u64(cc) * g.max_tiles + blockIdx.x), f.tile0, f.lo, f.hi,
                            [sums, nk, cc](u32 r, double val) { sums[u64(r) * nk + cc] = val; });
@@ -113,8 +130,8 @@ __device__ __forceinline__ void column_block(const SpmmArgs<T>& g, TileLds& s_ti
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void spmm_tile_kernel(const SpmmArgs<T> g)
+template <typename T, typename B>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void spmm_tile_kernel(const SpmmArgs<T, B> g)
 {
     SPECK_POISON();
     __shared__ TileLds s_tile;
@@ -149,20 +166,36 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
     // the columns in blocks of kCB, then what is left in pairs and alone; one straight path per form of block
     const u32 nk = g.k;
     u32 c0 = 0;
-    if (g.pairs) {
-        for (; c0 + kCB <= nk; c0 += kCB) column_block<kCB, true>(g, s_tile, rows, a, c, in_mask, f, c0);
-        for (; c0 + 2 <= nk; c0 += 2) column_block<2, true>(g, s_tile, rows, a, c, in_mask, f, c0);
+    if constexpr (sizeof(B) == 8) {
+        if (g.pairs) {
+            for (; c0 + kCB <= nk; c0 += kCB) column_block<kCB, 2>(g, s_tile, rows, a, c, in_mask, f, c0);
+            for (; c0 + 2 <= nk; c0 += 2) column_block<2, 2>(g, s_tile, rows, a, c, in_mask, f, c0);
+        } else {
+            for (; c0 + kCB <= nk; c0 += kCB) column_block<kCB, 1>(g, s_tile, rows, a, c, in_mask, f, c0);
+        }
     } else {
-        for (; c0 + kCB <= nk; c0 += kCB) column_block<kCB, false>(g, s_tile, rows, a, c, in_mask, f, c0);
+        // (c0 stays a multiple of the load's width: blocks of kCB32, then four, then two columns)
+        if (g.pairs == 4) {
+            for (; c0 + kCB32 <= nk; c0 += kCB32) column_block<kCB32, 4>(g, s_tile, rows, a, c, in_mask, f, c0);
+            if constexpr (kCB32 > 4)
+                for (; c0 + 4 <= nk; c0 += 4) column_block<4, 4>(g, s_tile, rows, a, c, in_mask, f, c0);
+        } else if (g.pairs == 2) {
+            for (; c0 + kCB32 <= nk; c0 += kCB32) column_block<kCB32, 2>(g, s_tile, rows, a, c, in_mask, f, c0);
+        } else {
+            for (; c0 + kCB32 <= nk; c0 += kCB32) column_block<kCB32, 1>(g, s_tile, rows, a, c, in_mask, f, c0);
+        }
+        if (g.pairs >= 2)
+            for (; c0 + 2 <= nk; c0 += 2) column_block<2, 2>(g, s_tile, rows, a, c, in_mask, f, c0);
     }
-    for (; c0 < nk; ++c0) column_block<1, false>(g, s_tile, rows, a, c, in_mask, f, c0);
+    for (; c0 < nk; ++c0) column_block<1, 1>(g, s_tile, rows, a, c, in_mask, f, c0);
 }
 
 // ------------------------------------------------------------------------------------------------ finish, and Y
+template <typename B>
 __global__ __launch_bounds__(kThreads) void spmm_finish_kernel(const u32* __restrict__ ro, u32 rows, u64 nnz, u32 k, u32 max_tiles,
                                                                u32 chain_blocks, u32 row_blocks, const double* __restrict__ sums,
                                                                const TileRec* __restrict__ recs, double alpha, double beta,
-                                                               double* __restrict__ y, u64 ldy, ProductStatus* st)
+                                                               B* __restrict__ y, u64 ldy, ProductStatus* st)
 {
     SPECK_POISON();
     __shared__ double s_w[kWaves];
@@ -201,24 +234,32 @@ __global__ __launch_bounds__(kThreads) void spmm_finish_kernel(const u32* __rest
 }
 
 // ------------------------------------------------------------------------------------------------ host
-template <typename T>
-int spmm_run(TileScratch* sc, hipStream_t s, double alpha, const speck_dcsr* A, const double* d_X, u64 ldx, u32 k, double beta,
-             double* d_Y, u64 ldy, ProductStatus* h)
+// the widest load every X(j, c) with c a multiple of its width is aligned to, as SpmmArgs::pairs has it
+inline u32 gather_width(const double* d_X, u64 ldx) { return on_16_bytes(d_X) && ldx % 2 == 0 ? 1u : 0u; }
+inline u32 gather_width(const float* d_X, u64 ldx)
+{
+    const uintptr_t at = reinterpret_cast<uintptr_t>(d_X);
+    return at % 16 == 0 && ldx % 4 == 0 ? 4u : at % 8 == 0 && ldx % 2 == 0 ? 2u : 1u;
+}
+
+template <typename T, typename B>
+int spmm_run(TileScratch* sc, hipStream_t s, double alpha, const speck_dcsr* A, const B* d_X, u64 ldx, u32 k, double beta,
+             B* d_Y, u64 ldy, ProductStatus* h)
 {
     const u32 rows = (u32)A->rows;
     TileWork<ProductStatus> w;
     int rc = carve_and_check(sc, s, A, k, size_t(rows) * k, &w);
     if (rc != SPECK_OK) return rc;
     if (w.max_tiles) {
-        const SpmmArgs<T> g{A->row_offsets, A->col_ids, static_cast<const T*>(A->data), d_X, w.sums, A->nnz, ldx, rows, (u32)A->cols, k,
-                            w.max_tiles, on_16_bytes(A->data) && on_16_bytes(A->col_ids) ? 1u : 0u,
-                            on_16_bytes(d_X) && ldx % 2 == 0 ? 1u : 0u, w.recs, w.tile_rows, w.st};
-        SPECK_LAUNCH(spmm_tile_kernel<T>, dim3(w.max_tiles), dim3(kThreads), 0, s, g);
+        const SpmmArgs<T, B> g{A->row_offsets, A->col_ids, static_cast<const T*>(A->data), d_X, w.sums, A->nnz, ldx, rows, (u32)A->cols, k,
+                               w.max_tiles, on_16_bytes(A->data) && on_16_bytes(A->col_ids) ? 1u : 0u, gather_width(d_X, ldx), w.recs,
+                               w.tile_rows, w.st};
+        SPECK_LAUNCH((spmm_tile_kernel<T, B>), dim3(w.max_tiles), dim3(kThreads), 0, s, g);
     }
     // (rows <= 2^27, k <= 2^10, tiles <= 2^20 + 1: the grid stays below 2^30)
     const u32 chain_blocks = (u32)((u64(w.max_tiles) * k + kWaves - 1) / kWaves);
     const u32 row_blocks = (u32)((u64(rows) * k + kThreads - 1) / kThreads);
-    SPECK_LAUNCH(spmm_finish_kernel, dim3(chain_blocks + row_blocks + 1u), dim3(kThreads), 0, s, A->row_offsets, rows, A->nnz, k,
+    SPECK_LAUNCH(spmm_finish_kernel<B>, dim3(chain_blocks + row_blocks + 1u), dim3(kThreads), 0, s, A->row_offsets, rows, A->nnz, k,
                  w.max_tiles, chain_blocks, row_blocks, w.sums, w.recs, alpha, beta, d_Y, ldy, w.st);
     // the ONE read-back of the call: the two verdicts, the counters
     rc = read_status(s, w.st, h);
@@ -228,8 +269,8 @@ int spmm_run(TileScratch* sc, hipStream_t s, double alpha, const speck_dcsr* A, 
 
 const char* const kGuardNames[3] = {"spmm status", "spmm tile records and rows", "spmm row sums"};
 
-template <typename T>
-int spmm_impl(speck_config* cfg, double alpha, const speck_dcsr* A, const double* d_X, u64 ldx, u32 k, double beta, double* d_Y,
+template <typename T, typename B>
+int spmm_impl(speck_config* cfg, double alpha, const speck_dcsr* A, const B* d_X, u64 ldx, u32 k, double beta, B* d_Y,
               u64 ldy, speck_spmm_info* info)
 {
     if (!A || alpha != alpha || beta != beta) return SPECK_ERR_INVALID;
@@ -245,7 +286,7 @@ int spmm_impl(speck_config* cfg, double alpha, const speck_dcsr* A, const double
     if (d_X && d_Y && A->rows && A->cols && k) {
         // what the call may touch: [d_X, d_X + (cols - 1) ldx + k) and [d_Y, d_Y + (rows - 1) ldy + k), padding inside included
         const u64 x0 = reinterpret_cast<uintptr_t>(d_X), y0 = reinterpret_cast<uintptr_t>(d_Y);
-        const u64 xs = 8 * ((A->cols - 1) * ldx + k), ys = 8 * ((A->rows - 1) * ldy + k);
+        const u64 xs = sizeof(B) * ((A->cols - 1) * ldx + k), ys = sizeof(B) * ((A->rows - 1) * ldy + k);
         if (x0 < y0 + ys && y0 < x0 + xs) return SPECK_ERR_INVALID;
     }
     if (info) *info = speck_spmm_info{};
@@ -253,7 +294,7 @@ int spmm_impl(speck_config* cfg, double alpha, const speck_dcsr* A, const double
     if (A->rows == 0 || k == 0) return SPECK_OK;  // no row or no column: nothing to write
     ProductStatus h{};
     const int rc = run_tile_call(cfg, spmm_scratch, kGuardNames, 3, " by the product with several right-hand sides",
-                                 [&](TileScratch* sc, hipStream_t s) { return spmm_run<T>(sc, s, alpha, A, d_X, ldx, k, beta, d_Y, ldy, &h); });
+                                 [&](TileScratch* sc, hipStream_t s) { return spmm_run<T, B>(sc, s, alpha, A, d_X, ldx, k, beta, d_Y, ldy, &h); });
     if (rc != SPECK_OK) return rc;
     if (info) {
         fill_tile_info(info, h, A);
@@ -274,6 +315,18 @@ int speck_spmm_f64(speck_config* cfg, double alpha, const speck_dcsr* A, const d
 
 int speck_spmm_f32(speck_config* cfg, double alpha, const speck_dcsr* A, const double* d_X, uint64_t ldx, uint32_t k, double beta,
                    double* d_Y, uint64_t ldy, speck_spmm_info* info)
+{
+    return spmm_impl<float>(cfg, alpha, A, d_X, ldx, k, beta, d_Y, ldy, info);
+}
+
+int speck_spmm_f64_b32(speck_config* cfg, double alpha, const speck_dcsr* A, const float* d_X, uint64_t ldx, uint32_t k, double beta,
+                       float* d_Y, uint64_t ldy, speck_spmm_info* info)
+{
+    return spmm_impl<double>(cfg, alpha, A, d_X, ldx, k, beta, d_Y, ldy, info);
+}
+
+int speck_spmm_f32_b32(speck_config* cfg, double alpha, const speck_dcsr* A, const float* d_X, uint64_t ldx, uint32_t k, double beta,
+                       float* d_Y, uint64_t ldy, speck_spmm_info* info)
 {
     return spmm_impl<float>(cfg, alpha, A, d_X, ldx, k, beta, d_Y, ldy, info);
 }

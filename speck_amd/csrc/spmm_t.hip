@@ -20,6 +20,10 @@
 //   spmm_t_finish_kernel  spmm_finish_kernel's sibling over (t_ro, cols) (sharing it would have changed spmm.hip): queued
 //                         last, it sees the verdict of EVERY tile, and only it writes Y.
 // t_pos < nnz and t_row < rows are the library's own; nothing of the caller's is ever used as an index.
+//
+// speck_spmm_t_*_b32: X and Y in float (B = float below), as spmm.hip has them: the same kernels with the block type as a
+// template parameter, an element of X widened where its term is formed, Y rounded to float once in write_y, blocks of
+// kCB32 columns loaded 16, 8 or 4 bytes at a time.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -42,6 +46,13 @@ using Sum = Op<SPECK_REDUCE_SUM>;
 
 constexpr u32 kCB = SPECK_SPMM_COLUMN_BLOCK;
 static_assert(kCB % 2 == 0, "a 16-byte gather takes two columns");
+// the same for float blocks (SPECK_SPMM_B32_FORCE_BLOCK: measurement builds only, profiles/blocks32.txt)
+#ifdef SPECK_SPMM_B32_FORCE_BLOCK
+constexpr u32 kCB32 = SPECK_SPMM_B32_FORCE_BLOCK;
+#else
+constexpr u32 kCB32 = SPECK_SPMM_COLUMN_BLOCK_B32;
+#endif
+static_assert(kCB32 % 4 == 0, "a 16-byte gather takes four columns");
 
 // tile_check_kernel's contract, then the product's own words
 struct SpmmTStatus {
@@ -52,19 +63,19 @@ struct SpmmTStatus {
     u32 a_base;   // A->row_offsets[0]
 };
 
-template <typename T>
+template <typename T, typename B = double>
 struct SpmmTArgs {
     const u32* t_ro;
     const u32* t_row;
     const u32* t_pos;
     const u32* col;  // A's, only compared
     const T* data;
-    const double* x;
+    const B* x;
     double* sums;  // cols k doubles: s(j,c) of the columns that lie whole in one tile
     u64 nnz, ldx;
     u32 k;          // >= 1
     u32 max_tiles;  // the records of column c start at recs + c max_tiles
-    u32 pairs;      // x starts on a 16-byte boundary and ldx is even
+    u32 pairs;      // x starts on a 16-byte boundary and ldx is even (B = float: the elements of the widest aligned load, 4, 2 or 1)
     TileRec* recs;
     const u32* tile_rows;
     SpmmTStatus* st;
@@ -88,24 +99,25 @@ __global__ __launch_bounds__(kThreads) void plan_match_kernel(const u32* __restr
 // and ids for the first time, so they and the X gathers are in flight together; nothing afterwards -- then per column the
 // terms and the segmented combine, with a barrier before the next column takes the LDS.  rows, a and in_mask are
 // references to the kernel's own variables: the first block's `between` is what fills them.
-template <u32 W, bool PAIR, typename T, typename Between>
-__device__ __forceinline__ void column_block(const SpmmTArgs<T>& g, TileLds& s_tile, const TileRows& rows, const double (&a)[kPer],
+template <u32 W, u32 VW, typename T, typename B, typename Between>
+__device__ __forceinline__ void column_block(const SpmmTArgs<T, B>& g, TileLds& s_tile, const TileRows& rows, const double (&a)[kPer],
                                              u32 (&row)[kPer], const u32& in_mask, const TileFrame& f, u32 c0, Between&& between)
 {
 #pragma clang fp contract(off)
-    static_assert(!PAIR || W % 2 == 0, "a 16-byte gather takes two columns");
+    static_assert(W % VW == 0 && VW * sizeof(B) <= 16, "whole loads of at most 16 bytes");
     // (the rows pass through an empty asm: the 16 addresses derived from them are computed per block, not kept)
 #pragma unroll
     for (u32 e = 0; e < kPer; ++e) asm volatile("" : "+v"(row[e]));
-    double xv[W][kPer];
+    B xv[W][kPer];
 #pragma unroll
     for (u32 e = 0; e < kPer; ++e) {
-        const double* src = g.x + (u64(row[e]) * g.ldx + c0);
-        if (PAIR) {
+        const B* src = g.x + (u64(row[e]) * g.ldx + c0);
+        if (VW > 1) {
 #pragma unroll
-            for (u32 j = 0; j < W; j += 2) {
-                const Vec<double, 2> p = reinterpret_cast<const Vec<double, 2>*>(src)[j / 2];
-                xv[j][e] = p.v[0], xv[j + 1][e] = p.v[1];
+            for (u32 j = 0; j < W; j += VW) {
+                const BlockVec<B, VW> p = reinterpret_cast<const BlockVec<B, VW>*>(src)[j / VW];
+#pragma unroll
+                for (u32 i = 0; i < VW; ++i) xv[j + i][e] = p.v[i];
             }
         } else {
 #pragma unroll
@@ -119,7 +131,7 @@ __device__ __forceinline__ void column_block(const SpmmTArgs<T>& g, TileLds& s_t
     for (u32 j = 0; j < W; ++j) {
         double v[kPer];
 #pragma unroll
-        for (u32 e = 0; e < kPer; ++e) v[e] = ((in_mask >> e) & 1u) ? a[e] * xv[j][e] : Sum::ident();
+        for (u32 e = 0; e < kPer; ++e) v[e] = ((in_mask >> e) & 1u) ? a[e] * (double)xv[j][e] : Sum::ident();
         const u32 cc = c0 + j;
         combine_terms<Sum>(s_tile, rows, v, g.t_ro, g.recs + (u64(cc) * g.max_tiles + blockIdx.x), f.tile0, f.lo, f.hi,
                            [sums, nk, cc](u32 r, double val) { sums[u64(r) * nk + cc] = val; });
@@ -127,8 +139,8 @@ __device__ __forceinline__ void column_block(const SpmmTArgs<T>& g, TileLds& s_t
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void spmm_t_tile_kernel(const SpmmTArgs<T> g)
+template <typename T, typename B>
+__global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void spmm_t_tile_kernel(const SpmmTArgs<T, B> g)
 {
     SPECK_POISON();
     __shared__ TileLds s_tile;
@@ -205,27 +217,51 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
     // carries first_use
     const u32 nk = g.k;
     u32 c0;
-    if (g.pairs && nk >= kCB) column_block<kCB, true>(g, s_tile, rows, a, row, in_mask, f, 0, first_use), c0 = kCB;
-    else if (g.pairs && nk >= 2) column_block<2, true>(g, s_tile, rows, a, row, in_mask, f, 0, first_use), c0 = 2;
-    else if (!g.pairs && nk >= kCB) column_block<kCB, false>(g, s_tile, rows, a, row, in_mask, f, 0, first_use), c0 = kCB;
-    else column_block<1, false>(g, s_tile, rows, a, row, in_mask, f, 0, first_use), c0 = 1;
-    if (g.pairs) {
-        for (; c0 + kCB <= nk; c0 += kCB) column_block<kCB, true>(g, s_tile, rows, a, row, in_mask, f, c0, nothing);
-        for (; c0 + 2 <= nk; c0 += 2) column_block<2, true>(g, s_tile, rows, a, row, in_mask, f, c0, nothing);
+    if constexpr (sizeof(B) == 8) {
+        if (g.pairs && nk >= kCB) column_block<kCB, 2>(g, s_tile, rows, a, row, in_mask, f, 0, first_use), c0 = kCB;
+        else if (g.pairs && nk >= 2) column_block<2, 2>(g, s_tile, rows, a, row, in_mask, f, 0, first_use), c0 = 2;
+        else if (!g.pairs && nk >= kCB) column_block<kCB, 1>(g, s_tile, rows, a, row, in_mask, f, 0, first_use), c0 = kCB;
+        else column_block<1, 1>(g, s_tile, rows, a, row, in_mask, f, 0, first_use), c0 = 1;
+        if (g.pairs) {
+            for (; c0 + kCB <= nk; c0 += kCB) column_block<kCB, 2>(g, s_tile, rows, a, row, in_mask, f, c0, nothing);
+            for (; c0 + 2 <= nk; c0 += 2) column_block<2, 2>(g, s_tile, rows, a, row, in_mask, f, c0, nothing);
+        } else {
+            for (; c0 + kCB <= nk; c0 += kCB) column_block<kCB, 1>(g, s_tile, rows, a, row, in_mask, f, c0, nothing);
+        }
     } else {
-        for (; c0 + kCB <= nk; c0 += kCB) column_block<kCB, false>(g, s_tile, rows, a, row, in_mask, f, c0, nothing);
+        // (c0 stays a multiple of the load's width: blocks of kCB32, then four, then two columns)
+        const u32 vw = g.pairs;
+        if (nk >= kCB32) {
+            if (vw == 4) column_block<kCB32, 4>(g, s_tile, rows, a, row, in_mask, f, 0, first_use);
+            else if (vw == 2) column_block<kCB32, 2>(g, s_tile, rows, a, row, in_mask, f, 0, first_use);
+            else column_block<kCB32, 1>(g, s_tile, rows, a, row, in_mask, f, 0, first_use);
+            c0 = kCB32;
+        } else if (vw >= 2 && nk >= 2) column_block<2, 2>(g, s_tile, rows, a, row, in_mask, f, 0, first_use), c0 = 2;
+        else column_block<1, 1>(g, s_tile, rows, a, row, in_mask, f, 0, first_use), c0 = 1;
+        if (vw == 4) {
+            for (; c0 + kCB32 <= nk; c0 += kCB32) column_block<kCB32, 4>(g, s_tile, rows, a, row, in_mask, f, c0, nothing);
+            if constexpr (kCB32 > 4)
+                for (; c0 % 4 == 0 && c0 + 4 <= nk; c0 += 4) column_block<4, 4>(g, s_tile, rows, a, row, in_mask, f, c0, nothing);
+        } else if (vw == 2) {
+            for (; c0 + kCB32 <= nk; c0 += kCB32) column_block<kCB32, 2>(g, s_tile, rows, a, row, in_mask, f, c0, nothing);
+        } else {
+            for (; c0 + kCB32 <= nk; c0 += kCB32) column_block<kCB32, 1>(g, s_tile, rows, a, row, in_mask, f, c0, nothing);
+        }
+        if (vw >= 2)
+            for (; c0 + 2 <= nk; c0 += 2) column_block<2, 2>(g, s_tile, rows, a, row, in_mask, f, c0, nothing);
     }
-    for (; c0 < nk; ++c0) column_block<1, false>(g, s_tile, rows, a, row, in_mask, f, c0, nothing);
+    for (; c0 < nk; ++c0) column_block<1, 1>(g, s_tile, rows, a, row, in_mask, f, c0, nothing);
 }
 
 // ------------------------------------------------------------------------------------------------ finish, and Y
 // spmm_finish_kernel over (t_ro, cols): a wave per (tile, column of Y) finishes the column of A that leaves the tile open;
 // a thread per (column of A, column of Y) writes one that lies in one tile (from `sums`) or holds no entry (+0.0); one
 // workgroup counts the split columns.  Every Y(j,c) is written once by one thread, which reads it itself where beta != 0.
+template <typename B>
 __global__ __launch_bounds__(kThreads) void spmm_t_finish_kernel(const u32* __restrict__ t_ro, u32 cols, u64 nnz, u32 k, u32 max_tiles,
                                                                  u32 chain_blocks, u32 row_blocks, const double* __restrict__ sums,
                                                                  const TileRec* __restrict__ recs, double alpha, double beta,
-                                                                 double* __restrict__ y, u64 ldy, SpmmTStatus* st)
+                                                                 B* __restrict__ y, u64 ldy, SpmmTStatus* st)
 {
     SPECK_POISON();
     __shared__ double s_w[kWaves];
@@ -259,9 +295,17 @@ __global__ __launch_bounds__(kThreads) void spmm_t_finish_kernel(const u32* __re
 }
 
 // ------------------------------------------------------------------------------------------------ host
-template <typename T>
-int spmm_t_run(TileScratch* sc, hipStream_t s, const speck_tplan* plan, double alpha, const speck_dcsr* A, const double* d_X, u64 ldx,
-               u32 k, double beta, double* d_Y, u64 ldy, SpmmTStatus* h)
+// the widest load every X(i, c) with c a multiple of its width is aligned to, as SpmmTArgs::pairs has it
+inline u32 gather_width(const double* d_X, u64 ldx) { return on_16_bytes(d_X) && ldx % 2 == 0 ? 1u : 0u; }
+inline u32 gather_width(const float* d_X, u64 ldx)
+{
+    const uintptr_t at = reinterpret_cast<uintptr_t>(d_X);
+    return at % 16 == 0 && ldx % 4 == 0 ? 4u : at % 8 == 0 && ldx % 2 == 0 ? 2u : 1u;
+}
+
+template <typename T, typename B>
+int spmm_t_run(TileScratch* sc, hipStream_t s, const speck_tplan* plan, double alpha, const speck_dcsr* A, const B* d_X, u64 ldx,
+               u32 k, double beta, B* d_Y, u64 ldy, SpmmTStatus* h)
 {
     const u32 rows = (u32)plan->rows, cols = (u32)plan->cols;
     // the plan's transposed structure as a matrix: what carve_and_check sizes the scratch for and checks
@@ -274,14 +318,14 @@ int spmm_t_run(TileScratch* sc, hipStream_t s, const speck_tplan* plan, double a
     if (rows) SPECK_LAUNCH(plan_match_kernel, dim3(rows / kThreads + 1u), dim3(kThreads), 0, s, A->row_offsets, plan->ro0, rows, w.st);
     const u32 ntiles = tiles_touched(0, plan->nnz);  // (the plan starts at 0: the tiles are known here)
     if (ntiles) {
-        const SpmmTArgs<T> g{plan->t_ro, plan->t_row, plan->t_pos, A->col_ids, static_cast<const T*>(A->data), d_X, w.sums, plan->nnz,
-                             ldx, k, w.max_tiles, on_16_bytes(d_X) && ldx % 2 == 0 ? 1u : 0u, w.recs, w.tile_rows, w.st};
-        SPECK_LAUNCH(spmm_t_tile_kernel<T>, dim3(ntiles), dim3(kThreads), 0, s, g);
+        const SpmmTArgs<T, B> g{plan->t_ro, plan->t_row, plan->t_pos, A->col_ids, static_cast<const T*>(A->data), d_X, w.sums, plan->nnz,
+                                ldx, k, w.max_tiles, gather_width(d_X, ldx), w.recs, w.tile_rows, w.st};
+        SPECK_LAUNCH((spmm_t_tile_kernel<T, B>), dim3(ntiles), dim3(kThreads), 0, s, g);
     }
     // (cols <= 2^27, k <= 2^10, tiles <= 2^20 + 1: the grid stays below 2^30)
     const u32 chain_blocks = (u32)((u64(w.max_tiles) * k + kWaves - 1) / kWaves);
     const u32 row_blocks = (u32)((u64(cols) * k + kThreads - 1) / kThreads);
-    SPECK_LAUNCH(spmm_t_finish_kernel, dim3(chain_blocks + row_blocks + 1u), dim3(kThreads), 0, s, plan->t_ro, cols, plan->nnz, k,
+    SPECK_LAUNCH(spmm_t_finish_kernel<B>, dim3(chain_blocks + row_blocks + 1u), dim3(kThreads), 0, s, plan->t_ro, cols, plan->nnz, k,
                  w.max_tiles, chain_blocks, row_blocks, w.sums, w.recs, alpha, beta, d_Y, ldy, w.st);
     // the ONE read-back of the call: the two verdicts, the counters
     rc = read_status(s, w.st, h);
@@ -291,9 +335,9 @@ int spmm_t_run(TileScratch* sc, hipStream_t s, const speck_tplan* plan, double a
 
 const char* const kGuardNames[3] = {"spmm_t status", "spmm_t tile records and columns", "spmm_t column sums"};
 
-template <typename T>
-int spmm_t_impl(speck_config* cfg, const speck_tplan* plan, double alpha, const speck_dcsr* A, const double* d_X, u64 ldx, u32 k,
-                double beta, double* d_Y, u64 ldy, speck_spmm_t_info* info)
+template <typename T, typename B>
+int spmm_t_impl(speck_config* cfg, const speck_tplan* plan, double alpha, const speck_dcsr* A, const B* d_X, u64 ldx, u32 k,
+                double beta, B* d_Y, u64 ldy, speck_spmm_t_info* info)
 {
     if (!plan || !A || alpha != alpha || beta != beta) return SPECK_ERR_INVALID;
     if (A->rows > (1ull << 27) || A->cols > (1ull << 27) || k > SPECK_SPMM_MAX_RHS) return SPECK_ERR_DIM_LIMIT;
@@ -309,7 +353,7 @@ int spmm_t_impl(speck_config* cfg, const speck_tplan* plan, double alpha, const 
     if (d_X && d_Y && A->rows && A->cols && k) {
         // what the call may touch: [d_X, d_X + (rows - 1) ldx + k) and [d_Y, d_Y + (cols - 1) ldy + k), padding inside included
         const u64 x0 = reinterpret_cast<uintptr_t>(d_X), y0 = reinterpret_cast<uintptr_t>(d_Y);
-        const u64 xs = 8 * ((A->rows - 1) * ldx + k), ys = 8 * ((A->cols - 1) * ldy + k);
+        const u64 xs = sizeof(B) * ((A->rows - 1) * ldx + k), ys = sizeof(B) * ((A->cols - 1) * ldy + k);
         if (x0 < y0 + ys && y0 < x0 + xs) return SPECK_ERR_INVALID;
     }
     if (info) *info = speck_spmm_t_info{};
@@ -317,7 +361,7 @@ int spmm_t_impl(speck_config* cfg, const speck_tplan* plan, double alpha, const 
     if (A->cols == 0 || k == 0) return SPECK_OK;  // no row or no column of Y: nothing to write
     SpmmTStatus h{};
     const int rc = run_tile_call(cfg, spmm_t_scratch, kGuardNames, 3, " by the transposed product", [&](TileScratch* sc, hipStream_t s) {
-        return spmm_t_run<T>(sc, s, plan, alpha, A, d_X, ldx, k, beta, d_Y, ldy, &h);
+        return spmm_t_run<T, B>(sc, s, plan, alpha, A, d_X, ldx, k, beta, d_Y, ldy, &h);
     });
     if (rc != SPECK_OK) return rc;
     if (info) {
@@ -342,6 +386,18 @@ int speck_spmm_t_f64(speck_config* cfg, const speck_tplan* plan, double alpha, c
 
 int speck_spmm_t_f32(speck_config* cfg, const speck_tplan* plan, double alpha, const speck_dcsr* A, const double* d_X, uint64_t ldx,
                      uint32_t k, double beta, double* d_Y, uint64_t ldy, speck_spmm_t_info* info)
+{
+    return spmm_t_impl<float>(cfg, plan, alpha, A, d_X, ldx, k, beta, d_Y, ldy, info);
+}
+
+int speck_spmm_t_f64_b32(speck_config* cfg, const speck_tplan* plan, double alpha, const speck_dcsr* A, const float* d_X, uint64_t ldx,
+                         uint32_t k, double beta, float* d_Y, uint64_t ldy, speck_spmm_t_info* info)
+{
+    return spmm_t_impl<double>(cfg, plan, alpha, A, d_X, ldx, k, beta, d_Y, ldy, info);
+}
+
+int speck_spmm_t_f32_b32(speck_config* cfg, const speck_tplan* plan, double alpha, const speck_dcsr* A, const float* d_X, uint64_t ldx,
+                         uint32_t k, double beta, float* d_Y, uint64_t ldy, speck_spmm_t_info* info)
 {
     return spmm_t_impl<float>(cfg, plan, alpha, A, d_X, ldx, k, beta, d_Y, ldy, info);
 }

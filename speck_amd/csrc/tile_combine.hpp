@@ -360,17 +360,26 @@ __device__ __forceinline__ bool totals_finish(const TileRec* __restrict__ recs, 
     return true;
 }
 
-// y[at] = alpha s + beta y[at], each product and the sum rounded on its own; the one write of a result of spmv.hip and spmm.hip
-__device__ __forceinline__ void write_y(double* __restrict__ y, u64 at, double s, double alpha, double beta)
+// y[at] = alpha s + beta y[at], each product and the sum rounded on its own; the one write of a result of spmv.hip, spmm.hip
+// and spmm_t.hip.  Y: double, or float for the float blocks of the two products -- what y holds is widened where it is
+// read, and the result is rounded to Y ONCE, at the store.
+template <typename Y>
+__device__ __forceinline__ void write_y(Y* __restrict__ y, u64 at, double s, double alpha, double beta)
 {
 #pragma clang fp contract(off)
     const double as = alpha * s;
-    if (beta == 0.0) y[at] = as;  // (y is not read: what it held does not survive)
+    if (beta == 0.0) y[at] = (Y)as;  // (y is not read: what it held does not survive)
     else {
-        const double by = beta * y[at];
-        y[at] = as + by;
+        const double by = beta * (double)y[at];
+        y[at] = (Y)(as + by);
     }
 }
+
+// N elements of a dense block in one load of N sizeof(V) bytes: 16 for two doubles or four floats, 8 for two floats
+template <typename V, u32 N>
+struct alignas(N * sizeof(V)) BlockVec {
+    V v[N];
+};
 #endif  // __HIPCC__
 
 }  // namespace tile_combine
