@@ -29,13 +29,51 @@ constexpr u32 num_esc_group_lds()
     return 4u * L * (u32)sizeof(Acc<T>) + L * (4u + (u32)sizeof(Acc<T>));
 }
 
+// A row's entries of A as its lanes hold them: lane `gl` of the group has entry a0 + gl -- the (start, length) of the B row
+// it references and a_ik; zeros in a lane beyond the row's end (and in every lane when the row is not `there`: nothing is
+// read for it).  REQUESTED here, USED by the row functions (num_esc_row / num_escw_row and the symbolic bodies): a group
+// that walks a class list requests the entries of its NEXT row in front of the current row's work, so that they travel
+// beside its B gathers (num_esc_body); a caller with one row per group requests and uses back to back.
+template <typename T>
+struct EscEntry {
+    uint2 sl;
+    T av;
+};
+template <typename T>
+__device__ __forceinline__ uint2 esc_request_sl(const ProductSrc<T>& src, u32 a0, u32 a1, u32 gl, bool there = true)
+{
+    uint2 sl = make_uint2(0u, 0u);
+    if (there && a0 + gl < a1) sl = src.b_sl[a0 + gl];
+    return sl;
+}
+template <typename T>
+__device__ __forceinline__ EscEntry<T> esc_request(const ProductSrc<T>& src, u32 a0, u32 a1, u32 gl, bool there = true)
+{
+    EscEntry<T> e{make_uint2(0u, 0u), T(0)};
+    if (there && a0 + gl < a1) {
+        e.sl = src.b_sl[a0 + gl];
+        e.av = src.a_val[a0 + gl];
+    }
+    return e;
+}
+// The wait for requested entries HERE, not at their first use.  In front of a walk's loop: the compiler places its waits
+// per loop, not per iteration -- entries still in flight on the way INTO the loop make it wait at the top of EVERY row,
+// for all that is in flight there (the previous row's stores, the prefetch just issued).
+__device__ __forceinline__ void esc_settle(uint2& sl) { asm volatile("" : "+v"(sl.x), "+v"(sl.y)); }
+template <typename T>
+__device__ __forceinline__ void esc_settle(EscEntry<T>& e)
+{
+    asm volatile("" : "+v"(e.sl.x), "+v"(e.sl.y), "+v"(e.av));
+}
+
 // One row of the class by its lane group: expand / sort / compress, the finished row (ascending columns, one entry per
 // distinct column) to out_col / out_val[0 .. nnz) -- if nnz <= room (else nothing is stored).  Returns the row's nnz.
-// `mine`: the group's num_esc_group_lds<T, L>() bytes of LDS.  An idle group passes a0 == a1 (nothing is read or stored);
-// every lane of the wave must call (wave-wide ballots and fences inside).
+// `mine`: the group's num_esc_group_lds<T, L>() bytes of LDS.  `mine_a`: the lane's entry of the row (esc_request; all zero
+// in an idle group: nothing is read or stored); every lane of the wave must call (wave-wide ballots and fences inside).
 template <typename T, u32 L>
-__device__ __forceinline__ u32 num_esc_row(const SubWave<L>& g, unsigned char* mine, const ProductSrc<T>& src, u32 a0, u32 a1,
-                                           u32* __restrict__ out_col, T* __restrict__ out_val, u32 room)
+__device__ __forceinline__ u32 num_esc_row(const SubWave<L>& g, unsigned char* mine, const ProductSrc<T>& src,
+                                           const EscEntry<T>& mine_a, u32* __restrict__ out_col, T* __restrict__ out_val,
+                                           u32 room)
 {
     static_assert(L == 8 || L == 16, "8 or 16 lanes per row");
     using Mask = typename std::conditional<L <= 8, u32, u64>::type;
@@ -45,13 +83,8 @@ __device__ __forceinline__ u32 num_esc_row(const SubWave<L>& g, unsigned char* m
     u32* s_off = reinterpret_cast<u32*>(s_av + L);        // [L]   its B-row start minus its first product number
     const u32 gl = g.lane;
     // ---- expand: my entry of A, where its products end
-    const bool have = a0 + gl < a1;
-    uint2 sl = make_uint2(0u, 0u);
-    Acc<T> av = 0;
-    if (have) {
-        sl = src.b_sl[a0 + gl];
-        av = (Acc<T>)src.a_val[a0 + gl];
-    }
+    const uint2 sl = mine_a.sl;
+    const Acc<T> av = (Acc<T>)mine_a.av;
     u32 total;
     const u32 incl = g.inclusive_scan(sl.y, &total, nullptr);
     const bool nonempty = sl.y != 0;
@@ -177,6 +210,13 @@ __device__ __forceinline__ u32 num_esc_row(const SubWave<L>& g, unsigned char* m
     wave_lds_fence();  // the next row overwrites the staging and the products
     return all;
 }
+// ... requested and used back to back: the row [a0, a1) of A (an idle group passes a0 == a1)
+template <typename T, u32 L>
+__device__ __forceinline__ u32 num_esc_row(const SubWave<L>& g, unsigned char* mine, const ProductSrc<T>& src, u32 a0, u32 a1,
+                                           u32* __restrict__ out_col, T* __restrict__ out_val, u32 room)
+{
+    return num_esc_row<T, L>(g, mine, src, esc_request(src, a0, a1, g.lane), out_col, out_val, room);
+}
 
 // FUSED (replayed sequence, symbolic phase): `cls` is the SYMBOLIC class whose list is walked; the row's nnz goes
 // to `counts`, the row itself to C at w.nf_pred_off[row] -- the offset the previous identical call gave it -- if its
@@ -195,15 +235,32 @@ __device__ __forceinline__ void num_esc_body(unsigned char* smem, const ProductS
     RowCursor cur = open_list<FUSED>(w, cls, hint, bidx, nblk, NG, gid, (w.xcd_aware & 8u) != 0);
     // (a replayed sequence that an earlier kernel has declared void walks nothing)
     if (wave_void(cur.miss)) return;
-    while (cur.more()) {
-        const RowRec rec = cur.take();  // (its successor's record is requested now: RowCursor)
-        u32 place = rec.base, room = 0xFFFFFFFFu;
-        if constexpr (FUSED) {
-            place = w.nf_pred_off[rec.row];
-            room = w.nf_pred_off[rec.row + 1] - place;
+    if constexpr (!FUSED) {
+        // The walk of a complete call, two rows deep.  In front of a row's work the group holds the row's entries of A and the
+        // record of its successor, both arrived; it requests the successor's entries and the record after that, and then
+        // expands the row: those requests travel beside the row's B gathers -- the one wait of the row (the gathers are
+        // predicated, so the compiler waits for all that is in flight: a request placed BEHIND them would be waited for as
+        // well, one placed in front costs that wait nothing) -- and the next row starts from registers.  Nothing is read for
+        // a row that is not there (no successor: `succ`) or for a lane beyond its end (esc_request).
+        bool have = cur.more();
+        RowRec rec = cur.take();  // (its successor's record is requested now: RowCursor)
+        EscEntry<T> ea = esc_request(src, rec.a0, rec.a1, g.lane, have);
+        esc_settle(ea);
+        while (have) {
+            const bool succ = cur.more();
+            const EscEntry<T> en = esc_request(src, cur.next.a0, cur.next.a1, g.lane, succ);
+            const RowRec nrec = cur.take();
+            num_esc_row<T, L>(g, mine, src, ea, c_col + rec.base, c_val + rec.base, 0xFFFFFFFFu);
+            ea = en;
+            rec = nrec;
+            have = succ;
         }
-        const u32 all = num_esc_row<T, L>(g, mine, src, rec.a0, rec.a1, c_col + place, c_val + place, room);
-        if constexpr (FUSED) {
+    } else {
+        while (cur.more()) {
+            const RowRec rec = cur.take();  // (its successor's record is requested now: RowCursor)
+            const u32 place = w.nf_pred_off[rec.row];
+            const u32 room = w.nf_pred_off[rec.row + 1] - place;
+            const u32 all = num_esc_row<T, L>(g, mine, src, rec.a0, rec.a1, c_col + place, c_val + place, room);
             if (g.lane == 0) {
                 counts[rec.row] = all;
                 if (all != room) const_cast<DeviceStats*>(w.st)->capacity_miss = 1;

@@ -178,8 +178,9 @@ constexpr u32 sym_escw_group_lds()
 // One row by its lane group (see num_esc_row): `cmin` = the first column the row can reach (the sort key holds the
 // column relative to it).  Returns the row's nnz; the row is stored if nnz <= room.
 template <typename T, u32 L>
-__device__ __forceinline__ u32 num_escw_row(const SubWave<L>& g, unsigned char* mine, const ProductSrc<T>& src, u32 a0, u32 a1,
-                                            u32 cmin, u32* __restrict__ out_col, T* __restrict__ out_val, u32 room)
+__device__ __forceinline__ u32 num_escw_row(const SubWave<L>& g, unsigned char* mine, const ProductSrc<T>& src,
+                                            const EscEntry<T>& mine_a, u32 cmin, u32* __restrict__ out_col,
+                                            T* __restrict__ out_val, u32 room)
 {
     static_assert(L == 32 || L == 64, "32 or 64 lanes per row");
     constexpr u32 PER = kEscPerLane, NP = PER * L, TAG = L == 32 ? 7u : 8u;
@@ -191,13 +192,8 @@ __device__ __forceinline__ u32 num_escw_row(const SubWave<L>& g, unsigned char* 
     const EscEnds<L> ends{reinterpret_cast<uint2*>(s_off + L)};
     const u32 gl = g.lane;
     // ---- expand: my entry of A, where its products end
-    const bool have = a0 + gl < a1;
-    uint2 sl = make_uint2(0u, 0u);
-    Acc<T> av = 0;
-    if (have) {
-        sl = src.b_sl[a0 + gl];
-        av = (Acc<T>)src.a_val[a0 + gl];
-    }
+    const uint2 sl = mine_a.sl;
+    const Acc<T> av = (Acc<T>)mine_a.av;
     u32 total;
     const u32 incl = g.inclusive_scan(sl.y, &total, nullptr);
     const bool nonempty = sl.y != 0;
@@ -322,6 +318,13 @@ __device__ __forceinline__ u32 num_escw_row(const SubWave<L>& g, unsigned char* 
     wave_lds_fence();  // the next row overwrites the staging and the products
     return all;
 }
+// ... requested and used back to back: the row [a0, a1) of A (an idle group passes a0 == a1)
+template <typename T, u32 L>
+__device__ __forceinline__ u32 num_escw_row(const SubWave<L>& g, unsigned char* mine, const ProductSrc<T>& src, u32 a0, u32 a1,
+                                            u32 cmin, u32* __restrict__ out_col, T* __restrict__ out_val, u32 room)
+{
+    return num_escw_row<T, L>(g, mine, src, esc_request(src, a0, a1, g.lane), cmin, out_col, out_val, room);
+}
 
 template <typename T, u32 L, int THREADS, bool FUSED = false>
 __device__ __forceinline__ void num_escw_body(unsigned char* smem, const ProductSrc<T>& src, const RowWork& w,
@@ -336,15 +339,27 @@ __device__ __forceinline__ void num_escw_body(unsigned char* smem, const Product
     RowCursor cur = open_list<FUSED>(w, cls, hint, bidx, nblk, NG, gid, (w.xcd_aware & 8u) != 0);
     // (a replayed sequence that an earlier kernel has declared void walks nothing)
     if (wave_void(cur.miss)) return;
-    while (cur.more()) {
-        const RowRec rec = cur.take();  // (its successor's record is requested now: RowCursor)
-        u32 place = rec.base, room = 0xFFFFFFFFu;
-        if constexpr (FUSED) {
-            place = w.nf_pred_off[rec.row];
-            room = w.nf_pred_off[rec.row + 1] - place;
+    if constexpr (!FUSED) {
+        // (two rows deep, as num_esc_body: the successor's entries of A and the record after it travel beside the row's gathers)
+        bool have = cur.more();
+        RowRec rec = cur.take();  // (its successor's record is requested now: RowCursor)
+        EscEntry<T> ea = esc_request(src, rec.a0, rec.a1, g.lane, have);
+        esc_settle(ea);
+        while (have) {
+            const bool succ = cur.more();
+            const EscEntry<T> en = esc_request(src, cur.next.a0, cur.next.a1, g.lane, succ);
+            const RowRec nrec = cur.take();
+            num_escw_row<T, L>(g, mine, src, ea, rec.cmin, c_col + rec.base, c_val + rec.base, 0xFFFFFFFFu);
+            ea = en;
+            rec = nrec;
+            have = succ;
         }
-        const u32 all = num_escw_row<T, L>(g, mine, src, rec.a0, rec.a1, rec.cmin, c_col + place, c_val + place, room);
-        if constexpr (FUSED) {
+    } else {
+        while (cur.more()) {
+            const RowRec rec = cur.take();  // (its successor's record is requested now: RowCursor)
+            const u32 place = w.nf_pred_off[rec.row];
+            const u32 room = w.nf_pred_off[rec.row + 1] - place;
+            const u32 all = num_escw_row<T, L>(g, mine, src, rec.a0, rec.a1, rec.cmin, c_col + place, c_val + place, room);
             if (g.lane == 0) {
                 counts[rec.row] = all;
                 if (all != room) const_cast<DeviceStats*>(w.st)->capacity_miss = 1;
@@ -371,10 +386,15 @@ __device__ __forceinline__ void sym_escw_body(unsigned char* smem, const Product
     // (a replayed sequence that an earlier kernel has declared void walks nothing)
     if (wave_void(cur.miss)) return;
     const u32 gl = g.lane;
-    while (cur.more()) {
-        const RowRec rec = cur.take();  // (its successor's record is requested now: RowCursor)
-        uint2 sl = make_uint2(0u, 0u);
-        if (rec.a0 + gl < rec.a1) sl = src.b_sl[rec.a0 + gl];
+    // (two rows deep, as num_esc_body: the successor's entries of A and the record after it travel beside the row's gathers)
+    bool have = cur.more();
+    RowRec rec = cur.take();  // (its successor's record is requested now: RowCursor)
+    uint2 sl = esc_request_sl(src, rec.a0, rec.a1, gl, have);
+    esc_settle(sl);
+    while (have) {
+        const bool succ = cur.more();
+        const uint2 sn = esc_request_sl(src, cur.next.a0, cur.next.a1, gl, succ);
+        const RowRec nrec = cur.take();
         u32 total;
         const u32 incl = g.inclusive_scan(sl.y, &total, nullptr);
         const bool nonempty = sl.y != 0;
@@ -399,6 +419,9 @@ __device__ __forceinline__ void sym_escw_body(unsigned char* smem, const Product
         heads = g.reduce_add(heads, nullptr);
         if (gl == 0) store_row_count(w, counts, rec.row, heads);
         wave_lds_fence();  // the next row overwrites the offsets
+        sl = sn;
+        rec = nrec;
+        have = succ;
     }
 }
 

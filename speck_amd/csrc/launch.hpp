@@ -371,6 +371,37 @@ bool plan_light(const ClassSlot (&tab)[N], u32 mask, const u32* counts_hint, boo
 }
 // resident-set multiples a class grid may reach before its workgroups start striding over rows
 void set_grid_rounds(u32 block_classes, u32 subwave_classes);
+// Register classes of a merged launch of a complete call (option esc_walk_rows, R): their lane groups walk their lists two
+// rows deep (esc_rows.hpp), which pays only for a group with several rows.  The block range of such a class grows one row
+// per group, as planned by plan_light, while the launch's workgroups all fit the chip at once; from there on the register
+// classes share the resident set in proportion to their needs and keep that many workgroups until their groups hold R rows;
+// beyond that the range grows again, R rows per group.  R = 1: the ranges of plan_light.  `resident`: the workgroups of the
+// launch the chip holds at once (light_resident); the other classes' workgroups are taken off it, up to half.
+void set_esc_walk(u32 rows, int64_t resident_override);  // (override: < 0 keeps it, 0 = ask the runtime, else a debug value)
+u32 esc_walk_rows();
+template <size_t N>
+void stretch_walks(const ClassSlot (&tab)[N], u32 esc_mask, u32 resident, ClassGrid* cg)
+{
+    const u32 R = esc_walk_rows();
+    u64 esc = 0;
+    for (size_t k = 0; k < N; ++k)
+        if (esc_mask >> tab[k].cls & 1u) esc += cg->first[k + 1] - cg->first[k];
+    const u64 others = cg->first[N + 1] - esc;
+    const u64 room = resident - (others < resident / 2 ? others : resident / 2);
+    if (R <= 1 || esc <= room) return;
+    u32 need[N + 1];
+    for (size_t k = 0; k <= N; ++k) need[k] = cg->first[k + 1] - cg->first[k];
+    for (size_t k = 0; k < N; ++k) {
+        if (!(esc_mask >> tab[k].cls & 1u) || !need[k]) continue;
+        const u64 share = room * need[k] / esc, by_rows = (u64(need[k]) + R - 1) / R;
+        const u64 blocks = share > by_rows ? share : by_rows;  // (<= need: esc > room, R >= 1)
+        need[k] = blocks ? (u32)blocks : 1u;
+    }
+    for (size_t k = 0; k <= N; ++k) cg->first[k + 1] = cg->first[k] + need[k];
+}
+// Workgroups of `kernel` (256 threads, `lds` bytes of dynamic LDS) the chip holds at once: what the runtime says of the very
+// kernel (its registers bound the numeric launch, its LDS the symbolic one), asked once per kernel and LDS size.
+u32 light_resident(const void* kernel, u32 lds, int cu_count);
 void set_b8k_full_first(u32 mask);  // NUM_B8K: the full-table launch in front of the half-table one (bit 0 complete calls, bit 1 reuse)
 void set_scan_small_items(int items);
 void set_spill_big_grid(u32 blocks);  // workgroups of the NUM_G launch that reduces the oversized buckets

@@ -1896,6 +1896,12 @@ void launch_numeric_light(hipStream_t s, const u32* counts_hint, u32 mask, const
     bool with_esc = false;  // (a class of the mask without rows has no blocks: its body is never entered)
     for (size_t k = 0; k < NS; ++k)
         if ((kNumEscMask >> kNumLight[k].cls & 1u) && cg.first[k + 1] != cg.first[k]) with_esc = true;
+    // (the register classes' ranges once the chip is full: stretch_walks)
+    if (with_esc && !w.verify_numeric && esc_walk_rows() > 1) {
+        const void* k = tiny_only ? reinterpret_cast<const void*>(num_tiny_kernel<T>)
+                                  : reinterpret_cast<const void*>(num_light_kernel<T, true>);
+        stretch_walks(kNumLight, kNumEscMask, light_resident(k, lds, cu_count), &cg);
+    }
     if (w.verify_numeric)  // (pipeline.hip plans such a sequence only when this launch has workgroup / wave classes and no
                            //  register-class rows of its own)
         SPECK_LAUNCH_TIMED((num_light_kernel<T, false, true>), dim3(cg.first[NS + 1]), dim3(256), lds, s, e0, e1, src,

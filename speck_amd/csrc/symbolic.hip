@@ -88,10 +88,15 @@ __device__ __forceinline__ void sym_esc_body(unsigned char* smem, const ProductS
     // (a replayed sequence that an earlier kernel has declared void walks nothing)
     if (wave_void(cur.miss)) return;
     const u32 gl = g.lane;
-    while (cur.more()) {
-        const RowRec rec = cur.take();  // (its successor's record is requested now: RowCursor)
-        uint2 sl = make_uint2(0u, 0u);
-        if (rec.a0 + gl < rec.a1) sl = src.b_sl[rec.a0 + gl];
+    // (two rows deep, as num_esc_body: the successor's entries of A and the record after it travel beside the row's gathers)
+    bool have = cur.more();
+    RowRec rec = cur.take();  // (its successor's record is requested now: RowCursor)
+    uint2 sl = esc_request_sl(src, rec.a0, rec.a1, gl, have);
+    esc_settle(sl);
+    while (have) {
+        const bool succ = cur.more();
+        const uint2 sn = esc_request_sl(src, cur.next.a0, cur.next.a1, gl, succ);
+        const RowRec nrec = cur.take();
         u32 total;
         const u32 incl = g.inclusive_scan(sl.y, &total, nullptr);
         const bool nonempty = sl.y != 0;
@@ -123,6 +128,9 @@ __device__ __forceinline__ void sym_esc_body(unsigned char* smem, const ProductS
         heads = g.reduce_add(heads, nullptr);
         if (gl == 0) store_row_count(w, counts, rec.row, heads);
         wave_lds_fence();  // the next row overwrites the offsets
+        sl = sn;
+        rec = nrec;
+        have = succ;
     }
 }
 
@@ -395,6 +403,35 @@ void set_grid_rounds(u32 block_classes, u32 subwave_classes)
     if (subwave_classes) g_grid_rounds_sub = subwave_classes;
 }
 
+static u32 g_esc_walk_rows = 4, g_esc_walk_resident = 0;
+void set_esc_walk(u32 rows, int64_t resident_override)
+{
+    if (rows) g_esc_walk_rows = rows;
+    if (resident_override >= 0) g_esc_walk_resident = (u32)resident_override;
+}
+u32 esc_walk_rows() { return g_esc_walk_rows; }
+
+u32 light_resident(const void* kernel, u32 lds, int cu_count)
+{
+    if (g_esc_walk_resident) return g_esc_walk_resident;
+    struct Known {
+        const void* kernel;
+        u32 lds, per_cu;
+    };
+    thread_local Known known[8];
+    thread_local u32 n_known = 0;
+    for (u32 i = 0; i < n_known; ++i)
+        if (known[i].kernel == kernel && known[i].lds == lds) return known[i].per_cu * (u32)cu_count;
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, lds) != hipSuccess || per_cu < 1) {
+        (void)hipGetLastError();
+        per_cu = lds ? (int)std::min<u32>(160u * 1024u / lds, 8u) : 8;  // (by LDS and threads alone: grid_for)
+        if (per_cu < 1) per_cu = 1;
+    }
+    if (n_known < 8) known[n_known++] = Known{kernel, lds, (u32)per_cu};
+    return (u32)per_cu * (u32)cu_count;
+}
+
 u32 grid_for(u32 count, u32 lds, int threads, int cu_count, u32 rows_per_block)
 {
     u32 per_cu = lds ? (160u * 1024u) / lds : 8;
@@ -451,6 +488,8 @@ void launch_symbolic_light(hipStream_t s, const u32* counts_hint, u32 mask, cons
         return;
     }
     const ProductSrc<float> src{b_sl, nullptr, b_col, nullptr, w.w_sl};
+    if (esc_walk_rows() > 1)  // (the register classes' ranges once the chip is full)
+        stretch_walks(kSymLight, kSymEscMask, light_resident(reinterpret_cast<const void*>(sym_light_kernel), lds, cu_count), &cg);
     SPECK_LAUNCH_TIMED(sym_light_kernel, dim3(cg.first[NS]), dim3(256), lds, s, e0, e1, src, a_ro, w, counts, cg);
 }
 
