@@ -223,7 +223,9 @@ int speck_compare_f32(speck_config *cfg, const speck_dcsr *ref, const speck_dcsr
 int speck_compare_bounded_f64(speck_config *cfg, const speck_dcsr *ref, const speck_dcsr *cmp,
                               const speck_dcsr *abs_products, double tol, uint64_t *h_structure_rows,
                               uint64_t *h_value_rows);
-/* Order-preserving transpose (source/GPU/Transpose.cu:10-117; DataLoader.cpp:65-69 for rows!=cols). */
+/* Order-preserving transpose (source/GPU/Transpose.cu:10-117; DataLoader.cpp:65-69 for rows!=cols).
+ * nnz > 2^32 - 64: SPECK_ERR_NNZ_OVERFLOW before anything is allocated (the kernel that expands the rows counts a row's
+ * entries in 32 bits, a wave of 64 at a time: a row that ends within one step of 2^32 would send the counter round). */
 int speck_transpose_f64(speck_config *cfg, const speck_dcsr *A, speck_dcsr *At);
 /* ... and its float instantiation (source/GPU/Transpose.cu:116) */
 int speck_transpose_f32(speck_config *cfg, const speck_dcsr *A, speck_dcsr *At);
@@ -822,7 +824,7 @@ int speck_softmax_f32(speck_config *cfg, const speck_dcsr *A, const speck_softma
  *  Unlike speck_transpose_* the creation CHECKS its input before it sorts or follows anything: offsets that descend or leave
  *      [row_offsets[0], row_offsets[0] + nnz], a last offset that is not row_offsets[0] + nnz, a column id >= cols, NULL
  *      buffers with nnz > 0: SPECK_ERR_INVALID, *out untouched, nothing left allocated.  Rows need not be sorted.  rows or
- *      cols > 2^27: SPECK_ERR_DIM_LIMIT; nnz >= 2^32: SPECK_ERR_NNZ_OVERFLOW; a failed allocation: SPECK_ERR_OOM, nothing
+ *      cols > 2^27: SPECK_ERR_DIM_LIMIT; nnz > 2^32 - 64 (as speck_transpose_*): SPECK_ERR_NNZ_OVERFLOW; a failed allocation: SPECK_ERR_OOM, nothing
  *      leaked.  nnz == 0 and rows == 0 give valid plans.  Like speck_transpose_* the creation works on the NULL stream and
  *      returns complete; cfg may be NULL.  After the creation a plan is only ever read: several calls, streams and configs
  *      may use one.  speck_tplan_destroy(NULL) is SPECK_OK.
@@ -958,6 +960,11 @@ int speck_sddmm_f32_b32(speck_config *cfg, const speck_dcsr *A, const speck_sddm
  *      does not span nnz (as everywhere); where d_col_out is given, a column id >= cols; an output inside one of A's
  *      buffers or the two outputs overlapping; row_base + rows exceeding 2^32 (index_bytes 4) or 2^63 (8); index_bytes
  *      not 4 or 8; NULL d_row_out: SPECK_ERR_INVALID.  The limits are speck_from_coo_*'s.  rows == 0: SPECK_OK.
+ *      "Inside A->data": this one function does not know A's value type, so it refuses an output that touches the bytes
+ *      from 4 row_offsets[0] to 8 (row_offsets[0] + nnz) behind A->data, the entries as floats and as doubles.  With FLOAT
+ *      values that span reaches 4 (row_offsets[0] + nnz) bytes behind the last value -- up to 16 GiB for a view that ends
+ *      near 2^32 -- and an output that lies there is refused although it touches nothing of A: keep the outputs clear of
+ *      it (tests/test_gpu_high_offsets_side.py does).  Telling the two apart needs the value type in the call.
  *  The checking kernel takes a thread per row and, for the ids, one streaming pass over the entries; the writing kernel
  *      is queued behind it and does nothing where the verdict is raised: a wave takes 64 rows at a time, a lane each, a
  *      row longer than 16 entries takes the whole wave, lanes striding its entries; the columns are widened in a streaming
@@ -1084,8 +1091,8 @@ int speck_extract_f32(speck_config *cfg, const speck_dcsr *A, const speck_extrac
  *  SPECK_ERR_INVALID with NOTHING written -- not C's struct, not its allocations, not the contents of buffers it would reuse:
  *      offsets that descend, leave [row_offsets[0], row_offsets[0] + nnz] or whose last one does not span nnz; a column id >=
  *      A->cols ANYWHERE in A (C must be a sound matrix); mode not one of the three; reserved != 0; NULL A, p or C; NULL
- *      buffers with a count > 0; C sharing a buffer with A.  A->rows or A->cols > 2^27: SPECK_ERR_DIM_LIMIT.  A->nnz >= 2^32:
- *      SPECK_ERR_NNZ_OVERFLOW.  No offset is used as an address before it has been checked.
+ *      buffers with a count > 0; C sharing a buffer with A.  A->rows or A->cols > 2^27: SPECK_ERR_DIM_LIMIT.  A->nnz > 2^32 -
+ *      1024: SPECK_ERR_NNZ_OVERFLOW (the copy of the rows kept whole numbers a tile's entries in 32 bits, 1024 a step).  No offset is used as an address before it has been checked.
  *  CHECK AND CLASSIFY: one pass over row_offsets and col_ids; min(len, k) per row, which the shared scan turns into C's
  *      offsets -- they depend on the lengths alone: there is no marking pass and no keep byte; the rows longer than k go to
  *      lists by length.  ONE read-back (the verdict, nnz(C), the lists) before C is allocated; every kernel that writes C
@@ -1165,8 +1172,9 @@ int speck_topk_f32(speck_config *cfg, const speck_dcsr *A, const speck_topk_para
  *      seed; the ids of rows nobody gathers are NEVER READ, so a matrix with a bad id in a row nobody asks for is served; an
  *      unknown mode; index_bytes not 4 or 8; a NULL index with n_rows != A->rows; row_base > 2^62; the index overlapping a
  *      buffer of A or C; C sharing a buffer with A; NULL A, p or C; NULL buffers with a count > 0.  A->rows, A->cols or
- *      n_rows > 2^27: SPECK_ERR_DIM_LIMIT.  A->nnz >= 2^32, an output of 2^32 entries or more (mode 1 reaches that easily:
- *      k times the non-empty gathered rows) or gathered rows of 2^32 entries or more (as speck_extract_*):
+ *      n_rows > 2^27: SPECK_ERR_DIM_LIMIT.  A->nnz > 2^32 - 1024, an output of 2^32 entries or more (mode 1 reaches that easily:
+ *      k times the non-empty gathered rows) or gathered rows of more than 2^32 - 1024 entries (the copy of the rows kept
+ *      whole numbers a tile's entries in 32 bits, 1024 a step):
  *      SPECK_ERR_NNZ_OVERFLOW, decided from 64-bit sums in the first pass before any 32-bit offset exists.
  *  CHECK: a thread per row of A and per index -- the offsets, the indices, the gathered length (0 where unsound: clamped,
  *      never followed), the output length min(len, k) or (len ? k : 0), the 64-bit sums of both and, for mode 0, the rows

@@ -74,6 +74,10 @@ __global__ void compare_kernel(const u32* __restrict__ ro_a, const u32* __restri
     }
 }
 
+// Its walk over a row counts entries from the matrix's first one in 32 bits and steps by a wave: a row that ends within
+// one step of 2^32 would send the counter round.  speck_transpose_* and speck_tplan_create refuse such a matrix on the host.
+constexpr u64 kExpandRowsNnzMax = (1ull << 32) - 64;
+
 __global__ void expand_rows_kernel(const u32* __restrict__ ro, u32 rows, u32 base,
                                    u32* __restrict__ row_of)
 {
@@ -298,6 +302,7 @@ template <typename T>
 int transpose_impl(const speck_dcsr* A, speck_dcsr* At)
 {
     if (!A || !At) return SPECK_ERR_INVALID;
+    if (A->nnz > kExpandRowsNnzMax) return SPECK_ERR_NNZ_OVERFLOW;  // (before the count is narrowed, and before anything is allocated)
     const u32 nnz = (u32)A->nnz, rows = (u32)A->rows, cols = (u32)A->cols;
     int rc = speck_dcsr_alloc(At, cols, rows, nnz, 1, sizeof(T));
     if (rc != SPECK_OK) return rc;
@@ -411,7 +416,7 @@ int tplan_create_impl(const speck_dcsr* A, speck_tplan** out, speck_tplan_info* 
 {
     if (!A || !out) return SPECK_ERR_INVALID;
     if (A->rows > (1ull << 27) || A->cols > (1ull << 27)) return SPECK_ERR_DIM_LIMIT;
-    if (A->nnz >= (1ull << 32)) return SPECK_ERR_NNZ_OVERFLOW;
+    if (A->nnz > kExpandRowsNnzMax) return SPECK_ERR_NNZ_OVERFLOW;  // (expand_rows_kernel)
     if (A->rows && !A->row_offsets) return SPECK_ERR_INVALID;
     if (A->nnz && (!A->col_ids || A->rows == 0 || A->cols == 0)) return SPECK_ERR_INVALID;
     if (!device_present()) return SPECK_ERR_NO_DEVICE;

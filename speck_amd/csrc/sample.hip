@@ -57,6 +57,8 @@ constexpr u32 kCheckGrid = 2048, kIdsGrid = 1024;                               
 constexpr u32 kGroupGrid = 2048, kLdsGrid = 2048, kLongGrid = 1024, kCopyTileRows = 256;  // workgroups of a launch at most
 constexpr u32 kTileRows = 4096;  // rows of a tile whose ends LDS holds
 
+constexpr u64 kSampleEntriesMax = (1ull << 32) - 1024;  // of A, and of the gathered rows: SPECK_ERR_NNZ_OVERFLOW beyond
+
 struct SampleStatus {
     u32 invalid;             // offsets of A, a row index, an id of a gathered row, the index inside A's entries
     u32 max_row;             // the longest row of C
@@ -549,7 +551,8 @@ int sample_run(SampleScratch* sc, hipStream_t s, const speck_dcsr* A, const spec
     rc = read_status(s, st, &h);
     if (rc != SPECK_OK) return rc;
     if (h.invalid) return SPECK_ERR_INVALID;
-    if (h.gross >= (1ull << 32) || h.nnz_out >= (1ull << 32)) return SPECK_ERR_NNZ_OVERFLOW;  // (the offsets wrapped: nothing has read them)
+    // (2^32: the offsets wrapped, nothing has read them; repeats in the list can make the gathered rows pass the copy's limit too)
+    if (h.gross > kSampleEntriesMax || h.nnz_out >= (1ull << 32)) return SPECK_ERR_NNZ_OVERFLOW;
     if (n == 0) return publish_empty_c(C, A->cols, sizeof(T), s, out);
 
     // ---- C
@@ -610,7 +613,8 @@ int sample_impl(speck_config* cfg, const speck_dcsr* A, const speck_sample_param
     if (p->index_bytes != 4 && p->index_bytes != 8) return SPECK_ERR_INVALID;
     if (p->row_base > (1ull << 62)) return SPECK_ERR_INVALID;
     if (A->rows > (1ull << 27) || A->cols > (1ull << 27) || p->n_rows > (1ull << 27)) return SPECK_ERR_DIM_LIMIT;
-    if (A->nnz >= (1ull << 32)) return SPECK_ERR_NNZ_OVERFLOW;
+    // (sample_copy_kernel numbers the kept entries of a tile of 256 rows in 32 bits and steps by 1024)
+    if (A->nnz > kSampleEntriesMax) return SPECK_ERR_NNZ_OVERFLOW;
     if (!csr_args_ok(A, true) || (A->nnz && (A->rows == 0 || A->cols == 0))) return SPECK_ERR_INVALID;
     if (!p->d_row_index && p->n_rows != A->rows) return SPECK_ERR_INVALID;
     if (shares_buffer(C, A)) return SPECK_ERR_INVALID;

@@ -504,7 +504,8 @@ int topk_impl(speck_config* cfg, const speck_dcsr* A, const speck_topk_params* p
     if (p->mode != SPECK_TOPK_LARGEST && p->mode != SPECK_TOPK_SMALLEST && p->mode != SPECK_TOPK_LARGEST_ABS) return SPECK_ERR_INVALID;
     if (p->reserved != 0) return SPECK_ERR_INVALID;
     if (A->rows > (1ull << 27) || A->cols > (1ull << 27)) return SPECK_ERR_DIM_LIMIT;
-    if (A->nnz >= (1ull << 32)) return SPECK_ERR_NNZ_OVERFLOW;
+    // (topk_copy_kernel numbers the kept entries of a tile of 256 rows in 32 bits and steps by 1024)
+    if (A->nnz > (1ull << 32) - 1024) return SPECK_ERR_NNZ_OVERFLOW;
     if (!csr_args_ok(A, true) || (A->nnz && (A->rows == 0 || A->cols == 0))) return SPECK_ERR_INVALID;
     if (shares_buffer(C, A)) return SPECK_ERR_INVALID;
     if (info) *info = speck_topk_info{};

@@ -260,11 +260,17 @@ def structure():
     return cached("structure", make)
 
 
-def view_matrix(dtype, kind="int"):
-    """THE view: integers in [-1024, 1024] or reals over twelve decades"""
+def view_matrix(dtype, kind="int", values=None):
+    """THE view: integers in [-1024, 1024] or reals over twelve decades -- or, under another name for `kind`, what
+    values(n, dtype) gives (test_gpu_high_offsets_side.py: the values of an operation's own test file on this structure)"""
     def make():
         ro, ci, _ = structure()
-        data = V.ints(len(ci), 4, dtype) if kind == "int" else V.real_values(len(ci), 4, dtype)
+        if values is not None:
+            assert kind not in ("int", "real")
+            data = np.ascontiguousarray(values(len(ci), np.dtype(dtype).type))
+            assert data.dtype == np.dtype(dtype) and data.shape == (len(ci),)
+        else:
+            data = V.ints(len(ci), 4, dtype) if kind == "int" else V.real_values(len(ci), 4, dtype)
         data.setflags(write=False)
         return sa.HostCSR(len(ro) - 1, COLS, ro, ci, data)
     return cached(("view", np.dtype(dtype).name, kind), make)
