@@ -579,8 +579,8 @@ int speck_scale_f32(speck_config *cfg, const speck_dcsr *A, const speck_scale_pa
  *  The entries are walked in tiles of SPECK_SPMV_TILE_ENTRIES, the reduction's, aligned to absolute positions; one path for
  *      every row length.  The 16-byte loads need data and col_ids on 16-byte boundaries; elsewhere the entries are loaded
  *      one by one, with the same results.
- *  Not built (A^T x: speck_spmm_t_* below with k = 1): vectors in float; a semiring other than (+, x); a spmv fused into the product
- *      that made A.  (Several right-hand sides: speck_spmm_* below.) ---- */
+ *  Not built (A^T x: speck_spmm_t_* below with k = 1; (min, +) and kin: speck_spmv_sr_* below): vectors in float; a spmv
+ *      fused into the product that made A.  (Several right-hand sides: speck_spmm_* below.) ---- */
 #define SPECK_SPMV_TILE_ENTRIES 4096
 typedef struct speck_spmv_info {
     uint64_t rows_empty;   /* rows without an entry: s_i = +0.0 */
@@ -626,8 +626,8 @@ int speck_spmv_f32(speck_config *cfg, double alpha, const speck_dcsr *A, const d
  *      blocks of SPECK_SPMM_COLUMN_BLOCK whose gathers are in flight together -- one 16-byte load per entry and pair of
  *      columns where d_X lies on a 16-byte boundary and ldx is even, 8-byte loads elsewhere, with the same results.
  *  info: rows_empty, rows_split, tiles and entries as speck_spmv_info -- they describe A, not k.
- *  Not built (A^T X: speck_spmm_t_* below; float blocks: speck_spmm_*_b32 below): column-major vectors; a semiring other
- *      than (+, x). ---- */
+ *  Not built (A^T X: speck_spmm_t_* below; float blocks: speck_spmm_*_b32 below; (min, +) and kin: speck_spmm_sr_* below):
+ *      column-major vectors. ---- */
 #define SPECK_SPMM_MAX_RHS 1024
 #define SPECK_SPMM_COLUMN_BLOCK 4
 typedef struct speck_spmm_info {
@@ -641,6 +641,61 @@ int speck_spmm_f64(speck_config *cfg, double alpha, const speck_dcsr *A, const d
                    double beta, double *d_Y, uint64_t ldy, speck_spmm_info *info /* may be NULL */);
 int speck_spmm_f32(speck_config *cfg, double alpha, const speck_dcsr *A, const double *d_X, uint64_t ldx, uint32_t k,
                    double beta, double *d_Y, uint64_t ldy, speck_spmm_info *info);
+
+/* ---- products over a (min | max, + | x | second) semiring (new: the reference has no counterpart): what shortest paths and
+ *      hop counts ((min, +)), label propagation for connected components ((min, second)), widest or most reliable paths
+ *      ((max, x) on probabilities) and "best neighbour" queries need on a matrix that is already on the device.
+ *      s_i = (+)_{(i,j) in A} (a_ij (x) x_j), where (+) is min or max and (x) is
+ *          PLUS   (double)a_ij + x[j]          TIMES   (double)a_ij * x[j]          SECOND   x[j] alone,
+ *      then y_i = s_i where d_z == NULL and y_i = z_i (+) s_i otherwise.  A row without entries has s_i = the identity:
+ *      +inf for min, -inf for max.  With SECOND A->data is NEVER dereferenced: it may be NULL or garbage, and a NaN there
+ *      does not show.  Vectors and blocks are doubles for both value types as for speck_spmv_* / speck_spmm_*: x / X
+ *      indexed by the column id, y / Y / z / Z by the row INSIDE A; blocks row-major, X(j,c) = d_X[j ldx + c], with
+ *      ld >= k and k <= SPECK_SPMM_MAX_RHS; the padding of a row of a block is neither read nor written.
+ *  Values: one rounding per term, nothing fused.  min and max PROPAGATE a NaN (fmin would drop it): a NaN in x, an
+ *      inf + -inf, a 0 * inf, a NaN in A (PLUS / TIMES) or a NaN in z lands in exactly the rows -- and for blocks the
+ *      column -- that reference it, and in no other.  The sign of a zero result is unspecified.  min and max are EXACT,
+ *      so every combination order gives the same value and the following hold with no tolerance: the same values from
+ *      run to run; a row-range view gives the rows of the whole; float A equals the call on the widened matrix; column c
+ *      of speck_spmm_sr_* equals speck_spmv_sr_* on contiguous copies of column c.
+ *  info->changed counts the elements with y_new != z_old compared as doubles (a NaN equals a NaN, +0.0 equals -0.0); 0
+ *      where d_z == NULL.  It is counted by the kernel that writes y, in integers, and comes back in the call's one
+ *      read-back: it ends a relaxation loop without a download of y.
+ *  Aliasing: x and z are only read; z may overlap x in any way or BE x (y = x (+) A (x) x: a Bellman-Ford step between
+ *      two ping-pong buffers, no copy).  z may be exactly y -- the same pointer and, for blocks, the same ld: in place,
+ *      every element is read and then written by the one thread that owns it.  Refused with SPECK_ERR_INVALID before
+ *      anything runs: the range (for blocks the SPAN, padding included, as for speck_spmm_*) of y overlapping that of x;
+ *      y overlapping z in any other way than being identical; any of the three pointers equal to one of A's; an unknown
+ *      semiring; ld < k; and the NULL pointers speck_spmm_* refuses (d_z and, with SECOND, A->data may be NULL).
+ *      Dimension and nnz limits, rows == 0, k == 0 as speck_spmm_*; nnz == 0 gives the identity, or z.
+ *  Safety as for speck_spmv_* / speck_spmm_*: the offsets are checked before an entry is read; an id >= cols raises the
+ *      verdict, is clamped and never followed; only the kernel queued last writes y, after it has seen the verdict of every
+ *      tile; on any error NOTHING of y is written and *info is zero.  All index arithmetic i ld + c is 64-bit.  No
+ *      floating-point atomic; one read-back, at the end.  Config stream, cfg == NULL and guard_bytes as there; the
+ *      temporaries are grow-only buffers of the config's own, neither those of speck_spmv_* nor those of speck_spmm_*.
+ *  The tiles and the walk are speck_spmv_*'s and speck_spmm_*'s (blocks of SPECK_SPMM_COLUMN_BLOCK columns, 16-byte
+ *      gathers where d_X lies on a 16-byte boundary and ldx is even).
+ *  Not built: argmin / parent pointers; a frontier mask; vectors in float; (or, and) on bit vectors; a semiring SpGEMM;
+ *      A^T through the transpose plan (transpose A once instead). ---- */
+enum { SPECK_SR_MIN_PLUS = 0, SPECK_SR_MAX_PLUS = 1, SPECK_SR_MIN_TIMES = 2, SPECK_SR_MAX_TIMES = 3,
+       SPECK_SR_MIN_SECOND = 4, SPECK_SR_MAX_SECOND = 5 };
+typedef struct speck_semiring_info {
+    uint64_t rows_empty;   /* rows without an entry: s_i = the identity */
+    uint64_t rows_split;   /* rows whose entries lie in more than one tile */
+    uint64_t tiles;        /* tiles walked (each once, for all columns) */
+    uint64_t entries;      /* entries read = nnz */
+    uint64_t terms;        /* terms formed = entries * k (k = 1 for a vector) */
+    uint64_t changed;      /* elements of y that differ from z (0 where z == NULL) */
+} speck_semiring_info;
+int speck_spmv_sr_f64(speck_config *cfg, int semiring, const speck_dcsr *A, const double *d_x,
+                      const double *d_z /* may be NULL */, double *d_y, speck_semiring_info *info /* may be NULL */);
+int speck_spmv_sr_f32(speck_config *cfg, int semiring, const speck_dcsr *A, const double *d_x,
+                      const double *d_z, double *d_y, speck_semiring_info *info);
+int speck_spmm_sr_f64(speck_config *cfg, int semiring, const speck_dcsr *A, const double *d_X, uint64_t ldx, uint32_t k,
+                      const double *d_Z /* may be NULL */, uint64_t ldz, double *d_Y, uint64_t ldy,
+                      speck_semiring_info *info /* may be NULL */);
+int speck_spmm_sr_f32(speck_config *cfg, int semiring, const speck_dcsr *A, const double *d_X, uint64_t ldx, uint32_t k,
+                      const double *d_Z, uint64_t ldz, double *d_Y, uint64_t ldy, speck_semiring_info *info);
 
 /* ---- sampled dense-dense product (new: the reference has no counterpart): C = alpha (U V^T) on A's pattern + beta A, the
  *      one map (block, block) -> matrix beside speck_spmm_* ((matrix, block) -> block): d(i,j) = sum_c U(i,c) V(j,c) is

@@ -28,4 +28,7 @@ from .api import (  # noqa: F401
     sddmm, sddmm_lanes, SddmmInfo, SDDMM_MAX_K, SDDMM_TILE_ENTRIES, SDDMM_AXPBY, SDDMM_HADAMARD, SDDMM_MODES,
     softmax, softmax_backward, SoftmaxInfo, SOFTMAX_NORMALIZED, SOFTMAX_EXP, SOFTMAX_BACKWARD, SOFTMAX_MODES,
     SOFTMAX_TILE_ENTRIES,
+    spmv_sr, spmm_sr, SemiringInfo, SEMIRINGS, SR_MIN_PLUS, SR_MAX_PLUS, SR_MIN_TIMES, SR_MAX_TIMES, SR_MIN_SECOND,
+    SR_MAX_SECOND,
 )
+from .graph import sssp, connected_components  # noqa: F401

@@ -97,6 +97,12 @@ class CSpmmInfo(C.Structure):
                 ("terms", C.c_uint64)]
 
 
+class CSemiringInfo(C.Structure):
+    # include/speck_c_api.h: speck_semiring_info
+    _fields_ = [("rows_empty", C.c_uint64), ("rows_split", C.c_uint64), ("tiles", C.c_uint64), ("entries", C.c_uint64),
+                ("terms", C.c_uint64), ("changed", C.c_uint64)]
+
+
 class CSddmmParams(C.Structure):
     # include/speck_c_api.h: speck_sddmm_params
     _fields_ = [("mode", C.c_uint32), ("k", C.c_uint32), ("alpha", C.c_double), ("beta", C.c_double),
@@ -232,6 +238,12 @@ _SIGS = {
                                  C.c_uint64, _P(CSpmmInfo)]),
     "speck_spmm_f32": (C.c_int, [C.c_void_p, C.c_double, _P(DCsr), C.c_void_p, C.c_uint64, C.c_uint32, C.c_double, C.c_void_p,
                                  C.c_uint64, _P(CSpmmInfo)]),
+    "speck_spmv_sr_f64": (C.c_int, [C.c_void_p, C.c_int, _P(DCsr), C.c_void_p, C.c_void_p, C.c_void_p, _P(CSemiringInfo)]),
+    "speck_spmv_sr_f32": (C.c_int, [C.c_void_p, C.c_int, _P(DCsr), C.c_void_p, C.c_void_p, C.c_void_p, _P(CSemiringInfo)]),
+    "speck_spmm_sr_f64": (C.c_int, [C.c_void_p, C.c_int, _P(DCsr), C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64,
+                                    C.c_void_p, C.c_uint64, _P(CSemiringInfo)]),
+    "speck_spmm_sr_f32": (C.c_int, [C.c_void_p, C.c_int, _P(DCsr), C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64,
+                                    C.c_void_p, C.c_uint64, _P(CSemiringInfo)]),
     "speck_sddmm_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(CSddmmParams), _P(DCsr), _P(CSddmmInfo)]),
     "speck_sddmm_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(CSddmmParams), _P(DCsr), _P(CSddmmInfo)]),
     "speck_softmax_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(CSoftmaxParams), _P(DCsr), _P(CSoftmaxInfo)]),

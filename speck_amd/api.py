@@ -884,6 +884,83 @@ def spmm(A, X, config, alpha=1.0, beta=0.0, Y=None, k=None, ldx=None, ldy=None, 
     return (_download_block(buf, A.rows * k, "spmm", blocks).reshape(A.rows, k) if buf is not None else None), SpmmInfo(info)
 
 
+# include/speck_c_api.h: SPECK_SR_*
+SR_MIN_PLUS, SR_MAX_PLUS, SR_MIN_TIMES, SR_MAX_TIMES, SR_MIN_SECOND, SR_MAX_SECOND = range(6)
+SEMIRINGS = {"min_plus": SR_MIN_PLUS, "max_plus": SR_MAX_PLUS, "min_times": SR_MIN_TIMES, "max_times": SR_MAX_TIMES,
+             "min_second": SR_MIN_SECOND, "max_second": SR_MAX_SECOND}
+
+
+class SemiringInfo(_Info):
+    """speck_semiring_info: A's counts as SpmmInfo has them, terms = entries * k, and changed: the elements of the result
+    that differ from z (0 without a z)."""
+    _fields = ("rows_empty", "rows_split", "tiles", "entries", "terms", "changed")
+
+
+def _semiring(semiring, op):
+    if isinstance(semiring, str):
+        if semiring not in SEMIRINGS:
+            raise ValueError(f"{op}: unknown semiring {semiring!r} (one of {', '.join(SEMIRINGS)})")
+        return SEMIRINGS[semiring]
+    if isinstance(semiring, (bool, float)) or not hasattr(semiring, "__index__") or int(semiring) not in SEMIRINGS.values():
+        raise ValueError(f"{op}: unknown semiring {semiring!r}")
+    return int(semiring)
+
+
+def spmv_sr(A, x, config, semiring="min_plus", z=None, y=None):
+    """y = [z (+)] A (x) x over a semiring on a device matrix (speck_spmv_sr_f64 / _f32): s_i = (+) over the entries (i, j) of
+    a_ij (x) x[j], where (+) is min or max and (x) is a + x[j] ("plus"), a * x[j] ("times") or x[j] alone ("second": A's
+    values are never read).  semiring is "min_plus", "max_plus", "min_times", "max_times", "min_second" or "max_second" (or
+    its SR_* number).  y = s without z, y = z (+) s with one; a row without entries has s_i = +inf (min) or -inf (max).
+    x (A.cols), z and y (A.rows, indexed by the row inside A) are float64 device vectors as spmv takes them.  z may be x (a
+    relaxation step between two buffers) or y (in place); y may not overlap x.  min and max are exact and propagate a NaN:
+    the result equals numpy's minimum / maximum.reduceat in value, NaN where that has one, from run to run and on a
+    row_view.  info.changed counts the elements with y != z (NaN equal to NaN): a loop ends on it without a download.
+    y=None: the result is a numpy array downloaded from a buffer of the library's allocator.  config may be None.
+    Returns (that array, or None where y was given and holds the result on the device, SemiringInfo)."""
+    sr = _semiring(semiring, "spmv_sr")
+    x_ptr = _device_vector(x, A.cols, "x", "spmv_sr")
+    z_ptr = _device_vector(z, A.rows, "z", "spmv_sr")
+    y_ptr = _device_vector(y, A.rows, "y", "spmv_sr")
+    L = _lib.load()
+    fn = L.speck_spmv_sr_f32 if A.dtype == np.float32 else L.speck_spmv_sr_f64
+    buf = None
+    if y is None:
+        buf = _dev_f64(A.rows)
+        y_ptr = buf._c.data
+    info = _lib.CSemiringInfo()
+    _check(fn(config._h if config is not None else None, sr, C.byref(A._c), x_ptr, z_ptr, y_ptr, C.byref(info)), "spmv_sr")
+    return (_download_f64(buf, A.rows, "spmv_sr") if buf is not None else None), SemiringInfo(info)
+
+
+def spmm_sr(A, X, config, semiring="min_plus", Z=None, Y=None, k=None, ldx=None, ldz=None, ldy=None):
+    """Y = [Z (+)] A (x) X over a semiring with k right-hand sides (speck_spmm_sr_f64 / _f32): spmv_sr per column, A read once
+    for all of them.  X (A.cols x k), Z and Y (A.rows x k) are row-major float64 device blocks as spmm takes them: a 2-D
+    object with data_ptr(), shape, stride() and dtype, or a device address with k (and ldx / ldz / ldy, default k).  Column
+    c equals spmv_sr on contiguous copies of column c; the padding between the rows of Y is neither read nor written.  Z
+    may be X, or Y with the same leading dimension (in place); the memory Y spans may not overlap what X spans (two
+    column slices of one tensor do and are refused).  Y=None: the result is a (rows, k) numpy array.  config may be None.
+    Returns (that array, or None where Y was given and holds the result on the device, SemiringInfo)."""
+    sr = _semiring(semiring, "spmm_sr")
+    x_ptr, k, ldx = _device_block(X, A.cols, k, ldx, "X", op="spmm_sr")
+    z_ptr, ldz_ = None, k
+    if Z is not None:
+        z_ptr, _, ldz_ = _device_block(Z, A.rows, k, ldz, "Z", op="spmm_sr")
+    if Y is not None:
+        y_ptr, _, ldy = _device_block(Y, A.rows, k, ldy, "Y", op="spmm_sr")
+    if k < 0 or ldx < k or ldz_ < k or (Y is not None and ldy < k):
+        raise ValueError(f"spmm_sr: k = {k} with ldx = {ldx}, ldz = {ldz_}, ldy = {ldy}: a leading dimension is at least k >= 0")
+    L = _lib.load()
+    fn = L.speck_spmm_sr_f32 if A.dtype == np.float32 else L.speck_spmm_sr_f64
+    buf = None
+    if Y is None:
+        buf = _dev_f64(A.rows * k)
+        y_ptr, ldy = buf._c.data, k
+    info = _lib.CSemiringInfo()
+    _check(fn(config._h if config is not None else None, sr, C.byref(A._c), x_ptr, ldx, k, z_ptr, ldz_, y_ptr, ldy, C.byref(info)),
+           "spmm_sr")
+    return (_download_f64(buf, A.rows * k, "spmm_sr").reshape(A.rows, k) if buf is not None else None), SemiringInfo(info)
+
+
 class TplanInfo(_Info):
     """speck_tplan_info: the matrix a transpose plan was made from, its empty and longest columns, the plan's device bytes."""
     _fields = ("rows", "cols", "nnz", "cols_empty", "max_col_entries", "bytes")

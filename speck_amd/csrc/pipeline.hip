@@ -244,6 +244,8 @@ struct speck_config {
     ScaleScratch sddmm;  // ... and of speck_sddmm_* (sddmm.hip): scale's pair of buffers, its own
     TileScratch softmax;  // ... and of speck_softmax_* (softmax.hip): two sets of tile records, the m and s of the split rows
     TileScratch spmm_t;  // ... and of speck_spmm_t_* (spmm_t.hip): the records of the plan's tiles, the column sums
+    TileScratch spmv_sr;  // ... and of speck_spmv_sr_* (semiring.hip)
+    TileScratch spmm_sr;  // ... and of speck_spmm_sr_* (semiring.hip): its own, as spmm's is not spmv's
     CooScratch coo;  // ... and of speck_from_coo_* / speck_to_coo (coo.hip): the status block, the keys and buffers of the sort
     ExtractScratch extract;  // ... and of speck_extract_* (extract.hip): the rows' lengths and offsets, the keep bytes
     TopKScratch topk;  // ... and of speck_topk_* (topk.hip): the row lists, the kept entries per row, the new row offsets
@@ -2015,6 +2017,8 @@ TileScratch* spmm_scratch(speck_config* c) { return &c->spmm; }
 ScaleScratch* sddmm_scratch(speck_config* c) { return &c->sddmm; }
 TileScratch* softmax_scratch(speck_config* c) { return &c->softmax; }
 TileScratch* spmm_t_scratch(speck_config* c) { return &c->spmm_t; }
+TileScratch* spmv_sr_scratch(speck_config* c) { return &c->spmv_sr; }
+TileScratch* spmm_sr_scratch(speck_config* c) { return &c->spmm_sr; }
 CooScratch* coo_scratch(speck_config* c) { return &c->coo; }
 ExtractScratch* extract_scratch(speck_config* c) { return &c->extract; }
 TopKScratch* topk_scratch(speck_config* c) { return &c->topk; }
@@ -2142,6 +2146,8 @@ int speck_config_destroy(speck_config* c)
     c->sddmm.release();
     c->softmax.release();
     c->spmm_t.release();
+    c->spmv_sr.release();
+    c->spmm_sr.release();
     c->coo.release();
     c->extract.release();
     c->topk.release();
@@ -2237,6 +2243,8 @@ int speck_config_set_option(speck_config* c, const char* name, int64_t value)
         c->sddmm.release();
         c->softmax.release();
         c->spmm_t.release();
+        c->spmv_sr.release();
+        c->spmm_sr.release();
         c->coo.release();
         c->extract.release();
         c->topk.release();

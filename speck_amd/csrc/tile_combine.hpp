@@ -187,6 +187,27 @@ __device__ __forceinline__ void load_entries(const TileFrame& f, bool wide, cons
     }
 }
 
+// The column ids alone, as load_entries<true> leaves them in c, for a caller that never reads the values (the SECOND
+// semirings of semiring.hip: A->data may be null).  wide: the tile is whole and col lies on a 16-byte boundary.
+__device__ __forceinline__ void load_ids(const TileFrame& f, bool wide, const u32* __restrict__ col, u32* c)
+{
+    const u64 q0 = f.tile0 + u64(threadIdx.x) * kPer;
+    if (wide) {
+        const Vec<u32, 4>* cs = reinterpret_cast<const Vec<u32, 4>*>(col + q0);
+        Vec<u32, 4> cv[kPer / 4];
+#pragma unroll
+        for (u32 k = 0; k < kPer / 4; ++k) cv[k] = cs[k];
+#pragma unroll
+        for (u32 k = 0; k < kPer; ++k) c[k] = cv[k / 4].v[k % 4];
+    } else {
+#pragma unroll
+        for (u32 k = 0; k < kPer; ++k) {
+            const u64 p = q0 + k;
+            c[k] = (p >= f.lo && p < f.hi) ? col[p] : 0u;
+        }
+    }
+}
+
 // whether entry k of the thread (load_entries) lies in [lo, hi) -- in a tile that is not whole, the entries the matrix
 // reaches: the term of any other is the identity
 __device__ __forceinline__ bool entry_in(const TileFrame& f, u32 k)

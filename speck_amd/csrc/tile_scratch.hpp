@@ -1,5 +1,6 @@
-// tile_scratch.hpp -- what speck_reduce_*, speck_spmv_*, speck_spmm_*, speck_softmax_* and speck_spmm_t_* (reduce.hip,
-// spmv.hip, spmm.hip, softmax.hip, spmm_t.hip) need from a config (pipeline.hip owns the structure).
+// tile_scratch.hpp -- what speck_reduce_*, speck_spmv_*, speck_spmm_*, speck_softmax_*, speck_spmm_t_*, speck_spmv_sr_* and
+// speck_spmm_sr_* (reduce.hip, spmv.hip, spmm.hip, softmax.hip, spmm_t.hip, semiring.hip) need from a config (pipeline.hip
+// owns the structure).
 #pragma once
 #include "host_common.hpp"
 
@@ -23,5 +24,8 @@ TileScratch* spmv_scratch(speck_config* c);
 TileScratch* spmm_scratch(speck_config* c);
 TileScratch* softmax_scratch(speck_config* c);
 TileScratch* spmm_t_scratch(speck_config* c);
+// (semiring.hip: neither spmv's nor spmm's -- a wide spmm_sr does not grow the buffers of a spmv)
+TileScratch* spmv_sr_scratch(speck_config* c);
+TileScratch* spmm_sr_scratch(speck_config* c);
 
 }  // namespace speck
