@@ -1276,6 +1276,89 @@ int speck_sample_f64(speck_config *cfg, const speck_dcsr *A, const speck_sample_
 int speck_sample_f32(speck_config *cfg, const speck_dcsr *A, const speck_sample_params *p, speck_dcsr *C,
                      speck_sample_info *info);
 
+/* ---- assembly from blocks (new: the reference has no counterpart; the "hstack / vstack" and the "blocked or batched
+ *      graphs" two blocks above name): C = bmat(grid) -- a grid of block_rows x block_cols cells that hold matrices already
+ *      on the device, an absent cell a zero block.  block_diag(G_1 .. G_n) makes one matrix of n small graphs, so that sddmm ->
+ *      softmax -> spmm, or one speck_multiply_* (block_diag(A_i) block_diag(B_i) = block_diag(A_i B_i)), runs once instead
+ *      of n times; [[H, A^T], [A, 0]] is a saddle-point system; vstack puts row shards back, hstack the column slices of a
+ *      column-split product: one call each, nothing leaves the device.
+ *  Block row g has the height h_g = row_sizes[g] where row_sizes is given, else the common `rows` of the blocks of block row
+ *      g; block column q the width w_q likewise.  R0 and C0 are their running sums (the ORIGINS).  Row R0_g + i of C is the
+ *      concatenation, in ascending q, of row i of every block present in block row g, each column id with C0_q added, each
+ *      value copied bit for bit (NaN payloads, -0.0 and subnormals survive).  Nothing is sorted, summed or dropped: rows of
+ *      the blocks need not be sorted or free of duplicates; where every block has strictly ascending rows C has them too and is
+ *      a valid input of speck_multiply_*.  With the cells of block row g in ascending q numbered 0 .. nb_g - 1, a PIECE is
+ *      (output row, block present in that row's block row): piece P0_g + i nb_g + q is row i of block q of block row g, the
+ *      pieces in this order are the entries of C in order, G = [0, cumsum(piece lengths)], and C.row_offsets[r] = G[first
+ *      piece of r].
+ *  blocks: HOST, n_blocks cells in ANY order (a sparse list: a block_diag of 1000 graphs is 1000 descriptors, not a million
+ *      pointers).  A block may be a row-range view with absolute offsets, each with its own base; one matrix may stand in
+ *      several cells; all blocks hold the call's value type.  A block with 0 rows or 0 columns, n_blocks == 0 with both size
+ *      arrays given, and a result with no entry (C then owns buffers of one entry) are all valid.
+ *  speck_bmat_layout is exactly the host computation the device call starts with, on its own: no device, no config.  It
+ *      returns the shape, nnz = the sum of the blocks' nnz, the pieces and, where the arrays are given, the origins -- where
+ *      graph i's vertices land in the batch.  It refuses what the device call refuses on the host, with the same status,
+ *      and then writes nothing.
+ *  SPECK_ERR_INVALID with NOTHING written -- not C's struct, not its allocations, not the contents of buffers it would reuse:
+ *      NULL p, C or M; n_blocks > 0 with NULL blocks; a cell outside the grid; a cell named twice; a line of the grid with
+ *      neither a block nor a size; a block that disagrees with its line; a block with nnz > 0 and a NULL buffer, no row or no
+ *      column; C sharing a buffer with any block; in any block offsets that descend, leave [ro[0], ro[0] + nnz] or whose last
+ *      one does not span nnz (every row of every block is checked; an unsound offset is clamped, never followed); a column id
+ *      >= cols OF ITS OWN BLOCK -- such an id may be smaller than cols(C), so only a per-block check finds it, and without
+ *      it the entry would land in a neighbour block's columns.  SPECK_ERR_DIM_LIMIT, decided on the host: n_blocks >
+ *      SPECK_BMAT_MAX_BLOCKS; rows or cols of C or of any block above 2^27; 2^32 pieces or more (a 64-bit count); 8 bytes per
+ *      piece that the config's scratch cannot hold.  SPECK_ERR_NNZ_OVERFLOW: the blocks' nnz sum to 2^32 or more (a 64-bit
+ *      sum on the host, before anything runs).  *info is zero once the arguments have passed, and again on an error.
+ *  The sum of the blocks' nnz is known before anything runs, so C's buffers are prepared first and the call has ONE read-back,
+ *      at the end.  CHECK: a thread per piece against the table of blocks uploaded once per call (three pointers, rows, cols,
+ *      nnz, C0); its block row by a search in P0, i and q by a division; the row's two offsets; the piece's length, 0 where
+ *      they are unsound; the shared scan gives G.  IDS: the tile kernel below in a mode that writes nothing compares every id
+ *      with its own block's cols.  PLACE: one workgroup per tile of SPECK_BMAT_TILE_ENTRIES output entries, four consecutive
+ *      ones per thread, whatever the row and block sizes; the tile's pieces by two searches in G, per piece its end, its
+ *      source offset and its block in LDS (up to 4096 pieces; a tile that more touch reads them from global memory).  A tile
+ *      that touches only block rows of a single block (vstack, block_diag) takes the blocks themselves for its units: a
+ *      shift per block from origins the host made, neither G nor a row offset is read.  Every kernel that writes into C's
+ *      buffers, the row offsets included, is queued behind the checks and does nothing where the verdict is raised; the host
+ *      reads the status once (verdict, empty rows, longest row) and only then publishes C.  Values move as integers; no
+ *      floating-point instruction and no atomic on anything but the two counters of the statistics: the same bytes from run
+ *      to run.  16-byte loads and stores only where the address allows; every form gives the same bytes.
+ *  Ownership of C as speck_select_* documents it: row_offsets reused when C->rows == rows(C), data / col_ids re-allocated
+ *      only when C->nnz differs.  There is no in-place mode.  Runs on the config's stream (speck_config_set_stream is
+ *      honoured: blocks produced on that stream need no synchronisation in front of the call) and returns with C complete.
+ *      Temporaries are grow-only buffers of the config's own (not the multiply's arena): 48 bytes per block, 4 per output
+ *      row, 8 per piece; cfg == NULL is allowed as for speck_sort_rows_*.  With the debug option guard_bytes the canary
+ *      zones of the temporaries and of C are checked after the call.
+ *  Not built: blocks of mixed value type, or pattern-only blocks; overlapping placements that add (assembly by speck_add_*);
+ *      a fused sort; a Kronecker product; the batch vector itself (torch's repeat_interleave on the returned origins); a plan
+ *      reused across calls; writing into a region of an existing C. ---- */
+#define SPECK_BMAT_MAX_BLOCKS 65536
+#define SPECK_BMAT_TILE_ENTRIES 4096
+typedef struct speck_bmat_block {
+    uint32_t block_row, block_col;           /* the cell */
+    const speck_dcsr *M;                     /* what stands there (the struct on the HOST, its buffers on the device) */
+} speck_bmat_block;
+typedef struct speck_bmat_params {
+    uint32_t block_rows, block_cols, n_blocks;
+    const speck_bmat_block *blocks;          /* HOST, n_blocks cells in ANY order; a cell named twice is refused */
+    const uint64_t *row_sizes, *col_sizes;   /* HOST, block_rows / block_cols entries; either may be NULL */
+} speck_bmat_params;
+typedef struct speck_bmat_info {
+    uint64_t blocks;             /* cells that hold a block = n_blocks */
+    uint64_t rows_out;           /* rows of C */
+    uint64_t cols_out;           /* columns of C */
+    uint64_t nnz_out;            /* entries of C = the sum of the blocks' nnz */
+    uint64_t pieces;             /* (output row, block of its block row) pairs */
+    uint64_t rows_empty;         /* rows of C without an entry */
+    uint64_t max_row_entries;    /* the longest row of C */
+} speck_bmat_info;
+typedef struct speck_bmat_layout_out {       /* all HOST; the arrays may be NULL */
+    uint64_t rows, cols, nnz, pieces;
+    uint64_t *row_origins, *col_origins;     /* block_rows + 1 / block_cols + 1 entries */
+} speck_bmat_layout_out;
+int speck_bmat_layout(const speck_bmat_params *p, speck_bmat_layout_out *out);   /* host only: no device, no config */
+int speck_bmat_f64(speck_config *cfg, const speck_bmat_params *p, speck_dcsr *C, speck_bmat_info *info /* may be NULL */);
+int speck_bmat_f32(speck_config *cfg, const speck_bmat_params *p, speck_dcsr *C, speck_bmat_info *info);
+
 /* ---- row-sharded multi-GPU (new: the reference is single-GPU, source/Executor.cpp:25).  One process per GPU;
  *      rank p multiplies the row range [b_p, b_{p+1}) of A (a view with absolute offsets, boundaries from
  *      speck_partition_rows) with a replicated B, then ONE exchange concatenates the shards on a root rank:

@@ -25,6 +25,7 @@ from .api import (  # noqa: F401
     topk, TopKInfo, TOPK_LARGEST, TOPK_SMALLEST, TOPK_LARGEST_ABS, TOPK_MODES, TOPK_GROUP_MAX, TOPK_LDS_MAX,
     sample_neighbors, SampleInfo, SAMPLE_WITHOUT_REPLACEMENT, SAMPLE_WITH_REPLACEMENT, SAMPLE_GROUP_MAX, SAMPLE_LDS_MAX,
     SAMPLE_TILE_ENTRIES,
+    bmat, vstack, hstack, block_diag, bmat_layout, BmatInfo, BmatLayout, BMAT_TILE_ENTRIES, BMAT_MAX_BLOCKS,
     sddmm, sddmm_lanes, SddmmInfo, SDDMM_MAX_K, SDDMM_TILE_ENTRIES, SDDMM_AXPBY, SDDMM_HADAMARD, SDDMM_MODES,
     softmax, softmax_backward, SoftmaxInfo, SOFTMAX_NORMALIZED, SOFTMAX_EXP, SOFTMAX_BACKWARD, SOFTMAX_MODES,
     SOFTMAX_TILE_ENTRIES,

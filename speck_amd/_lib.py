@@ -191,6 +191,29 @@ class CSampleInfo(C.Structure):
                 ("nnz_out", C.c_uint64), ("max_row_entries", C.c_uint64)]
 
 
+class CBmatBlock(C.Structure):
+    # include/speck_c_api.h: speck_bmat_block
+    _fields_ = [("block_row", C.c_uint32), ("block_col", C.c_uint32), ("M", C.POINTER(DCsr))]
+
+
+class CBmatParams(C.Structure):
+    # include/speck_c_api.h: speck_bmat_params
+    _fields_ = [("block_rows", C.c_uint32), ("block_cols", C.c_uint32), ("n_blocks", C.c_uint32),
+                ("blocks", C.POINTER(CBmatBlock)), ("row_sizes", C.POINTER(C.c_uint64)), ("col_sizes", C.POINTER(C.c_uint64))]
+
+
+class CBmatInfo(C.Structure):
+    # include/speck_c_api.h: speck_bmat_info
+    _fields_ = [("blocks", C.c_uint64), ("rows_out", C.c_uint64), ("cols_out", C.c_uint64), ("nnz_out", C.c_uint64),
+                ("pieces", C.c_uint64), ("rows_empty", C.c_uint64), ("max_row_entries", C.c_uint64)]
+
+
+class CBmatLayoutOut(C.Structure):
+    # include/speck_c_api.h: speck_bmat_layout_out
+    _fields_ = [("rows", C.c_uint64), ("cols", C.c_uint64), ("nnz", C.c_uint64), ("pieces", C.c_uint64),
+                ("row_origins", C.POINTER(C.c_uint64)), ("col_origins", C.POINTER(C.c_uint64))]
+
+
 # every symbol include/speck_c_api.h declares, with its ctypes signature
 _P = C.POINTER
 _SIGS = {
@@ -273,6 +296,9 @@ _SIGS = {
     "speck_topk_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(CTopKParams), _P(DCsr), _P(CTopKInfo)]),
     "speck_sample_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(CSampleParams), _P(DCsr), _P(CSampleInfo)]),
     "speck_sample_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(CSampleParams), _P(DCsr), _P(CSampleInfo)]),
+    "speck_bmat_layout": (C.c_int, [_P(CBmatParams), _P(CBmatLayoutOut)]),
+    "speck_bmat_f64": (C.c_int, [C.c_void_p, _P(CBmatParams), _P(DCsr), _P(CBmatInfo)]),
+    "speck_bmat_f32": (C.c_int, [C.c_void_p, _P(CBmatParams), _P(DCsr), _P(CBmatInfo)]),
     "speck_compare_f32": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), C.c_int, C.c_double, _P(C.c_uint64)]),
     "speck_compare_bounded_f64": (C.c_int, [C.c_void_p, _P(DCsr), _P(DCsr), _P(DCsr), C.c_double, _P(C.c_uint64),
                                             _P(C.c_uint64)]),

@@ -1343,6 +1343,174 @@ def permute(A, row_perm=None, col_perm=None, config=None, matOut=None, canonical
     return extract(A, rows=row_perm, col_map=cmap, out_cols=A.cols, config=config, matOut=matOut, canonical=canonical, who="permute")
 
 
+# include/speck_c_api.h: SPECK_BMAT_TILE_ENTRIES (the output entries of a tile of bmat's id check and placing pass),
+# SPECK_BMAT_MAX_BLOCKS (the cells a grid may name)
+BMAT_TILE_ENTRIES = 4096
+BMAT_MAX_BLOCKS = 65536
+
+
+class BmatInfo(_Info):
+    """speck_bmat_info: the blocks, the shape and the entries of the result, its pieces -- (output row, block of its block
+    row) pairs --, its rows without an entry and its longest row."""
+    _fields = ("blocks", "rows_out", "cols_out", "nnz_out", "pieces", "rows_empty", "max_row_entries")
+
+
+class BmatLayout:
+    """speck_bmat_layout_out: the shape, the entries and the pieces of a grid's result, and the origins of its block rows
+    and block columns (block_rows + 1 / block_cols + 1 ints: line g covers [origins[g], origins[g + 1]))."""
+
+    def __init__(self, rows, cols, nnz, pieces, row_origins, col_origins):
+        self.rows, self.cols, self.nnz, self.pieces = rows, cols, nnz, pieces
+        self.row_origins, self.col_origins = row_origins, col_origins
+
+    def __repr__(self):
+        return f"BmatLayout(rows={self.rows}, cols={self.cols}, nnz={self.nnz}, pieces={self.pieces})"
+
+
+def _bmat_sizes(sizes, n, what, who):
+    if sizes is None:
+        return None
+    sizes = list(sizes)
+    if len(sizes) != n or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0 for v in sizes):
+        raise ValueError(f"{who}: {what} must hold {n} non-negative integers")
+    return [int(v) for v in sizes]
+
+
+def _bmat_cells(blocks, row_sizes, col_sizes, who):
+    """A grid given as a list of lists (None: a zero block) as (cells, block_rows, block_cols): checked without asking
+    any cell for an address."""
+    if not isinstance(blocks, (list, tuple)) or any(not isinstance(line, (list, tuple)) for line in blocks):
+        raise ValueError(f"{who}: blocks must be a list of lists of dCSR or None")
+    block_rows = len(blocks)
+    block_cols = len(blocks[0]) if block_rows else (len(col_sizes) if col_sizes is not None else 0)
+    if any(len(line) != block_cols for line in blocks):
+        raise ValueError(f"{who}: blocks is ragged: every block row must name {block_cols} cells")
+    cells = []
+    for g, line in enumerate(blocks):
+        for q, m in enumerate(line):
+            if m is None:
+                continue
+            if not isinstance(m, dCSR):
+                raise ValueError(f"{who}: the cell ({g}, {q}) must be a dCSR or None, not {type(m).__name__}")
+            cells.append((g, q, m))
+    return cells, block_rows, block_cols
+
+
+def _bmat_params(cells, block_rows, block_cols, row_sizes, col_sizes, who):
+    """The checks the wrappers make themselves, then speck_bmat_params with everything it points to: (params, keep, dtype)."""
+    row_sizes = _bmat_sizes(row_sizes, block_rows, "row_sizes", who)
+    col_sizes = _bmat_sizes(col_sizes, block_cols, "col_sizes", who)
+    if len(cells) > BMAT_MAX_BLOCKS:
+        raise ValueError(f"{who}: {len(cells)} blocks are beyond the limit of {BMAT_MAX_BLOCKS}")
+    dtypes = {m.dtype for _, _, m in cells}
+    if len(dtypes) > 1:
+        raise TypeError(f"{who}: the blocks hold {sorted(str(d) for d in dtypes)}: blocks of mixed value type are not converted")
+    for sizes, n, at, line in ((row_sizes, block_rows, 0, "block row"), (col_sizes, block_cols, 1, "block column")):
+        if sizes is None:
+            named = {c[at] for c in cells}
+            missing = [g for g in range(n) if g not in named]
+            if missing:
+                raise ValueError(f"{who}: {line} {missing[0]} has neither a block nor a size")
+    arr = (_lib.CBmatBlock * max(len(cells), 1))()
+    for k, (g, q, m) in enumerate(cells):
+        arr[k].block_row, arr[k].block_col, arr[k].M = g, q, C.pointer(m._c)
+    p = _lib.CBmatParams()
+    p.block_rows, p.block_cols, p.n_blocks = block_rows, block_cols, len(cells)
+    p.blocks = arr if cells else None
+    rs = (C.c_uint64 * max(block_rows, 1))(*row_sizes) if row_sizes is not None else None
+    cs = (C.c_uint64 * max(block_cols, 1))(*col_sizes) if col_sizes is not None else None
+    p.row_sizes, p.col_sizes = rs, cs
+    return p, (arr, rs, cs, cells), (dtypes.pop() if dtypes else None)
+
+
+def _bmat_layout(p, who):
+    out = _lib.CBmatLayoutOut()
+    ro = (C.c_uint64 * (p.block_rows + 1))()
+    co = (C.c_uint64 * (p.block_cols + 1))()
+    out.row_origins, out.col_origins = ro, co
+    _check(_lib.load().speck_bmat_layout(C.byref(p), C.byref(out)), who)
+    return BmatLayout(int(out.rows), int(out.cols), int(out.nnz), int(out.pieces), tuple(int(v) for v in ro), tuple(int(v) for v in co))
+
+
+def bmat_layout(blocks, row_sizes=None, col_sizes=None):
+    """What bmat(blocks, ...) would build, from the host alone (speck_bmat_layout: no device, no config): a BmatLayout with the
+    shape, nnz, the pieces and the origins of the block rows and block columns."""
+    cells, block_rows, block_cols = _bmat_cells(blocks, row_sizes, col_sizes, "bmat_layout")
+    p, keep, _ = _bmat_params(cells, block_rows, block_cols, row_sizes, col_sizes, "bmat_layout")
+    return _bmat_layout(p, "bmat_layout")
+
+
+def _bmat_call(cells, block_rows, block_cols, config, row_sizes, col_sizes, matOut, return_info, who, dtype=None, return_offsets=False):
+    p, keep, found = _bmat_params(cells, block_rows, block_cols, row_sizes, col_sizes, who)
+    if matOut is not None and any(m is matOut for _, _, m in cells):
+        raise ValueError(f"{who}: matOut is one of the blocks (there is no in-place form)")
+    dtype = found if found is not None else np.dtype(dtype) if dtype is not None else matOut.dtype if matOut is not None else np.dtype(np.float64)
+    if dtype not in (np.float32, np.float64):
+        raise TypeError(f"{who}: the values must be float32 or float64, not {dtype}")
+    L = _lib.load()
+    fn = L.speck_bmat_f32 if dtype == np.float32 else L.speck_bmat_f64
+    if matOut is None:
+        matOut = dCSR(dtype)
+    if matOut.dtype != dtype:
+        matOut.reset()
+        matOut.dtype = np.dtype(dtype)
+    info = _lib.CBmatInfo()
+    _check(fn(config._h if config is not None else None, C.byref(p), C.byref(matOut._c), C.byref(info)), who)
+    matOut._host_row_offsets = None  # (row_offsets were rewritten on the device)
+    res = (matOut, BmatInfo(info)) if return_info else (matOut,)
+    if return_offsets:
+        lay = _bmat_layout(p, who)
+        res += (lay.row_origins, lay.col_origins)
+    del keep
+    return res if len(res) > 1 else res[0]
+
+
+def bmat(blocks, config, row_sizes=None, col_sizes=None, matOut=None, return_info=False, dtype=None):
+    """C = the device matrix assembled from a grid of device matrices (speck_bmat_f64 / _f32; scipy.sparse.bmat without the
+    sort): blocks is a list of block rows, each a list of dCSR or None (a zero block).  Row i of block row g of C is the
+    concatenation, in ascending block column, of row i of its blocks, each column id shifted by its block column's origin,
+    each value copied bit for bit; nothing is sorted, summed or dropped.  A block row's height is row_sizes[g] where
+    row_sizes is given, else the common rows of its blocks (columns likewise): a line with neither a block nor a size, a
+    ragged grid, a cell that is no dCSR and a matOut that is one of the blocks raise ValueError, blocks of mixed dtype
+    TypeError (they are never converted).  A block may be a row_view, one matrix may stand in several cells.  config may be
+    None; dtype names the value type of a grid without a block.  Returns matOut, or (matOut, BmatInfo) with return_info."""
+    cells, block_rows, block_cols = _bmat_cells(blocks, row_sizes, col_sizes, "bmat")
+    return _bmat_call(cells, block_rows, block_cols, config, row_sizes, col_sizes, matOut, return_info, "bmat", dtype)
+
+
+def _bmat_list(mats, who):
+    if not isinstance(mats, (list, tuple)) or any(not isinstance(m, dCSR) for m in mats):
+        raise ValueError(f"{who}: mats must be a list of dCSR")
+    return list(mats)
+
+
+def vstack(mats, config, matOut=None, return_info=False):
+    """The matrices one below the other (scipy.sparse.vstack): a bmat grid of one column.  They share their cols."""
+    mats = _bmat_list(mats, "vstack")
+    if not mats:
+        raise ValueError("vstack: mats is empty (bmat with row_sizes and col_sizes builds a matrix without a block)")
+    return _bmat_call([(g, 0, m) for g, m in enumerate(mats)], len(mats), 1, config, None, None, matOut, return_info, "vstack")
+
+
+def hstack(mats, config, matOut=None, return_info=False):
+    """The matrices side by side (scipy.sparse.hstack, entries of a row in the order of the list): a bmat grid of one row."""
+    mats = _bmat_list(mats, "hstack")
+    if not mats:
+        raise ValueError("hstack: mats is empty (bmat with row_sizes and col_sizes builds a matrix without a block)")
+    return _bmat_call([(0, q, m) for q, m in enumerate(mats)], 1, len(mats), config, None, None, matOut, return_info, "hstack")
+
+
+def block_diag(mats, config, matOut=None, return_info=False, return_offsets=False, dtype=None):
+    """block_diag(G_1 .. G_n) (scipy.sparse.block_diag): n descriptors, not n^2 cells.  One matrix of a batch of graphs, or
+    the operand of a batched product: block_diag(A_i) block_diag(B_i) = block_diag(A_i B_i).  return_offsets=True also
+    returns the row and the column origins (n + 1 ints each, from bmat_layout): graph i owns the rows
+    [row_origins[i], row_origins[i + 1]) -- torch.repeat_interleave on their differences is the batch vector."""
+    mats = _bmat_list(mats, "block_diag")
+    n = len(mats)
+    return _bmat_call([(i, i, m) for i, m in enumerate(mats)], n, n, config, [] if n == 0 else None, [] if n == 0 else None, matOut,
+                      return_info, "block_diag", dtype, return_offsets)
+
+
 # include/speck_c_api.h: SPECK_TOPK_*; SPECK_TOPK_GROUP_MAX / SPECK_TOPK_LDS_MAX (rows of more than k entries up to this many:
 # ranked by a group of 8 / 16 / 32 / 64 lanes -- up to GROUP_MAX / 8, / 4, / 2, GROUP_MAX entries -- / selected by one
 # workgroup with the row's keys in LDS; longer ones are selected from global memory)

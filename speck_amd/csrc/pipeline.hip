@@ -38,6 +38,7 @@
 #include "extract.hpp"
 #include "topk.hpp"
 #include "sample.hpp"
+#include "bmat.hpp"
 
 using namespace speck;
 
@@ -250,6 +251,7 @@ struct speck_config {
     ExtractScratch extract;  // ... and of speck_extract_* (extract.hip): the rows' lengths and offsets, the keep bytes
     TopKScratch topk;  // ... and of speck_topk_* (topk.hip): the row lists, the kept entries per row, the new row offsets
     SampleScratch sample;  // ... and of speck_sample_* (sample.hip): the row lists, the rows' sources, lengths and offsets
+    BmatScratch bmat;  // ... and of speck_bmat_* (bmat.hip): the tables of blocks and groups, the piece lengths and their scan
     const void* zones_arena = nullptr;
     u64 zones_m = 0, zones_nnz = 0, zones_gap = 0;
     bool gpool_zones_filled = false;
@@ -2023,6 +2025,7 @@ CooScratch* coo_scratch(speck_config* c) { return &c->coo; }
 ExtractScratch* extract_scratch(speck_config* c) { return &c->extract; }
 TopKScratch* topk_scratch(speck_config* c) { return &c->topk; }
 SampleScratch* sample_scratch(speck_config* c) { return &c->sample; }
+BmatScratch* bmat_scratch(speck_config* c) { return &c->bmat; }
 }  // namespace speck
 
 extern "C" {
@@ -2152,6 +2155,7 @@ int speck_config_destroy(speck_config* c)
     c->extract.release();
     c->topk.release();
     c->sample.release();
+    c->bmat.release();
     if (c->pred.off) (void)guarded_free(c->pred.off);
     if (c->gpred.off) (void)guarded_free(c->gpred.off);
     if (c->d_stats) (void)hipFree(c->d_stats);
@@ -2249,6 +2253,7 @@ int speck_config_set_option(speck_config* c, const char* name, int64_t value)
         c->extract.release();
         c->topk.release();
         c->sample.release();
+        c->bmat.release();
     }
     else if (n == "sort_reg_max") c->sort.reg_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_REG_MAX);
     else if (n == "sort_lds_max") c->sort.lds_max = (u32)std::min<int64_t>(std::max<int64_t>(value, 0), SPECK_SORT_LDS_MAX);
